@@ -128,6 +128,67 @@ def fixture_parity(m, dev):
             "within_tolerance": all(v < 1e-3 for v in res.values())}
 
 
+DUMP_BYTES = 64 * 10**6    # --dump-outputs: all files together (all ranks), .npy headers included
+
+
+def _arrays(out):
+    """(name, tensor) for every tensor of a forward's output dict; nested dicts / lists are flattened as <key>.<subkey> and
+    <key>.<i>.  A container already visited under another key is skipped (with --gs and no voxel merge, preds["splats"] IS
+    preds["splats_raw"])."""
+    seen = set()
+
+    def walk(v, name):
+        if isinstance(v, torch.Tensor):
+            yield name, v
+        elif isinstance(v, (dict, list, tuple)) and id(v) not in seen:
+            seen.add(id(v))
+            items = v.items() if isinstance(v, dict) else enumerate(v)
+            for k, x in items:
+                yield from walk(x, f"{name}.{k}" if name else str(k))
+    yield from walk(out, "")
+
+
+def _pixel_axes(t, n_pix):
+    """Number of leading axes of t that enumerate the n_pix pixels of the views ([1, n, H, W, ...] or [1, n*H*W, ...]), else 0."""
+    if t.dim() < 2 or t.shape[0] != 1:
+        return 0
+    p = 1
+    for i in range(1, t.dim()):
+        p *= t.shape[i]
+        if p == n_pix:
+            return i + 1
+        if p > n_pix:
+            return 0
+    return 0
+
+
+def dump_outputs(out, path, n_pix, budget=DUMP_BYTES, suffix=""):
+    """Writes every array of one forward's outputs as <path>/<name><suffix>.npy (float32; float64 stays float64).  When the set
+    exceeds `budget` bytes, each per-pixel array keeps the SAME pixels, a fixed sample drawn with torch.randperm(n_pix) on a
+    CPU generator seeded 0, in pixel order ([K, channels...] instead of [1, n, H, W, channels...]); the other arrays are
+    written whole.  So the files of two builds run with the same arguments compare element for element.  Returns the number of
+    pixels kept per per-pixel array."""
+    import numpy as np
+    arrs = [(name, t.detach(), _pixel_axes(t, n_pix)) for name, t in _arrays(out)]
+    size = lambda t: 8 if t.dtype == torch.float64 else 4
+    header = 1024 * len(arrs)
+    whole = sum(t.numel() * size(t) for _, t, ax in arrs if not ax)
+    per_pix = sum(t.numel() // n_pix * size(t) for _, t, ax in arrs if ax)
+    if whole + header > budget:
+        raise ValueError(f"--dump-outputs: {whole} bytes of non-pixel outputs exceed the {budget}-byte budget")
+    keep = n_pix if per_pix == 0 else min(n_pix, (budget - whole - header) // per_pix)
+    idx = None
+    if keep < n_pix:
+        idx = torch.randperm(n_pix, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    os.makedirs(path, exist_ok=True)
+    for name, t, ax in arrs:
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        if ax and idx is not None:
+            t = t.reshape((n_pix,) + tuple(t.shape[ax:])).index_select(0, idx.to(t.device))
+        np.save(os.path.join(path, name + suffix + ".npy"), t.cpu().numpy())
+    return keep
+
+
 def two_pass_overlap(set_overlap, forward, timed, allreduce_max, profile_once=None, bound=2.5e-3,
                      keys=("pts3d", "depth", "normals", "camera_params")):
     """N > 1: let the run decide by itself whether the K|V all-gather of the global layers goes on the compute queue (comm_overlap 0:
@@ -181,7 +242,12 @@ def main():
                     help="N > 1: the K|V exchange as ncclAllGather (default) or as one group of point-to-point sends / receives (direct over the xGMI mesh; opt-in, never run on hardware)")
     ap.add_argument("--tiny", action="store_true", help="scaled-down architecture (plumbing check only)")
     ap.add_argument("--gs", action="store_true", help="3D-Gaussian head on (BASELINE config C5's flag set with --dtype f16; rasterisation not run, voxel merge off)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; at most 64 MB in all: past that a fixed "
+                         "seeded sample of the pixels, the same for every per-pixel array; N > 1: <name>.rank<r>.npy per rank)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from hunyuanworld_mirror_amd import WorldMirror, WMConfig
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -238,18 +304,28 @@ def main():
         torch.cuda.synchronize(dev)
         log(f"warmup {i} done")
 
+    last = {}       # outputs of the last timed step, by comm_overlap mode (None at N = 1)
+    mode = [None]
+
     def timed():
-        """EXACTLY a.steps forwards between two (barrier + synchronize) brackets; this rank's ms per step"""
+        """EXACTLY a.steps forwards between two (barrier + synchronize) brackets; this rank's ms per step.  The last step's outputs
+        are kept in last[mode]; the earlier steps' are dropped at once, so that every step reuses the same allocator blocks."""
         sync()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for _ in range(a.steps - 1):
             m(views, flags)
+        out = m(views, flags)
         sync()
+        last[mode[0]] = out
         return (time.perf_counter() - t0) / a.steps * 1e3
 
     overlap_info = None
     if world > 1:
         from hunyuanworld_mirror_amd import _lib as _wl
+
+        def set_overlap(v):
+            mode[0] = v
+            _wl.lib().wm_set_tuning(b"comm_overlap", v)
 
         def allmax(x):
             t = torch.tensor([float(x)], device=dev, dtype=torch.float64)
@@ -271,11 +347,16 @@ def main():
             o = m(views, flags)
             torch.cuda.synchronize(dev)
             return o
-        pick, ms_step, overlap_info = two_pass_overlap(lambda v: _wl.lib().wm_set_tuning(b"comm_overlap", v), fwd, timed, allmax, prof_once)
+        pick, ms_step, overlap_info = two_pass_overlap(set_overlap, fwd, timed, allmax, prof_once)
         log(f"two-pass gather decision: {overlap_info['ms_per_step']} -> comm_overlap {pick} (comparison passed: {overlap_info['comparison_passed']})")
     else:
+        pick = None
         ms_step = timed()
     log(f"timed region done: {ms_step:.2f} ms/step")
+    if a.dump_outputs:
+        keep = dump_outputs(last[pick], a.dump_outputs, n_local * H * W, DUMP_BYTES // world, suffix=f".rank{rank}" if world > 1 else "")
+        log(f"outputs of the last timed step written to {a.dump_outputs} ({keep} of {n_local * H * W} pixels per per-pixel array)")
+    last.clear()
 
     # per-kernel-class timing: HIP events recorded by the library on the launch stream (one extra step)
     m.profile(True)

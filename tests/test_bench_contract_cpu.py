@@ -77,3 +77,41 @@ def test_two_pass_gather_decision_logic():
     assert pick == 0 and not info["comparison_passed"]
     pick, info = run(10.0, 5.0, 0.0, nan=True)          # non-finite output
     assert pick == 0 and not info["comparison_passed"]
+
+
+def test_dump_outputs_budget_and_fixed_pixel_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every output array is written as float32 .npy; over the byte budget the per-pixel arrays
+    keep one and the same seeded pixel sample (so that the files of two builds compare element for element) while the small arrays
+    stay whole, the total stays within the budget, and a container reachable under two keys is written once."""
+    import numpy as np
+    import torch
+    b = _bench()
+    n, H, W = 2, 20, 30
+    n_pix = n * H * W
+    g = torch.Generator().manual_seed(5)
+    pix = torch.arange(n_pix, dtype=torch.float32)           # each pixel carries its own index in every per-pixel array
+    raw = {"means": pix.reshape(1, n_pix, 1).repeat(1, 1, 3), "weights": pix.reshape(1, n_pix)}
+    out = {"camera_params": torch.rand(1, n, 9, generator=g), "depth": pix.reshape(1, n, H, W, 1),
+           "pts3d": pix.reshape(1, n, H, W, 1).repeat(1, 1, 1, 1, 3).double(), "splats_raw": raw, "splats": raw}
+    keep = b.dump_outputs(out, str(tmp_path / "all"), n_pix)             # fits: everything whole
+    assert keep == n_pix
+    files = sorted(p.name for p in (tmp_path / "all").iterdir())
+    assert files == ["camera_params.npy", "depth.npy", "pts3d.npy", "splats_raw.means.npy", "splats_raw.weights.npy"]
+    d = np.load(tmp_path / "all" / "depth.npy")
+    assert d.dtype == np.float32 and d.shape == (1, n, H, W, 1) and np.array_equal(d.ravel(), pix.numpy())
+    assert np.load(tmp_path / "all" / "pts3d.npy").dtype == np.float64
+    budget = 16 * 1024
+    runs = []
+    for r in range(2):
+        path = tmp_path / f"s{r}"
+        keep = b.dump_outputs(out, str(path), n_pix, budget=budget)
+        assert 0 < keep < n_pix
+        assert sum(p.stat().st_size for p in path.iterdir()) <= budget
+        runs.append({p.name: np.load(p) for p in path.iterdir()})
+    s = runs[0]
+    assert np.array_equal(s["camera_params.npy"], out["camera_params"].numpy())
+    idx = s["depth.npy"][:, 0]
+    assert idx.shape == (keep,) and np.all(np.diff(idx) > 0)            # pixel order, no repeats
+    assert np.array_equal(s["pts3d.npy"], np.repeat(idx[:, None], 3, 1))
+    assert np.array_equal(s["splats_raw.means.npy"][:, 0], idx) and np.array_equal(s["splats_raw.weights.npy"], idx)
+    assert all(np.array_equal(s[k], runs[1][k]) for k in s)             # the same sample on every run

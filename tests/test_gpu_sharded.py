@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden, rel_l2
+from conftest import ROOT, load_golden, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -201,7 +201,7 @@ assert torch.equal(out2['pts3d'], out['pts3d']) and torch.equal(out2['depth'], o
 print('rccl world-1 p2p gather: bit-identical')
 """
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     print(r.stdout[-500:], r.stderr[-1500:])
     assert r.returncode == 0
 
