@@ -52,6 +52,7 @@ EXPORTS = [
     "wm_op_gemm", "wm_op_gemm_resid_ln", "wm_op_gemm_qkv", "wm_op_attention", "wm_op_layernorm", "wm_op_qkv_post", "wm_op_conv", "wm_op_bilinear",
     "wm_op_linear_f32", "wm_host_to_16", "wm_set_tuning", "wm_op_attention_split", "wm_op_attention_ex", "wm_op_attention_flag_count", "wm_op_gs_splat", "wm_op_conv3x3_up", "wm_depth_to_world", "wm_confidence_mask", "wm_confidence_mask_workspace_bytes", "wm_preprocess_image", "wm_preprocess_image_size",
     "wm_preprocess_image_workspace_bytes", "wm_rasterize_splats", "wm_rasterize_workspace_bytes", "wm_prune_gs", "wm_prune_gs_workspace_bytes", "wm_op_up_conv_n32", "wm_op_conv3x3_gemm16", "wm_op_conv_ex", "wm_op_upconv3x3_tap", "wm_op_tconv", "wm_op_upconv_gather",
+    "wm_depth_edge", "wm_normals_edge", "wm_point_filter_mask_workspace_bytes", "wm_point_filter_mask",
 ]
 
 _lib = None
@@ -117,6 +118,14 @@ def lib() -> C.CDLL:
     L.wm_confidence_mask_workspace_bytes.restype = C.c_size_t
     L.wm_confidence_mask.argtypes = [vp, C.c_size_t, f32, vp, vp, C.c_size_t, vp]
     L.wm_confidence_mask.restype = i32
+    L.wm_depth_edge.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, vp]
+    L.wm_depth_edge.restype = i32
+    L.wm_normals_edge.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, vp, vp]
+    L.wm_normals_edge.restype = i32
+    L.wm_point_filter_mask_workspace_bytes.argtypes = [i32, i32, i32]
+    L.wm_point_filter_mask_workspace_bytes.restype = C.c_size_t
+    L.wm_point_filter_mask.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_double, i32, C.c_double, f32, vp, vp, vp, C.c_size_t, vp]
+    L.wm_point_filter_mask.restype = i32
     L.wm_op_up_conv_n32.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]
     L.wm_op_up_conv_n32.restype = i32
     L.wm_op_conv3x3_gemm16.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]

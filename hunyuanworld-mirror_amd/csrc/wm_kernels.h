@@ -190,6 +190,17 @@ hipError_t wm_launch_resample_v_tensor(const unsigned char* tmp, float* out, int
                                        const int* bounds, const int* kk, int ksize, hipStream_t s);
 size_t wm_confidence_mask_workspace(size_t n);
 hipError_t wm_launch_confidence_mask(const float* conf, size_t n, unsigned int K, unsigned char* mask, void* workspace, hipStream_t s);
+// point-cloud filter masks (pointmask.hip): depth_edge / normals_edge over S views of H x W (k = 3, 5, 7), and app.py's fused
+// per-view quantile + edge composition (out_de / out_ne optional: the two edge masks of the composition)
+hipError_t wm_launch_depth_edge(const float* depth, const unsigned char* mask, int S, int H, int W, int k, int has_atol, float atol,
+                                int has_rtol, float rtol, unsigned char* out, hipStream_t s);
+hipError_t wm_launch_normals_edge(const float* normals, const unsigned char* mask, int S, int H, int W, int k, double tol_deg,
+                                  unsigned char* out, hipStream_t s);
+size_t wm_point_filter_mask_workspace(int S, int H, int W);
+hipError_t wm_launch_point_filter_mask(const float* conf, const float* depth, const float* normals, int S, int H, int W, int apply_conf,
+                                       double percentile, int apply_edge, double normal_tol_deg, float depth_rtol,
+                                       float* thresholds_out, unsigned char* mask_out, unsigned char* out_de, unsigned char* out_ne,
+                                       void* ws, hipStream_t s);
 hipError_t wm_launch_dpt_tail(const float* y32, const float* w, const float* b, float* attr, float* conf,
                               size_t npix, int C, int act, hipStream_t s);
 enum { WM_ACT_INV_LOG = 0, WM_ACT_EXP = 1, WM_ACT_NORM = 2 };

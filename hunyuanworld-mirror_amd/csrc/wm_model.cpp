@@ -2211,6 +2211,29 @@ extern "C" wm_status wm_confidence_mask(const float* conf, size_t n, float conf_
   if (K > n) K = n;
   return wm_launch_confidence_mask(conf, n, (unsigned int)K, mask, workspace, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
+extern "C" wm_status wm_depth_edge(const float* depth, const unsigned char* mask, int S, int H, int W, int k, int has_atol, float atol,
+                                   int has_rtol, float rtol, unsigned char* out, void* stream) {
+  if (!depth || !out || S < 0 || H < 0 || W < 0 || (k != 3 && k != 5 && k != 7) || (long long)S * H * W >= (1LL << 31)) return WM_ERR_INVALID;
+  return wm_launch_depth_edge(depth, mask, S, H, W, k, has_atol, atol, has_rtol, rtol, out, (hipStream_t)stream) == hipSuccess ? WM_OK
+                                                                                                                           : WM_ERR_HIP;
+}
+extern "C" wm_status wm_normals_edge(const float* normals, const unsigned char* mask, int S, int H, int W, int k, double tol_deg,
+                                     unsigned char* out, void* stream) {
+  if (!normals || !out || S < 0 || H < 0 || W < 0 || (k != 3 && k != 5 && k != 7) || (long long)S * H * W >= (1LL << 31)) return WM_ERR_INVALID;
+  return wm_launch_normals_edge(normals, mask, S, H, W, k, tol_deg, out, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
+}
+extern "C" size_t wm_point_filter_mask_workspace_bytes(int S, int H, int W) { return wm_point_filter_mask_workspace(S, H, W); }
+extern "C" wm_status wm_point_filter_mask(const float* conf, const float* depth, const float* normals, int S, int H, int W, int apply_conf,
+                                          double percentile, int apply_edge, double normal_tol_deg, float depth_rtol, float* thresholds_out,
+                                          unsigned char* mask_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!mask_out || S < 0 || H < 0 || W < 0 || (long long)S * H * W >= (1LL << 31)) return WM_ERR_INVALID;
+  if ((apply_conf && !conf) || (apply_edge && (!depth || !normals))) return WM_ERR_INVALID;
+  if (apply_conf && !(percentile >= 0.0 && percentile <= 100.0)) return WM_ERR_INVALID;
+  if (!workspace || workspace_bytes < wm_point_filter_mask_workspace(S, H, W)) return WM_ERR_INVALID;
+  return wm_launch_point_filter_mask(conf, depth, normals, S, H, W, apply_conf, percentile, apply_edge, normal_tol_deg, depth_rtol,
+                                     thresholds_out, mask_out, nullptr, nullptr, workspace, (hipStream_t)stream) == hipSuccess ? WM_OK
+                                                                                                                               : WM_ERR_HIP;
+}
 extern "C" wm_status wm_depth_to_world(const float* depth, const float* extrinsic, const float* intrinsic, float* world, float* cam,
                                        unsigned char* mask, int B, int H, int W, float eps, void* stream) {
   if (!depth || !extrinsic || !intrinsic || B < 0 || H < 0 || W < 0) return WM_ERR_INVALID;

@@ -210,6 +210,27 @@ size_t wm_confidence_mask_workspace_bytes(size_t n);
 wm_status wm_confidence_mask(const float* conf, size_t n, float conf_threshold_percent, unsigned char* mask, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* Point-cloud filter masks: the per-view mask app.py:172-206 (run_model) builds for every export.
+ * All views are S x H x W, S*H*W < 2^31; k (window) is 3, 5 or 7; outputs are u8 0/1.  Bit-for-bit semantics of the
+ * reference's numpy code, including its transposed mask window in normals_edge and its NaN handling (pointmask.hip).
+ * depth_edge (src/utils/geometry.py:374-416): depth [S][H][W] f32, mask [S][H][W] u8 or NULL; atol / rtol apply when
+ * has_atol / has_rtol (compared in fp32, as numpy 2 compares a Python float against a float32 array). */
+wm_status wm_depth_edge(const float* depth, const unsigned char* mask, int S, int H, int W, int k, int has_atol, float atol,
+                        int has_rtol, float rtol, unsigned char* out, void* stream);
+/* normals_edge (src/utils/geometry.py:472-531): normals [S][H][W][3] f32, mask [S][H][W] u8 or NULL (with a mask, each view
+ * is the reference's 2-D call); tol in degrees (edge: fp64 angle > np.deg2rad(tol)). */
+wm_status wm_normals_edge(const float* normals, const unsigned char* mask, int S, int H, int W, int k, double tol_deg, unsigned char* out,
+                          void* stream);
+/* app.py:172-206 in one call: per view, conf_mask = conf >= np.quantile(conf[i], percentile / 100) (apply_conf; numpy's linear
+ * method, exact), then conf_mask & ~(depth_edge(depth[i], rtol=depth_rtol, mask) & normals_edge(normals[i], normal_tol_deg, mask))
+ * (apply_edge; mask = conf_mask or NULL, k = 3); neither flag: all ones.  conf / depth [S][H][W] f32, normals [S][H][W][3] f32,
+ * mask_out [S][H][W] u8, thresholds_out [S] f32 (the per-view np.quantile values; may be NULL).  workspace:
+ * wm_point_filter_mask_workspace_bytes(S, H, W) bytes of device memory. */
+size_t wm_point_filter_mask_workspace_bytes(int S, int H, int W);
+wm_status wm_point_filter_mask(const float* conf, const float* depth, const float* normals, int S, int H, int W, int apply_conf,
+                               double percentile, int apply_edge, double normal_tol_deg, float depth_rtol, float* thresholds_out,
+                               unsigned char* mask_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Operator-level entry (parity tests / A-B): F.interpolate(x, (Hi, Wi), bilinear, align_corners=True) (+ separable position tables
  * addx [Wi][Cin/2], addy [Hi][Cin/2], may be NULL) rounded to the 16-bit operand type, then Conv2d(Cin, 32, 3, padding=1) (+ ReLU):
  * the un-fused form the DPT tail uses for output_conv2[0] (dense_head.py:97-105,217-251).  up16: caller-owned device scratch of
