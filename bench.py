@@ -9,8 +9,14 @@ Workload (synthetic, random-init weights of the full 1.23 B-parameter architectu
   N > 1 : 8 views per GPU, view-sharded, K/V of every global-attention layer all-gathered over RCCL
           (N = 8 is BASELINE config C4: 64 views) -> "scaling": "weak" (views per GPU fixed).
 A step = one full forward of the whole job; value = total views / step time (inputs resident in HBM).
-The JSON line also carries `roofline` (dominant kernel class, HIP-event timed on the launch stream) and,
-at N = 1, `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample).
+
+A plain run does what the headline needs and nothing else: weights + inputs, W warm-up steps, K timed steps, the outputs of the last
+timed step if --dump-outputs is given, one JSON line (metric / value / unit / ms_per_step / config).  Everything else the benchmark
+measures sits behind --full, after and outside the timed region, and adds its own keys to the same line: `roofline` (per-kernel
+HIP-event times of one extra forward, dominant kernel against the MFMA peak) and, at N = 1, `north_star` (the C3 workload: 32 views,
+priors), `parity` (the timed build against the committed reference fixture) and `cpu_baseline` (the CPU oracle timed on the host
+cores); at N > 1, `multi_gpu.per_rank` (per-rank event times).  --no-north-star / --no-parity / --no-cpu-baseline drop single legs
+of a --full run.
 """
 from __future__ import annotations
 
@@ -73,6 +79,19 @@ def host_cores():
     except AttributeError:
         n = os.cpu_count() or 1
     return max(1, min(n, int(os.environ.get("WM_BENCH_CORES", "16"))))
+
+
+def synthetic_state_dict(cfg, threads):
+    """The package's deterministic synthetic weights (weights.iter_params, default seed and preset) as a {name: fp32 array} dict,
+    drawn on `threads` host threads.  Every tensor comes from its own Philox stream keyed on the parameter NAME (weights.py), so the
+    values depend neither on the order nor on the thread they are drawn in: bit for bit what iter_params yields serially, in a
+    fraction of its 10 s at the full 1.23 B parameters."""
+    from concurrent.futures import ThreadPoolExecutor
+    from hunyuanworld_mirror_amd.config import param_spec
+    from hunyuanworld_mirror_amd.weights import make_param
+    spec = param_spec(cfg)
+    with ThreadPoolExecutor(threads) as ex:
+        return dict(zip(spec, ex.map(lambda kv: make_param(*kv), spec.items())))
 
 
 def cpu_baseline(cfg, H, W, budget_views=8):
@@ -234,10 +253,13 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--priors", action="store_true",
                     help="camera-pose + intrinsics priors on (BASELINE config C3: --views-per-gpu 32 --priors), cond_flags [1, 0, 1]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-views", type=int, default=8, help="views of the CPU-baseline sample (8 = the C2 workload itself)")
-    ap.add_argument("--no-north-star", action="store_true", help="skip the C3 (32 views, priors) leg that follows the timed region at N = 1")
-    ap.add_argument("--no-parity", action="store_true", help="skip the committed-fixture parity leg that follows the timed region at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run everything else the benchmark measures: per-kernel / roofline step, and at N = 1 "
+                         "the north-star (C3) leg, the committed-fixture parity leg and the CPU baseline (minutes; off by default)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-oracle baseline")
+    ap.add_argument("--cpu-views", type=int, default=8, help="with --full: views of the CPU-baseline sample (8 = the C2 workload itself)")
+    ap.add_argument("--no-north-star", action="store_true", help="with --full: skip the C3 (32 views, priors) leg that follows the timed region at N = 1")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the committed-fixture parity leg that follows the timed region at N = 1")
     ap.add_argument("--gather", default="allgather", choices=["allgather", "p2p"],
                     help="N > 1: the K|V exchange as ncclAllGather (default) or as one group of point-to-point sends / receives (direct over the xGMI mesh; opt-in, never run on hardware)")
     ap.add_argument("--tiny", action="store_true", help="scaled-down architecture (plumbing check only)")
@@ -267,7 +289,8 @@ def main():
     n_local, n_total = a.views_per_gpu, a.views_per_gpu * world
     torch.set_num_threads(host_cores())
     log("generating + uploading weights")
-    m = WorldMirror(arch=cfg, dtype=a.dtype).to(dev).init_synthetic_weights()
+    m = WorldMirror(arch=cfg, dtype=a.dtype).to(dev)
+    m.load_state_dict(synthetic_state_dict(cfg, host_cores()), strict=True)   # = init_synthetic_weights(), drawn in parallel
     if a.gs:
         m.enable_prune = False   # the cross-view voxel merge is a caller's step (rasterization.py:301), not part of the forward's heads
     log("weights ready")
@@ -347,7 +370,7 @@ def main():
             o = m(views, flags)
             torch.cuda.synchronize(dev)
             return o
-        pick, ms_step, overlap_info = two_pass_overlap(set_overlap, fwd, timed, allmax, prof_once)
+        pick, ms_step, overlap_info = two_pass_overlap(set_overlap, fwd, timed, allmax, prof_once if a.full else None)
         log(f"two-pass gather decision: {overlap_info['ms_per_step']} -> comm_overlap {pick} (comparison passed: {overlap_info['comparison_passed']})")
     else:
         pick = None
@@ -357,6 +380,27 @@ def main():
         keep = dump_outputs(last[pick], a.dump_outputs, n_local * H * W, DUMP_BYTES // world, suffix=f".rank{rank}" if world > 1 else "")
         log(f"outputs of the last timed step written to {a.dump_outputs} ({keep} of {n_local * H * W} pixels per per-pixel array)")
     last.clear()
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    line = {"metric": "views/sec", "value": round(n_total / (ms_step * 1e-3), 3), "unit": "views/s", "n_gpus": world,
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
+            "head_dtype": "f16 MFMA operands, fp32 accumulate / residuals / activations (the reference's DPT heads are fp32: worldmirror.py:146); camera head fp32",
+            "data": "synthetic",
+            "config": {"workload": f"{n_total}-view {H}x{W} {a.dtype}, {'camera-pose + intrinsics priors' if a.priors else 'no priors'}, camera+depth+pointmap+normal" + ("+gaussian" if a.gs else "") + " heads, "
+                                   f"{n_local} views/GPU" + (", tiny arch" if a.tiny else ", full 1.23B-param arch"),
+                       "views_per_gpu": n_local, "global_views": n_total, "parallelism": f"view-shard x{world}",
+                       "collective": (f"RCCL {'grouped send/recv (direct)' if a.gather == 'p2p' else 'all-gather'} of K|V per global layer, world {m._comm[1]}" if m._comm else "none (1 GPU)")}}
+    if world > 1:
+        line["multi_gpu"] = {"gather_decision": overlap_info, "rccl_world": m._comm[1] if m._comm else 1}
+    if not a.full:     # a plain run ends here: the headline and what describes it
+        return finish()
 
     # per-kernel-class timing: HIP events recorded by the library on the launch stream (one extra step)
     m.profile(True)
@@ -445,16 +489,7 @@ def main():
                 "per_gpu_algorithmic_tflop": round(fl["total"] / 1e12, 2),
                 "whole_forward_tflops": round(fl["total"] / (ms_step * 1e-3) / 1e12, 1),
                 "whole_forward_frac": round(fl["total"] / (ms_step * 1e-3) / 1e12 / PEAK_TFLOPS, 4)}
-        line = {"metric": "views/sec", "value": round(n_total / (ms_step * 1e-3), 3), "unit": "views/s", "n_gpus": world,
-                "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True,
-                "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
-                "head_dtype": "f16 MFMA operands, fp32 accumulate / residuals / activations (the reference's DPT heads are fp32: worldmirror.py:146); camera head fp32",
-                "data": "synthetic",
-                "config": {"workload": f"{n_total}-view {H}x{W} {a.dtype}, {'camera-pose + intrinsics priors' if a.priors else 'no priors'}, camera+depth+pointmap+normal" + ("+gaussian" if a.gs else "") + " heads, "
-                                       f"{n_local} views/GPU" + (", tiny arch" if a.tiny else ", full 1.23B-param arch"),
-                           "views_per_gpu": n_local, "global_views": n_total, "parallelism": f"view-shard x{world}",
-                           "collective": (f"RCCL {'grouped send/recv (direct)' if a.gather == 'p2p' else 'all-gather'} of K|V per global layer, world {m._comm[1]}" if m._comm else "none (1 GPU)")},
-                "roofline": roof}
+        line["roofline"] = roof
         if north is not None:
             line["north_star"] = north
         if multi is not None:
@@ -463,10 +498,7 @@ def main():
             line["parity"] = fixture_parity(m, dev)
         if world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, H, W, a.cpu_views)
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

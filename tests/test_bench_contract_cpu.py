@@ -115,3 +115,31 @@ def test_dump_outputs_budget_and_fixed_pixel_sample(tmp_path):
     assert np.array_equal(s["pts3d.npy"], np.repeat(idx[:, None], 3, 1))
     assert np.array_equal(s["splats_raw.means.npy"][:, 0], idx) and np.array_equal(s["splats_raw.weights.npy"], idx)
     assert all(np.array_equal(s[k], runs[1][k]) for k in s)             # the same sample on every run
+
+
+def test_parallel_weight_draw_is_the_serial_one_bit_for_bit():
+    """bench.synthetic_state_dict draws the synthetic weights on several threads; the benchmark's inputs must stay what
+    WorldMirror.init_synthetic_weights() uploads: the same names in the same order, every tensor bit-identical."""
+    import numpy as np
+    from hunyuanworld_mirror_amd import WMConfig
+    from hunyuanworld_mirror_amd.weights import iter_params
+    b = _bench()
+    cfg = WMConfig.tiny(enable_gs=True)
+    got = b.synthetic_state_dict(cfg, 4)
+    ref = dict(iter_params(cfg))
+    assert list(got) == list(ref)
+    for k, v in ref.items():
+        assert got[k].dtype == np.float32 and got[k].shape == v.shape and got[k].tobytes() == v.tobytes(), k
+
+
+def test_full_option_exists_and_is_off_by_default():
+    """Everything beyond the headline (roofline step, north-star / parity legs, CPU baseline) sits behind --full: the option is in the
+    command line, and the options that drop single legs of a --full run are still accepted."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    for opt in ("--full", "--gpus", "--steps", "--warmup", "--dump-outputs", "--no-cpu-baseline", "--no-north-star", "--no-parity"):
+        assert opt in r.stdout, opt
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert re.search(r'add_argument\("--full", action="store_true"', src)
