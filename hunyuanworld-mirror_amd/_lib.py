@@ -53,6 +53,9 @@ EXPORTS = [
     "wm_op_linear_f32", "wm_host_to_16", "wm_set_tuning", "wm_op_attention_split", "wm_op_attention_ex", "wm_op_attention_flag_count", "wm_op_gs_splat", "wm_op_conv3x3_up", "wm_depth_to_world", "wm_confidence_mask", "wm_confidence_mask_workspace_bytes", "wm_preprocess_image", "wm_preprocess_image_size",
     "wm_preprocess_image_workspace_bytes", "wm_rasterize_splats", "wm_rasterize_workspace_bytes", "wm_prune_gs", "wm_prune_gs_workspace_bytes", "wm_op_up_conv_n32", "wm_op_conv3x3_gemm16", "wm_op_conv_ex", "wm_op_upconv3x3_tap", "wm_op_tconv", "wm_op_upconv_gather",
     "wm_depth_edge", "wm_normals_edge", "wm_point_filter_mask_workspace_bytes", "wm_point_filter_mask",
+    "wm_op_im2col", "wm_op_im2col7", "wm_op_dino_tokens", "wm_op_vgt_special", "wm_op_gemm_rowmap", "wm_op_gemm_convt", "wm_op_layernorm_rows",
+    "wm_op_bilinear_add", "wm_op_bilinear16", "wm_op_copy2d", "wm_op_small_attention", "wm_op_adaln", "wm_op_cam_update", "wm_op_cam_matrices",
+    "wm_op_linear_f32_ex",
 ]
 
 _lib = None
@@ -153,6 +156,21 @@ def lib() -> C.CDLL:
     L.wm_preprocess_image_workspace_bytes.restype = C.c_size_t
     L.wm_preprocess_image.argtypes = [vp, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]
     L.wm_preprocess_image.restype = i32
+    L.wm_op_im2col.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.wm_op_im2col7.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
+    L.wm_op_dino_tokens.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.wm_op_vgt_special.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.wm_op_gemm_rowmap.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.wm_op_gemm_convt.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.wm_op_layernorm_rows.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.wm_op_bilinear_add.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.wm_op_bilinear16.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.wm_op_copy2d.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    L.wm_op_small_attention.argtypes = [vp, vp, i32, i32, i32, vp]
+    L.wm_op_adaln.argtypes = [vp, vp, vp, i32, i32, f32, vp]
+    L.wm_op_cam_update.argtypes = [vp, vp, vp, i32, i32, vp]
+    L.wm_op_cam_matrices.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    L.wm_op_linear_f32_ex.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]
     L.wm_set_tuning.argtypes = [C.c_char_p, i32]
     L.wm_set_tuning.restype = i32
     _lib = L

@@ -2246,3 +2246,96 @@ extern "C" wm_status wm_op_linear_f32(const float* X, const float* Wp, const flo
                                       int post_act, void* stream) {
   return wm_launch_linear_f32(X, Wp, b, Y, M, N, K, ldx, N, pre_act, post_act, nullptr, 0, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
+
+// ---- operator-level entry points of the token front end and the camera head (tests/test_gpu_ops_frontend.py): args struct, launcher, status
+static wm_status op_status(hipError_t e) { return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP; }
+
+extern "C" wm_status wm_op_im2col(int dtype, const float* img, void* out, int N, int C, int H, int W, int ps, int Kpad, int normalize,
+                                  void* stream) {
+  if (!img || !out || N < 0 || C <= 0 || H <= 0 || W <= 0 || ps <= 0 || Kpad < C * ps * ps || (normalize && C != 3)) return WM_ERR_INVALID;
+  return op_status(wm_launch_im2col(img, out, N, C, H, W, ps, Kpad, normalize, dtype, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_im2col7(int dtype, const float* img, void* out, int N, int H, int W, int Kpad, void* stream) {
+  if (!img || !out || N < 0 || H <= 0 || W <= 0 || Kpad < 147) return WM_ERR_INVALID;
+  return op_status(wm_launch_im2col7(img, out, N, H, W, Kpad, dtype, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_dino_tokens(const float* patch, const float* cls, const float* reg, const float* pos, float* X, int N, int hw,
+                                       int R, int D, void* stream) {
+  if (!cls || !pos || !X || (R > 0 && !reg) || N <= 0 || hw < 0 || R < 0 || D <= 0) return WM_ERR_INVALID;
+  return op_status(wm_launch_dino_tokens(patch, cls, reg, pos, X, N, hw, R, D, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_vgt_special(float* X, const float* cam_tok, const float* reg_tok, const float* pose_tok, const float* ray_tok,
+                                       int N, int P, int R, int D, int cond, int first_view_global, void* stream) {
+  if (!X || !cam_tok || (R > 0 && !reg_tok) || N <= 0 || R < 0 || D <= 0 || P < 1 + R + (cond ? 2 : 0)) return WM_ERR_INVALID;
+  return op_status(wm_launch_vgt_special(X, cam_tok, reg_tok, pose_tok, ray_tok, N, P, R, D, cond, first_view_global, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_gemm_rowmap(int dtype, const void* A, const void* Wp, void* C, const float* bias, const float* add, int M, int N,
+                                       int K, int ldc, int rows_per_group, int out_group, int out_off, int accumulate, int out16, int relu,
+                                       void* stream) {
+  if (rows_per_group <= 0 || out_group < 0 || out_off < 0 || ldc < N || (out16 && accumulate)) return WM_ERR_INVALID;
+  WmGemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = A; a.W = Wp; a.C = C; a.bias = bias; a.add = add; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldc = ldc;
+  a.dtype = dtype; a.epi = WM_EPI_ROWMAP_ADD;
+  a.rows_per_group = rows_per_group; a.out_group = out_group; a.out_off = out_off; a.accumulate = accumulate; a.out16 = out16; a.relu = relu;
+  return op_status(wm_launch_gemm(a, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_gemm_convt(int dtype, const void* A, const void* Wp, float* C, const float* bias, int M, int N, int K, int ct_k,
+                                      int ct_cout, int ct_gh, int ct_gw, void* stream) {
+  if (!bias || ct_k <= 0 || ct_cout <= 0 || ct_gh <= 0 || ct_gw <= 0 || N != ct_k * ct_k * ct_cout || M % (ct_gh * ct_gw)) return WM_ERR_INVALID;
+  WmGemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.A = A; a.W = Wp; a.C = C; a.bias = bias; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldc = 0;
+  a.dtype = dtype; a.epi = WM_EPI_CONVT;
+  a.ct_k = ct_k; a.ct_cout = ct_cout; a.ct_gh = ct_gh; a.ct_gw = ct_gw;
+  return op_status(wm_launch_gemm(a, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_layernorm_rows(const float* x, void* y, const float* w, const float* b, int D, int ld_in, int ld_out, float eps,
+                                          int groups, int rows_per_group, int in_group, int in_off, int out_group, int out_off, int out_f32,
+                                          int dtype, void* stream) {
+  if (!x || !y || D <= 0 || ld_in < D || ld_out < D || groups < 0 || rows_per_group <= 0 || in_group < 0 || in_off < 0 || out_group < 0 || out_off < 0)
+    return WM_ERR_INVALID;
+  WmLnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = x; a.y = y; a.w = w; a.b = b; a.D = D; a.ld_in = ld_in; a.ld_out = ld_out; a.eps = eps;
+  a.groups = groups; a.rows_per_group = rows_per_group; a.in_group = in_group; a.in_off = in_off; a.out_group = out_group; a.out_off = out_off;
+  a.out_f32 = out_f32; a.dtype = dtype;
+  return op_status(wm_launch_layernorm(a, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_bilinear_add(const float* in, float* out, int N, int Hi, int Wi, int Ho, int Wo, int C, const float* addx,
+                                        const float* addy, void* stream) {
+  if (!in || !out || N < 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (addx != nullptr) != (addy != nullptr)) return WM_ERR_INVALID;
+  return op_status(wm_launch_bilinear(in, out, N, Hi, Wi, Ho, Wo, C, addx, addy, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_bilinear16(int dtype, const float* in, void* out16, int N, int Hi, int Wi, int Ho, int Wo, int C, const float* addx,
+                                      const float* addy, void* stream) {
+  // C % 8: the position tables are read as whole float4s on either side of C / 2
+  if (!in || !out16 || N < 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (addx != nullptr) != (addy != nullptr) || (addx && C % 8))
+    return WM_ERR_INVALID;
+  return op_status(wm_launch_bilinear16(in, out16, N, Hi, Wi, Ho, Wo, C, addx, addy, dtype, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_copy2d(const float* src, float* dst, int rows, int cols, int ld_src, int ld_dst, void* stream) {
+  if (!src || !dst || rows < 0 || cols <= 0 || ld_src < cols || ld_dst < cols) return WM_ERR_INVALID;
+  return op_status(wm_launch_copy2d(src, dst, rows, cols, ld_src, ld_dst, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_small_attention(const float* qkv, float* out, int S, int heads, int hd, void* stream) {
+  if (!qkv || !out || S < 0 || heads <= 0 || hd <= 0) return WM_ERR_INVALID;
+  return op_status(wm_launch_small_attention(qkv, out, S, heads, hd, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_adaln(const float* tok, const float* mod, float* h, int S, int D, float eps, void* stream) {
+  if (!tok || !mod || !h || S < 0 || D <= 0) return WM_ERR_INVALID;
+  return op_status(wm_launch_adaln(tok, mod, h, S, D, eps, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_cam_update(float* pred, const float* delta, float* out, int S, int first, void* stream) {
+  if (!pred || !delta || !out || S < 0) return WM_ERR_INVALID;
+  return op_status(wm_launch_cam_update(pred, delta, out, S, first, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_cam_matrices(const float* params, float* poses, float* intrs, int S, int H, int W, void* stream) {
+  if (!params || !poses || !intrs || S < 0) return WM_ERR_INVALID;
+  return op_status(wm_launch_cam_matrices(params, poses, intrs, S, H, W, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_linear_f32_ex(const float* X, const float* Wp, const float* b, float* Y, int M, int N, int K, int ldx, int ldy,
+                                         int pre_act, int post_act, const float* gamma, int accumulate, void* stream) {
+  if (!X || !Wp || !Y || K <= 0 || ldx < K || ldy < N) return WM_ERR_INVALID;
+  return op_status(wm_launch_linear_f32(X, Wp, b, Y, M, N, K, ldx, ldy, pre_act, post_act, gamma, accumulate, (hipStream_t)stream));
+}

@@ -183,7 +183,58 @@ wm_status wm_op_conv3x3_up(int dtype, const float* x, const void* w16, const flo
 wm_status wm_op_bilinear(const float* in, float* out, int N, int Hi, int Wi, int Ho, int Wo, int C, void* stream);
 wm_status wm_op_linear_f32(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int ldx, int pre_act,
                            int post_act, void* stream);
-/* host helper: fp32 -> 16-bit (round to nearest even), for building test operands */
+
+/* ---- operator-level entry points of the token front end and the camera head (parity tests: tests/test_gpu_ops_frontend.py).
+ * Thin: they fill the launcher's arguments and map its status (WM_ERR_INVALID for a shape the launcher refuses, nothing launched). ---- */
+/* Patchify (patch_embed.py:70, conv kernel = stride = ps as a GEMM): img f32 [N][C][H][W] -> out 16-bit [N*(H/ps)*(W/ps)][Kpad], column
+ * c*ps*ps + ky*ps + kx, zeros in [C*ps*ps, Kpad); normalize (C = 3 only): (x - mean[c]) / std[c] of visual_transformer.py:16-17.
+ * Rows and columns of the image beyond the last whole patch are dropped.  The launcher takes the input-indexed kernel when ps, W, C*ps*ps
+ * and Kpad are even and ps * W * 2 bytes fit 64 KiB of LDS, the output-indexed one otherwise. */
+wm_status wm_op_im2col(int dtype, const float* img, void* out, int N, int C, int H, int W, int ps, int Kpad, int normalize, void* stream);
+/* im2col of Conv2d(3, C, 7, 1, 3) (dense_head.py:91-95): img f32 [N][3][H][W] -> out 16-bit [N*H*W][Kpad], column c*49 + ky*7 + kx, zeros
+ * outside the image and in [147, Kpad) */
+wm_status wm_op_im2col7(int dtype, const float* img, void* out, int N, int H, int W, int Kpad, void* stream);
+/* Special rows of the DINO token buffer X f32 [N][1 + R + hw][D] (vision_transformer.py:215-219): row 0 = cls + pos[0], rows 1..R = reg;
+ * the hw patch rows are not touched (patch is unused: the patch-embed GEMM writes them). */
+wm_status wm_op_dino_tokens(const float* patch, const float* cls, const float* reg, const float* pos, float* X, int N, int hw, int R, int D,
+                            void* stream);
+/* Special rows [0, 1 + R + 2 cond) of the multi-view token buffer X f32 [N][P][D] (visual_transformer.py:285-295,397-416): cam_tok [2][D],
+ * reg_tok [2][R][D] (slot 0 for GLOBAL view 0 = first_view_global + n, slot 1 for the others); with cond, rows 1 + R and 2 + R take
+ * pose_tok [N][D] / ray_tok [N][D], or zeros where that pointer is NULL. */
+wm_status wm_op_vgt_special(float* X, const float* cam_tok, const float* reg_tok, const float* pose_tok, const float* ray_tok, int N, int P,
+                            int R, int D, int cond, int first_view_global, void* stream);
+/* GEMM with the row-remapping epilogue: row r = g * rows_per_group + q of A W^T lands in C row g * out_group + out_off + q as
+ * relu?(acc + bias) + add[q] (+ the old content when accumulate); add f32 [rows_per_group][N] or NULL; C f32, or 16-bit when out16 (no
+ * accumulate); ldc in elements of C.  (patch embed + pos table, depth-prior MLP into the view tokens, the DPT heads' projections) */
+wm_status wm_op_gemm_rowmap(int dtype, const void* A, const void* W, void* C, const float* bias, const float* add, int M, int N, int K,
+                            int ldc, int rows_per_group, int out_group, int out_off, int accumulate, int out16, int relu, void* stream);
+/* GEMM with the ConvTranspose2d(kernel = stride = ct_k) pixel-shuffle epilogue (dense_head.py:57-66): A 16-bit [n*ct_gh*ct_gw][K] tokens,
+ * W 16-bit [ct_k*ct_k*ct_cout][K] with row (ii*ct_k + jj)*ct_cout + co, bias f32 [ct_cout] -> C f32 NHWC [n][ct_gh*ct_k][ct_gw*ct_k][ct_cout] */
+wm_status wm_op_gemm_convt(int dtype, const void* A, const void* W, float* C, const float* bias, int M, int N, int K, int ct_k, int ct_cout,
+                           int ct_gh, int ct_gw, void* stream);
+/* LayerNorm with row remapping and row pitches: out row g*out_group + out_off + q <- in row g*in_group + in_off + q, q < rows_per_group,
+ * g < groups; pitches ld_in / ld_out in elements (columns [D, ld_out) are not written); f32 or 16-bit output. */
+wm_status wm_op_layernorm_rows(const float* x, void* y, const float* w, const float* b, int D, int ld_in, int ld_out, float eps, int groups,
+                               int rows_per_group, int in_group, int in_off, int out_group, int out_off, int out_f32, int dtype, void* stream);
+/* wm_op_bilinear + the separable position tables (dense_head.py:253-263): channel c < C/2 gets addx[x][c], the others addy[y][c - C/2]
+ * (addx [Wo][C/2], addy [Ho][C/2], both or neither NULL); f32 output, and the same written as a 16-bit NHWC tensor */
+wm_status wm_op_bilinear_add(const float* in, float* out, int N, int Hi, int Wi, int Ho, int Wo, int C, const float* addx, const float* addy,
+                             void* stream);
+wm_status wm_op_bilinear16(int dtype, const float* in, void* out16, int N, int Hi, int Wi, int Ho, int Wo, int C, const float* addx,
+                           const float* addy, void* stream);
+/* dst[r][0..cols) = src[r][0..cols), f32, row pitches ld_src / ld_dst (all multiples of 4) */
+wm_status wm_op_copy2d(const float* src, float* dst, int rows, int cols, int ld_src, int ld_dst, void* stream);
+/* Camera head (camera_head.py:84-147), all f32.  small_attention: qkv [S][3*heads*hd] -> out [S][heads*hd], softmax(q k^T / sqrt(hd)) v,
+ * S <= 8192.  adaln: h = gate * (LayerNorm_noaffine(tok) * (1 + scale) + shift) + tok with mod [S][3*D] = (shift, scale, gate).
+ * cam_update: pred [S][12] columns 0..8 = delta (first) or pred + delta, out [S][9] = the same with ReLU on columns 7, 8.
+ * cam_matrices: params [S][9] = (t, quat xyzw, fov_h, fov_w) -> poses [S][4][4] = inverse of [R|t], intrs [S][3][3] (camera_utils.py:46-75). */
+wm_status wm_op_small_attention(const float* qkv, float* out, int S, int heads, int hd, void* stream);
+wm_status wm_op_adaln(const float* tok, const float* mod, float* h, int S, int D, float eps, void* stream);
+wm_status wm_op_cam_update(float* pred, const float* delta, float* out, int S, int first, void* stream);
+wm_status wm_op_cam_matrices(const float* params, float* poses, float* intrs, int S, int H, int W, void* stream);
+/* wm_op_linear_f32 with the output pitch ldy, a per-column scale gamma (or NULL) and accumulation: Y (+)= gamma * post(pre(X) W^T + b) */
+wm_status wm_op_linear_f32_ex(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int ldx, int ldy, int pre_act,
+                              int post_act, const float* gamma, int accumulate, void* stream);
 /* ---- post-path geometry (the step right after the path in infer.py:303 / app.py:151) ----
  * depth_to_world_coords_points (src/models/utils/geometry.py:57-89): depth [B][H][W] f32, extrinsic [B][4][4]
  * camera-to-world, intrinsic [B][3][3] -> world [B][H][W][3], cam [B][H][W][3], mask [B][H][W] (u8, depth > eps).
@@ -307,6 +358,7 @@ wm_status wm_rasterize_splats(const float* means, const float* quats, const floa
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
 int wm_set_tuning(const char* key, int value);
 
+/* host helper: fp32 -> 16-bit (round to nearest even), for building test operands */
 void wm_host_to_16(const float* in, uint16_t* out, size_t n, int dtype);
 
 #ifdef __cplusplus
