@@ -51,7 +51,7 @@ EXPORTS = [
     "wm_local_group_create", "wm_local_group_destroy", "wm_comm_init_local", "wm_allgather", "wm_profile_enable", "wm_profile_read",
     "wm_op_gemm", "wm_op_gemm_resid_ln", "wm_op_gemm_qkv", "wm_op_attention", "wm_op_layernorm", "wm_op_qkv_post", "wm_op_conv", "wm_op_bilinear",
     "wm_op_linear_f32", "wm_host_to_16", "wm_set_tuning", "wm_op_attention_split", "wm_op_attention_ex", "wm_op_attention_flag_count", "wm_op_gs_splat", "wm_op_conv3x3_up", "wm_depth_to_world", "wm_confidence_mask", "wm_confidence_mask_workspace_bytes", "wm_preprocess_image", "wm_preprocess_image_size",
-    "wm_preprocess_image_workspace_bytes", "wm_rasterize_splats", "wm_rasterize_workspace_bytes", "wm_prune_gs", "wm_prune_gs_workspace_bytes", "wm_op_up_conv_n32", "wm_op_conv3x3_gemm16", "wm_op_conv_ex", "wm_op_upconv3x3_tap", "wm_op_tconv", "wm_op_upconv_gather",
+    "wm_preprocess_image_workspace_bytes", "wm_rasterize_splats", "wm_rasterize_workspace_bytes", "wm_rasterize_splats_backward", "wm_rasterize_backward_workspace_bytes", "wm_prune_gs", "wm_prune_gs_workspace_bytes", "wm_op_up_conv_n32", "wm_op_conv3x3_gemm16", "wm_op_conv_ex", "wm_op_upconv3x3_tap", "wm_op_tconv", "wm_op_upconv_gather",
     "wm_depth_edge", "wm_normals_edge", "wm_point_filter_mask_workspace_bytes", "wm_point_filter_mask",
     "wm_op_im2col", "wm_op_im2col7", "wm_op_dino_tokens", "wm_op_vgt_special", "wm_op_gemm_rowmap", "wm_op_gemm_convt", "wm_op_layernorm_rows",
     "wm_op_bilinear_add", "wm_op_bilinear16", "wm_op_copy2d", "wm_op_small_attention", "wm_op_adaln", "wm_op_cam_update", "wm_op_cam_matrices",
@@ -150,6 +150,11 @@ def lib() -> C.CDLL:
     L.wm_rasterize_splats.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t,
                                       C.POINTER(C.c_ulonglong), vp]
     L.wm_rasterize_splats.restype = i32
+    L.wm_rasterize_backward_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_size_t]
+    L.wm_rasterize_backward_workspace_bytes.restype = C.c_size_t
+    L.wm_rasterize_splats_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                               vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.wm_rasterize_splats_backward.restype = i32
     L.wm_preprocess_image_size.argtypes = [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.wm_preprocess_image_size.restype = i32
     L.wm_preprocess_image_workspace_bytes.argtypes = [i32, i32, i32, i32]

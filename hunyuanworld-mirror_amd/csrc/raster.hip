@@ -17,25 +17,13 @@
 // skip the blend when no pixel of the quadrant is hit, leave the list when all 64 are saturated.
 #include "wm_common.h"
 #include "wm_kernels.h"
+#include "raster_common.h"
 
 #include <hipcub/hipcub.hpp>
 
+using namespace wm_raster;
+
 namespace {
-
-constexpr int TILE = 16;
-constexpr float SH_C0 = 0.28209479177387814f;
-constexpr float ALPHA_THRESHOLD = 1.0f / 255.0f;
-
-struct __attribute__((aligned(16))) G2D {  // per (camera, Gaussian): 48 B = three 16-byte scalar loads of the compositing pass
-  float mx, my;         // pixel-space mean
-  float ca, cb;         // conic
-  float cc, opacity;
-  float depth;
-  float r, g, b;        // colour (view-independent: degree-0 SH or given colours)
-  int rect;             // x0 | y0 << 8 | x1 << 16 | y1 << 24 in tiles (tile grids up to 255 x 255); the compositing pass reads words 0-9 only
-  int pad;
-};
-static_assert(sizeof(G2D) == 48, "G2D is read as three dwordx4");
 
 __global__ __launch_bounds__(256) void raster_project_kernel(const float* __restrict__ means, const float* __restrict__ quats,
                                                              const float* __restrict__ scales, const float* __restrict__ viewmats,
@@ -273,14 +261,9 @@ __global__ __launch_bounds__(256 / (PX * PY)) void raster_composite_kernel(const
   }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+}  // namespace
 
-struct RasterWs {
-  G2D* g2d; unsigned long long* counts; unsigned long long* offsets; float4* rgb;
-  unsigned long long* keys[2]; unsigned int* vals[2]; unsigned int* tile_offs; void* cub; size_t cub_bytes; size_t total;
-};
-
-RasterWs carve(char* base, size_t N, size_t C, int tiles, size_t max_isects) {
+RasterWs wm_raster::carve(char* base, size_t N, size_t C, int tiles, size_t max_isects) {
   RasterWs w;
   size_t o = 0;
   auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
@@ -302,8 +285,6 @@ RasterWs carve(char* base, size_t N, size_t C, int tiles, size_t max_isects) {
   w.total = o;
   return w;
 }
-
-}  // namespace
 
 size_t wm_raster_workspace_bytes(int N, int C, int width, int height, size_t max_isects) {
   const int tiles = ((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);

@@ -278,6 +278,17 @@ struct WmRasterArgs {
 };
 size_t wm_raster_workspace_bytes(int N, int C, int width, int height, size_t max_isects);
 hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned long long* n_isects_out);
+// backward (raster_bwd.hip): fwd = the arguments of the forward call whose workspace is still as that call left it (outputs unused)
+struct WmRasterBwdArgs {
+  WmRasterArgs fwd;
+  size_t n_isects;                                     // the pair count the forward reported
+  const float* out_depth;                              // [C,H,W] the forward's expected depth
+  const float* v_rgb; const float* v_depth; const float* v_alpha;   // cotangents [C,H,W,3] [C,H,W] [C,H,W]
+  float* v_means; float* v_quats; float* v_scales; float* v_opacities; float* v_colors;   // [N,3] [N,4] [N,3] [N] [N,3]
+  void* grad_workspace; size_t grad_workspace_bytes;
+};
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects);
+hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s);
 
 // ------------------------------------------------------------------ voxel merge of splats (splat_prune.hip)
 size_t wm_prune_workspace_bytes(size_t N);

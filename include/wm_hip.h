@@ -353,6 +353,29 @@ wm_status wm_rasterize_splats(const float* means, const float* quats, const floa
                               int* radii_out, void* workspace, size_t workspace_bytes, size_t max_isects,
                               unsigned long long* n_isects, void* stream);
 
+/* 3D-Gaussian-splat rasteriser backward — the gradient gsplat.rasterization gives through its autograd functions
+ * (gsplat/cuda/_wrapper.py _RasterizeToPixels.backward -> csrc/RasterizeToPixels3DGSBwd.cu, _FullyFusedProjection.backward,
+ * _QuatScaleToCovarPreci.backward), which the reference's "Post 3DGS Optimization" (README; gsplat's simple_trainer) runs on.
+ * Gradients of out_rgb / out_depth / out_alpha of ONE wm_rasterize_splats call with respect to means [N,3], quats [N,4] (through
+ * the normalisation), scales [N,3], opacities [N] and colors [N,3] (the degree-0 SH coefficients when colors_are_sh0: zero where
+ * 0.2820948 sh + 0.5 <= 0).  No gradient for viewmats or Ks, no absgrad, no packed / sparse layout.
+ * CONTRACT: pass the same inputs, sizes, workspace, workspace_bytes and max_isects as the forward call and the *n_isects it
+ * reported; the workspace must be UNTOUCHED between that forward and this call (no other wm_rasterize_splats on it): the
+ * backward reads the projection records, the sorted pair list and the tile offsets the forward left there.  out_depth is the
+ * forward's output; out_rgb and out_alpha are part of the interface but are not read (may be null).  v_rgb [C,H,W,3], v_depth
+ * [C,H,W], v_alpha [C,H,W]: cotangents.  All five gradient outputs are overwritten (zero for Gaussians no camera sees).
+ * grad_workspace: wm_rasterize_backward_workspace_bytes bytes (40 bytes per (Gaussian, tile) pair).  Sums run in a fixed
+ * order, no atomics: results are bitwise reproducible.  Asynchronous on stream.  Returns WM_ERR_STATE when n_isects >
+ * max_isects (that forward rendered nothing), WM_ERR_INVALID / WM_ERR_HIP as the forward. */
+size_t wm_rasterize_backward_workspace_bytes(int n_gaussians, int n_cameras, int width, int height, size_t n_isects);
+wm_status wm_rasterize_splats_backward(const float* means, const float* quats, const float* scales, const float* opacities,
+                                       const float* colors, int colors_are_sh0, int n_gaussians, const float* viewmats, const float* Ks,
+                                       int n_cameras, int width, int height, const void* workspace, size_t workspace_bytes,
+                                       size_t max_isects, size_t n_isects, const float* out_rgb, const float* out_depth,
+                                       const float* out_alpha, const float* v_rgb, const float* v_depth, const float* v_alpha,
+                                       float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
+                                       void* grad_workspace, size_t grad_workspace_bytes, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  key: "gemm_cfg"
  * (tile config id), "gemm_pp" (0/1 ping-pong GEMM), "gemm_mfma16" (0/1/2), "attn_qb" (attention variant);
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
