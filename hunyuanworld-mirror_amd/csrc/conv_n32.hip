@@ -155,7 +155,7 @@ __global__ __launch_bounds__(512) void conv3x3_n32_in16_kernel(const WmConvN32Ar
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float bias_e = e == 0 ? bs[g].x : e == 1 ? bs[g].y : e == 2 ? bs[g].z : bs[g].w;
-            const float v = fmaxf(acc[4 * g + e] + bias_e, 0.f);
+            const float v = relu_keep_nan(acc[4 * g + e] + bias_e);
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[c] += v * tw[c][4 * g + e];
           }
@@ -170,10 +170,7 @@ __global__ __launch_bounds__(512) void conv3x3_n32_in16_kernel(const WmConvN32Ar
         } else if (p.tail_act == WM_ACT_EXP) {
           for (int c = 0; c < A; ++c) tres[c] = expf(o[c]);
         } else {
-          for (int c = 0; c < A; ++c) {
-            const float e = expm1f(fabsf(o[c]));
-            tres[c] = o[c] > 0.f ? e : (o[c] < 0.f ? -e : 0.f);
-          }
+          for (int c = 0; c < A; ++c) tres[c] = inv_log(o[c]);
         }
         tres[3] = 1.0f + expf(o[A]);
       } else {

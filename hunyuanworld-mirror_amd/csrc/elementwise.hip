@@ -296,7 +296,9 @@ __global__ __launch_bounds__(256) void gs_splat_kernel(const float* __restrict__
     const float4 g0 = *(const float4*)g, g1 = *(const float4*)(g + 4), g2 = *(const float4*)(g + 8);
     const float qn = sqrtf(g0.x * g0.x + g0.y * g0.y + g0.z * g0.z + g0.w * g0.w) + 1e-8f;
     quats[i * 4 + 0] = g0.x / qn; quats[i * 4 + 1] = g0.y / qn; quats[i * 4 + 2] = g0.z / qn; quats[i * 4 + 3] = g0.w / qn;
-    scales[i * 3 + 0] = fminf(expf(g1.x), 0.3f); scales[i * 3 + 1] = fminf(expf(g1.y), 0.3f); scales[i * 3 + 2] = fminf(expf(g1.z), 0.3f);
+    // (e > 0.3f ? 0.3f : e, not fminf: a NaN scale stays NaN, as .exp().clamp_max(0.3) leaves it)
+    const float e0 = expf(g1.x), e1 = expf(g1.y), e2 = expf(g1.z);
+    scales[i * 3 + 0] = e0 > 0.3f ? 0.3f : e0; scales[i * 3 + 1] = e1 > 0.3f ? 0.3f : e1; scales[i * 3 + 2] = e2 > 0.3f ? 0.3f : e2;
     opac[i] = 1.0f / (1.0f + expf(-g1.w));
     const float C0 = 0.28209479177387814f;
     const size_t hw = (size_t)H * W, p0 = (size_t)n * 3 * hw + (size_t)y * W + x;
@@ -534,7 +536,7 @@ __global__ __launch_bounds__(256) void dpt_tail_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float4 v = src[k];
-      v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+      v.x = relu_keep_nan(v.x); v.y = relu_keep_nan(v.y); v.z = relu_keep_nan(v.z); v.w = relu_keep_nan(v.w);
 #pragma unroll
       for (int c = 0; c < 4; ++c)
         if (c < C) o[c] += v.x * sw[c * 32 + 4 * k] + v.y * sw[c * 32 + 4 * k + 1] + v.z * sw[c * 32 + 4 * k + 2] + v.w * sw[c * 32 + 4 * k + 3];
@@ -548,10 +550,7 @@ __global__ __launch_bounds__(256) void dpt_tail_kernel(const float* __restrict__
     } else if (act == WM_ACT_EXP) {
       for (int c = 0; c < A; ++c) attr[i * A + c] = expf(o[c]);
     } else {
-      for (int c = 0; c < A; ++c) {
-        const float e = expm1f(fabsf(o[c]));
-        attr[i * A + c] = o[c] > 0.f ? e : (o[c] < 0.f ? -e : 0.f);
-      }
+      for (int c = 0; c < A; ++c) attr[i * A + c] = inv_log(o[c]);
     }
     conf[i] = 1.0f + expf(o[A]);
   }

@@ -133,6 +133,13 @@ __device__ __forceinline__ void xhalf_pair(float x, float& a, float& b) {
 __device__ __forceinline__ float xhalf_max(float x) { float a, b; xhalf_pair(x, a, b); return fmaxf(a, b); }
 __device__ __forceinline__ float xhalf_sum(float x) { float a, b; xhalf_pair(x, a, b); return a + b; }
 
+// The DPT tails (dpt_tail_kernel, the epilogue of conv3x3_n32_in16_kernel) keep a NaN a NaN, as the reference's fp32 heads do
+// (NaN policy).  F.relu(NaN) is NaN: fmaxf would return 0.  Equal to fmaxf(v, 0.f) on every other input (for -0 up to the sign
+// of the zero, which no activation of the tails lets through).
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+// dense_head.py:356 sign(x) * expm1(|x|): odd, +0 for both zeros, NaN for NaN (a three-way select on x > 0 / x < 0 returned 0 for it)
+__device__ __forceinline__ float inv_log(float x) { return x == 0.f ? 0.f : copysignf(expm1f(fabsf(x)), x); }
+
 // v_permlane16_swap exchanges the odd 16-lane rows of its first operand with the even rows of its second.  With
 // a = this lane's packed columns of sub-tile j0 and b = those of sub-tile j1 (MFMA 16x16 D layout: lane = (row l15,
 // quad lq) owns 4 consecutive columns), afterwards an even-lq lane holds {a, b} = 8 consecutive columns of j0

@@ -1961,7 +1961,8 @@ extern "C" wm_status wm_op_up_conv_n32(int dtype, const float* x, const void* w1
   a.N = N; a.H = Hi; a.W = Wi; a.Cin = Cin; a.relu_out = relu_out; a.dtype = dtype;
   return wm_launch_conv3x3_n32_in16(a, s) == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
-// splat assembly of prepare_splats (rasterization.py:389-498) as an operator: used by tools/micro/splat_hazard_repro.cpp
+// splat assembly of prepare_splats (rasterization.py:389-498) as an operator: the launch the forward makes behind the gs head, for the
+// parity tests (tests/test_gpu_ops_tails.py) and tools/micro/splat_hazard_repro.cpp
 extern "C" wm_status wm_op_gs_splat(const float* gp, const float* img, const float* depth, const float* cam, float* means, float* quats,
                                     float* scales, float* opac, float* sh, float* wts, int N, int H, int W, void* stream) {
   return wm_launch_gs_splat(gp, img, depth, cam, means, quats, scales, opac, sh, wts, N, H, W, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
@@ -2366,4 +2367,30 @@ extern "C" wm_status wm_op_linear_f32_ex(const float* X, const float* Wp, const 
                                          int pre_act, int post_act, const float* gamma, int accumulate, void* stream) {
   if (!X || !Wp || !Y || K <= 0 || ldx < K || ldy < N) return WM_ERR_INVALID;
   return op_status(wm_launch_linear_f32(X, Wp, b, Y, M, N, K, ldx, ldy, pre_act, post_act, gamma, accumulate, (hipStream_t)stream));
+}
+extern "C" wm_status wm_op_dpt_tail(const float* y32, const float* w, const float* b, float* attr, float* conf, size_t npix, int C, int act,
+                                    void* stream) {
+  if (!y32 || !w || !b || !attr || !conf || act < WM_ACT_INV_LOG || act > WM_ACT_NORM) return WM_ERR_INVALID;
+  return op_status(wm_launch_dpt_tail(y32, w, b, attr, conf, npix, C, act, (hipStream_t)stream));   // the launcher refuses C outside 2..4
+}
+// wm_op_up_conv_n32 with the head's tail in the conv's epilogue: the launch pair dpt_head makes for output_conv2 when dpt_features / 2 is a
+// multiple of 64 (the 32-channel tensor is never stored)
+extern "C" wm_status wm_op_up_conv_n32_tail(int dtype, const float* x, const void* w16, const float* bias, int N, int Hs, int Ws, int Hi, int Wi,
+                                            int Cin, const float* addx, const float* addy, const float* tail_w, const float* tail_b, int tail_C,
+                                            int tail_act, float* attr, float* conf, void* up16, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if ((dtype != WM_DT_BF16 && dtype != WM_DT_F16) || !x || !w16 || !up16 || !tail_w || !tail_b || !attr || !conf || N < 0 || Hs <= 0 || Ws <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin % 64 || Cin > 128 ||
+      (addx != nullptr) != (addy != nullptr) || tail_act < WM_ACT_INV_LOG || tail_act > WM_ACT_NORM || tail_C < 2 || tail_C > 4)
+    return WM_ERR_INVALID;
+  const size_t n16 = (size_t)N * Hi * Wi * Cin;
+  uint16_t* zero = (uint16_t*)up16 + ((n16 + 7) & ~(size_t)7);
+  if (hipMemsetAsync(zero, 0, 16, s) != hipSuccess) return WM_ERR_HIP;
+  const wm_status st = op_status(wm_launch_bilinear16(x, up16, N, Hs, Ws, Hi, Wi, Cin, addx, addy, dtype, s));
+  if (st != WM_OK) return st;
+  WmConvN32Args a;
+  memset(&a, 0, sizeof(a));
+  a.x = (const uint16_t*)up16; a.w = (const uint16_t*)w16; a.bias = bias; a.zero = zero;
+  a.N = N; a.H = Hi; a.W = Wi; a.Cin = Cin; a.relu_out = 0; a.dtype = dtype;
+  a.tail_w = tail_w; a.tail_b = tail_b; a.tail_C = tail_C; a.tail_act = tail_act; a.tail_attr = attr; a.tail_conf = conf;
+  return op_status(wm_launch_conv3x3_n32_in16(a, s));
 }

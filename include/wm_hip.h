@@ -235,6 +235,19 @@ wm_status wm_op_cam_matrices(const float* params, float* poses, float* intrs, in
 /* wm_op_linear_f32 with the output pitch ldy, a per-column scale gamma (or NULL) and accumulation: Y (+)= gamma * post(pre(X) W^T + b) */
 wm_status wm_op_linear_f32_ex(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int ldx, int ldy, int pre_act,
                               int post_act, const float* gamma, int accumulate, void* stream);
+/* ---- operator-level entry points of the DPT heads' tails (parity tests: tests/test_gpu_ops_tails.py); thin, as the ones above ---- */
+/* The tail of a DPT head (src/models/heads/dense_head.py:97-105 output_conv2[1:], :297-344 activate_head, :356 the inverse log transform):
+ * y32 f32 [npix][32] -> ReLU -> 1x1 conv 32 -> C (w f32 [C][32], b f32 [C]) -> attr f32 [npix][C - 1] = act(first C - 1 channels),
+ * conf f32 [npix] = 1 + exp(last channel).  act: 0 = inv_log (sign(x) expm1(|x|)), 1 = exp, 2 = norm (x / |x|, no epsilon: the zero vector
+ * gives NaN as in the reference).  C in 2..4, anything else is WM_ERR_INVALID.  NaN in y32, w or b reaches every output it feeds. */
+wm_status wm_op_dpt_tail(const float* y32, const float* w, const float* b, float* attr, float* conf, size_t npix, int C, int act, void* stream);
+/* wm_op_up_conv_n32 (below) with that tail in the conv's epilogue (dense_head.py:217-251 + the lines above): the launch pair the forward
+ * makes for the depth / pts / normal heads when dpt_features / 2 is a multiple of 64; the 32-channel tensor is never stored.  tail_w f32
+ * [tail_C][32], tail_b f32 [tail_C], tail_C in 2..4, tail_act as act above, attr f32 [N][Hi][Wi][tail_C - 1], conf f32 [N][Hi][Wi]; Cin 64
+ * or 128; up16 as for wm_op_up_conv_n32 (it holds the rounded resize afterwards). */
+wm_status wm_op_up_conv_n32_tail(int dtype, const float* x, const void* w16, const float* bias, int N, int Hs, int Ws, int Hi, int Wi, int Cin,
+                                 const float* addx, const float* addy, const float* tail_w, const float* tail_b, int tail_C, int tail_act,
+                                 float* attr, float* conf, void* up16, void* stream);
 /* ---- post-path geometry (the step right after the path in infer.py:303 / app.py:151) ----
  * depth_to_world_coords_points (src/models/utils/geometry.py:57-89): depth [B][H][W] f32, extrinsic [B][4][4]
  * camera-to-world, intrinsic [B][3][3] -> world [B][H][W][3], cam [B][H][W][3], mask [B][H][W] (u8, depth > eps).

@@ -176,6 +176,33 @@ def test_conv3x3_kernels_do_not_spill(tmp_path):
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
+def test_conv_n32_fused_tail_stays_out_of_scratch(tmp_path):
+    """conv3x3_n32_in16_kernel (conv_n32.hip) keeps, beside its 16 accumulators and the deferred copy, the fused tail's 64 weights and
+    indexes the small arrays o[4] / tres[4] with the run-time tail_C: an epilogue edit that makes hipcc give up on keeping them in
+    registers puts them in scratch, whose loads and stores count in vmcnt beside the kernel's LDS-DMA pieces.  Neither instantiation may
+    use scratch or spill.  VGPRs, bf16 / f16: 218 / 218 with fmaxf and the three-way inv_log select in the tail, 218 / 218 with the
+    NaN-keeping ReLU and inv_log (wm_common.h); 2 waves per SIMD and 17 SGPRs parked in VGPR lanes (no memory) either way."""
+    flags = None
+    for line in open(os.path.join(CSRC, "Makefile")):
+        if line.startswith("CXXFLAGS"):
+            flags = [f.replace("$(ARCH)", "gfx950") for f in line.split("=", 1)[1].split() if not f.startswith("$(")]
+    r = subprocess.run(["hipcc", *flags, "-x", "hip", "-c", os.path.join(CSRC, "conv_n32.hip"), "-o", str(tmp_path / "c.o"),
+                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    n = 0
+    for b in re.split(r"remark: Function Name: ", r.stderr)[1:]:
+        name = b.split()[0]
+        if "conv3x3_n32_in16_kernel" not in name:
+            continue
+        n += 1
+        get = lambda key: int(re.search(key + r": (\d+)", b).group(1))
+        print(name, "VGPRs", get(r"VGPRs"), "occupancy", get(r"Occupancy \[waves/SIMD\]"))
+        assert get(r"ScratchSize \[bytes/lane\]") == 0 and get(r"VGPRs Spill") == 0, b[:400]
+        assert get(r"VGPRs") <= 256 and get(r"Occupancy \[waves/SIMD\]") >= 2, b[:400]   # a block is 8 waves: 2 per SIMD must fit
+    assert n == 2
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
 def test_raster_compositing_streams_records_through_scalar_loads(tmp_path):
     """The compositing pass (raster.hip) is written for 64-wide waves: the Gaussian of a step is wave-uniform, fetched by scalar loads
     into two alternating SGPR sets whose requests are asm statements (the compiler sinks plain loads next to their use).  What that
