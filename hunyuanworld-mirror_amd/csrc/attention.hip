@@ -19,8 +19,6 @@
 #include "wm_common.h"
 #include "wm_kernels.h"
 
-#include <cstdlib>
-
 namespace {
 
 // One 1-KiB LDS-DMA piece (16 B per lane) from inline asm: M0 carries the LDS destination; it is saved and restored
@@ -709,8 +707,10 @@ hipError_t launch(const WmAttnArgs& a_in, hipStream_t s, int fast = 0) {   // fa
     lim = lim < WM_ATTN_MAX_SPLITS ? lim : WM_ATTN_MAX_SPLITS;
     lim = lim < ntiles / 8 ? lim : (ntiles / 8 > 1 ? ntiles / 8 : 1);  // keep slices >= 8 tiles
     int best = 1;
+    const int forced_splits = wm_tune(WM_TUNE_ATTN_SPLITS, 0);   // 0: choose below
+    const int tail_mode = wm_tune(WM_TUNE_ATTN_TAIL, 1);         // 0: no tail split, 1: slices by the model below, > 1: that many
     if (a.kv_splits > 0) best = a.kv_splits < lim ? a.kv_splits : lim;
-    else if (wm_tuning[WM_TUNE_ATTN_SPLITS] > 0) best = wm_tuning[WM_TUNE_ATTN_SPLITS] < lim ? wm_tuning[WM_TUNE_ATTN_SPLITS] : lim;
+    else if (forced_splits > 0) best = forced_splits < lim ? forced_splits : lim;
     // Automatic split only on the view-sharded path (kv_chunks > 1: 8 local views of queries against all ranks' keys):
     // the q-tiles alone give 1.3 rounds of long blocks there and 4 slices measure +18 % at 8 chunks, +7 % at 4, +6 % at
     // 2 (tools/bench_attn_split_chunks.py).  On one GPU (kv_chunks == 1) the combine pass costs what the better
@@ -731,7 +731,7 @@ hipError_t launch(const WmAttnArgs& a_in, hipStream_t s, int fast = 0) {   // fa
     const long tail = blocks % slots;
     // (the short per-frame sequences — 22 key tiles — lose 10 % with the general kernel and are left alone there; the pipelined
     //  kernel splits them too: 768 units on 512 slots = 512 whole + 256 x 2 halves = two even rounds)
-    if (!a.force_partial && a_in.kv_splits == 0 && wm_tuning[WM_TUNE_ATTN_SPLITS] <= 0 && lim >= 2 && ntiles >= (use_v3 ? 16 : 64) && blocks > slots && tail > 0 && wm_tuning[WM_TUNE_ATTN_TAIL] != 0) {
+    if (!a.force_partial && a_in.kv_splits == 0 && forced_splits <= 0 && lim >= 2 && ntiles >= (use_v3 ? 16 : 64) && blocks > slots && tail > 0 && tail_mode != 0) {
       // (one block per CU — attn_v4 — has no partner to lose: a half-filled round costs a whole one)
       auto round_cost = [&](long n) { const long rem = n % slots; return (double)(n / slots) + (rem == 0 ? 0.0 : (rem * 2 <= slots && fast != 4) ? 0.73 : 1.0); };
       double best_cost = round_cost(tail);
@@ -740,7 +740,7 @@ hipError_t launch(const WmAttnArgs& a_in, hipStream_t s, int fast = 0) {   // fa
         const double c = round_cost(tail * S) / S + 0.01 * S;
         if (c < best_cost - 0.05) { best_cost = c; bs = S; }
       }
-      if (wm_tuning[WM_TUNE_ATTN_TAIL] > 1) bs = wm_tuning[WM_TUNE_ATTN_TAIL] < lim ? wm_tuning[WM_TUNE_ATTN_TAIL] : lim;  // A/B: forced slice count
+      if (tail_mode > 1) bs = tail_mode < lim ? tail_mode : lim;  // A/B: forced slice count
       if (bs > 1) { a.kv_splits = bs; a.full_units = (int)(blocks - tail); }
       else if (best > 1) a.kv_splits = best;  // keep the uniform choice
     }
@@ -749,15 +749,14 @@ hipError_t launch(const WmAttnArgs& a_in, hipStream_t s, int fast = 0) {   // fa
   const int nfull = a.kv_splits > 1 ? a.full_units : units;
   dim3 grid(nfull + (units - nfull) * a.kv_splits), block(NW * 64);
   if (use_v3) {  // same unit / split numbering (QT = 256 / 512): the fast kernel, then the general kernel on the blocks it flagged
-    static const int v3_minw = [] { const char* e = wm_env("WM_ATTN_V3_MINW"); return e ? atoi(e) : 2; }();
-    hipError_t e = fast == 4 ? wm_launch_attention_v4(a, (int)grid.x, a.unit_flags, s) : wm_launch_attention_v3(a, (int)grid.x, a.unit_flags, v3_minw, s);
+    hipError_t e = fast == 4 ? wm_launch_attention_v4(a, (int)grid.x, a.unit_flags, s) : wm_launch_attention_v3(a, (int)grid.x, a.unit_flags, s);
     if (e != hipSuccess) return e;
     a.only_if = a.unit_flags;
   }
 #ifdef WM_ATTN_TIMING_EXPERIMENT
-  // (timing-only build for tools/attn_launch_cost.py, make EXTRA="-DWM_ATTN_TIMING_EXPERIMENT -DWM_DIAG_ENV": 1 skips the recompute pass behind
-  //  a fast kernel, 2 the combine pass, 3 both — wrong results; not in the shipped library)
-  static const int dbg_skip = [] { const char* e = wm_env("WM_ATTN_DEBUG_SKIP"); return e ? atoi(e) : 0; }();
+  // (timing-only build for tools/attn_launch_cost.py, make EXTRA=-DWM_ATTN_TIMING_EXPERIMENT: tuning attn_debug_skip = 1 skips the recompute
+  //  pass behind a fast kernel, 2 the combine pass, 3 both — wrong results; not in the shipped library)
+  const int dbg_skip = wm_tune(WM_TUNE_ATTN_DEBUG_SKIP, 0);
 #else
   constexpr int dbg_skip = 0;
 #endif
@@ -792,8 +791,7 @@ hipError_t wm_launch_attention_combine(const WmAttnArgs& a_in, int slots, hipStr
 //   4  general kernel, 32 rows per wave at 3 waves / SIMD: the short per-frame / DINO sequences
 // 7 and 8 need a flag workspace and key segments of >= 512 keys (a ragged last tile is padded with zero keys); other values: A/B variants (forced only).
 int wm_attention_variant(const WmAttnArgs& a) {
-  static const int forced_env = [] { const char* e = wm_env("WM_ATTN_QB"); return e ? atoi(e) : 0; }();
-  const int forced = wm_tuning[WM_TUNE_ATTN_QB] >= 0 ? wm_tuning[WM_TUNE_ATTN_QB] : forced_env;
+  const int forced = wm_tune(WM_TUNE_ATTN_QB, 0);   // 0: choose below
   const int seg_rows = a.kv_chunks > 1 ? a.kv_rows_per_chunk : a.seq_len;
   const bool fast_ok = a.unit_flags != nullptr && seg_rows >= 512;   // (a ragged last tile is padded with zero keys)
   const bool v3ok = a.dtype == WM_T_BF16 && fast_ok;

@@ -442,11 +442,10 @@ __global__ __launch_bounds__(256, MINW) void attn_v3_kernel(const WmAttnArgs p, 
 }  // namespace
 
 // grid / split decisions are the caller's (attention.hip: the same unit numbering as attn_fwd_kernel<.., 4, 2, ..>)
-hipError_t wm_launch_attention_v3(const WmAttnArgs& a, int grid, int* flags, int minw, hipStream_t s) {
+hipError_t wm_launch_attention_v3(const WmAttnArgs& a, int grid, int* flags, hipStream_t s) {
   const int seg_rows = a.kv_chunks > 1 ? a.kv_rows_per_chunk : a.seq_len;
   if (seg_rows < KVB) return hipErrorInvalidValue;
-  if (minw >= 2) hipLaunchKernelGGL((attn_v3_kernel<2, false>), dim3(grid), dim3(256), 0, s, a, flags);
-  else hipLaunchKernelGGL((attn_v3_kernel<1, false>), dim3(grid), dim3(256), 0, s, a, flags);
+  hipLaunchKernelGGL((attn_v3_kernel<2, false>), dim3(grid), dim3(256), 0, s, a, flags);
   return hipGetLastError();
 }
 

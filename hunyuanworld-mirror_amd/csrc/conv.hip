@@ -13,8 +13,6 @@
 #include "wm_common.h"
 #include "wm_kernels.h"
 
-#include <cstdlib>
-
 namespace {
 
 typedef __attribute__((address_space(3))) void* lds_vp;
@@ -213,8 +211,8 @@ hipError_t launch_T(const WmConvArgs& a, hipStream_t s) {
     static const int ncu = [] { hipDeviceProp_t pr; int d = 0; (void)hipGetDevice(&d); return hipGetDeviceProperties(&pr, d) == hipSuccess ? pr.multiProcessorCount : 256; }();
     const long M = (long)a.N * a.Ho * a.Wo;
     const long t128 = ((M + 127) / 128) * ((a.Cout + 127) / 128);
-    static const int bm_env = [] { const char* e = wm_env("WM_CONV_BM"); return e ? atoi(e) : 0; }();
-    if (!narrow && (bm_env == 64 || (bm_env == 0 && t128 < ncu))) return launch_cfg<T, 64, 2, 2, 1, 2>(a, s);
+    const int bm = wm_tune(WM_TUNE_CONV_BM, 0);   // 0: choose, 64 / 128: that pixel tile (A/B: tools/bench_conv_s2.py)
+    if (!narrow && (bm == 64 || (bm == 0 && t128 < ncu))) return launch_cfg<T, 64, 2, 2, 1, 2>(a, s);
     return narrow ? launch_cfg<T, 64, 4, 1, 1, 1>(a, s) : launch_cfg<T, 64, 2, 2, 2, 2>(a, s);
   } else {
     return narrow ? launch_cfg<T, 32, 4, 1, 1, 1>(a, s) : launch_cfg<T, 32, 2, 2, 2, 2>(a, s);
@@ -228,12 +226,11 @@ hipError_t wm_launch_conv3x3(const WmConvArgs& a, hipStream_t s);
 
 hipError_t wm_launch_conv(const WmConvArgs& a, hipStream_t s) {
   if (a.N <= 0) return hipSuccess;
-  const bool no_halo = wm_conv_force_generic();   // (wm_conv3x3_out16_ok knows the switch too: no out16 grant that this launch cannot honour)
   if (a.up_hs > 0) {  // fused input upsample exists in the halo kernel only; callers test wm_conv3x3_applicable first
     if (!wm_conv3x3_applicable(a) || a.up_ws <= 0 || (a.up_addx && (a.Cin & 15))) return hipErrorInvalidValue;
     return wm_launch_conv3x3(a, s);
   }
-  if (!no_halo && wm_conv3x3_applicable(a)) return wm_launch_conv3x3(a, s);
+  if (wm_conv3x3_applicable(a)) return wm_launch_conv3x3(a, s);
   if (a.in16) return hipErrorInvalidValue;   // only the register-staged 3x3 kernel reads a 16-bit input
   if (a.Cin % 32 != 0 || a.ksize < 1 || a.out16) return hipErrorInvalidValue;  // (16-bit output: register-staged 3x3 kernel only)
   if (a.Ho != (a.Hi + 2 * a.pad - a.ksize) / a.stride + 1 || a.Wo != (a.Wi + 2 * a.pad - a.ksize) / a.stride + 1)

@@ -695,7 +695,8 @@ int pick_bn(const WmConvArgs& a) {  // output-channel tile (see launch_T)
   const long ptiles = (long)a.N * ((a.Hi + TP - 1) / TP) * ((a.Wi + TP - 1) / TP);
   int bn = a.Cout > 128 ? 256 : a.Cout > 64 ? 128 : a.Cout > 32 ? 64 : 32;
   while (bn > 64 && 2 * ptiles * ((a.Cout + bn - 1) / bn) < ncu) bn >>= 1;
-  if (wm_tuning[WM_TUNE_CONV_BN] > 0) bn = wm_tuning[WM_TUNE_CONV_BN];
+  const int forced = wm_tune(WM_TUNE_CONV_BN, 0);   // 0: the choice above
+  if (forced > 0) bn = forced;
   return bn;
 }
 
@@ -708,35 +709,32 @@ hipError_t launch_T(const WmConvArgs& a, hipStream_t s) {
   static const int ncu = cu_count();
   const long ptiles = (long)a.N * ((a.Hi + TP - 1) / TP) * ((a.Wi + TP - 1) / TP);
   const int bn = pick_bn(a);
-  const bool rs_ok = (a.Cin / 64) % 2 == 0 && wm_tuning[WM_TUNE_CONV_RS] != 0;
+  const bool rs_ok = (a.Cin / 64) % 2 == 0 && wm_tune(WM_TUNE_CONV_RS, 1) != 0;
   const bool rs = rs_ok && a.up_hs == 0;  // register-staged main loop (plain input, even chunk count)
+  const int tpx = wm_tune(WM_TUNE_CONV_TPX, 0);   // 0: choose below, 16 / 32: that pixel-tile width
   if (rs_ok && a.up_hs > 0 && bn == 128) {  // fused resize, 128-channel tile
-    if (wm_tuning[WM_TUNE_CONV_TPX] == 32) return launch_rs<T, 4, 2, 2, 2, 1, 32>(a, s);  // A/B: 32 x 8 pixel tile (no LDS bank conflicts, 2.5 % more tiles at 296^2)
+    if (tpx == 32) return launch_rs<T, 4, 2, 2, 2, 1, 32>(a, s);  // A/B: 32 x 8 pixel tile (no LDS bank conflicts, 2.5 % more tiles at 296^2)
     return launch_rs<T, 4, 2, 2, 2, 1>(a, s);
   }
-  if (rs && bn >= 128 && wm_tuning[WM_TUNE_CONV_TPX] != 16) {
+  if (rs && bn >= 128 && tpx != 16) {
     // pixel-tile shape: rounds over the CUs (one block per CU) with 16 x 16 vs 32 x 8 tiles
     const long ct = (a.Cout + bn - 1) / bn;
     const long t16 = ptiles * ct, t32 = (long)a.N * ((a.Hi + 7) / 8) * ((a.Wi + 31) / 32) * ct;
     const long r16 = (t16 + ncu - 1) / ncu, r32 = (t32 + ncu - 1) / ncu;
-    if (r32 < r16 || (r32 == r16 && t32 < t16) || wm_tuning[WM_TUNE_CONV_TPX] == 32)  // fewer rounds, else fewer (less ragged) tiles
+    if (r32 < r16 || (r32 == r16 && t32 < t16) || tpx == 32)  // fewer rounds, else fewer (less ragged) tiles
       return bn >= 256 ? launch_rs<T, 2, 4, 4, 2, 0, 32>(a, s) : launch_rs<T, 4, 2, 2, 2, 0, 32>(a, s);
   }
   if (bn >= 256) return rs ? launch_rs<T, 2, 4, 4, 2>(a, s) : launch_cfg<T, 2, 4, 4, 2>(a, s);   // 256 px x 256 ch (a two-group ping-pong main loop was tried here: bit-identical, no faster)
   if (bn >= 128) return rs ? launch_rs<T, 4, 2, 2, 2>(a, s) : launch_cfg<T, 4, 2, 2, 2>(a, s);   // 256 px x 128 ch
   if (bn >= 64) return launch_cfg<T, 4, 2, 2, 1>(a, s);    // 256 px x 64 ch (register staging measured equal here)
-  if (wm_tuning[WM_TUNE_CONV_NARROW] == 0) return launch_cfg<T, 8, 1, 1, 1>(a, s);  // per-tap loop (A/B)
+  if (wm_tune(WM_TUNE_CONV_NARROW, 1) == 0) return launch_cfg<T, 8, 1, 1, 1>(a, s);  // per-tap loop (A/B)
   return launch_cfg<T, 8, 1, 1, 1, 1>(a, s);               // 256 px x 32 ch, narrow variant
 }
 
 }  // namespace
 
-bool wm_conv_force_generic() {  // WM_CONV_GENERIC (A/B switch): every conv through the generic kernel of conv.hip
-  static const bool g = wm_env("WM_CONV_GENERIC") != nullptr;
-  return g;
-}
 bool wm_conv3x3_out16_ok(const WmConvArgs& a) {  // exactly the launches launch_T sends to conv3x3_rs_kernel with a plain input
-  return !wm_conv_force_generic() && wm_conv3x3_applicable(a) && a.up_hs == 0 && (a.Cin / 64) % 2 == 0 && wm_tuning[WM_TUNE_CONV_RS] != 0 && pick_bn(a) >= 128;
+  return wm_conv3x3_applicable(a) && a.up_hs == 0 && (a.Cin / 64) % 2 == 0 && wm_tune(WM_TUNE_CONV_RS, 1) != 0 && pick_bn(a) >= 128;
 }
 
 bool wm_conv3x3_applicable(const WmConvArgs& a) {
@@ -746,7 +744,7 @@ bool wm_conv3x3_applicable(const WmConvArgs& a) {
 hipError_t wm_launch_conv3x3(const WmConvArgs& a_in, hipStream_t s) {
   WmConvArgs a = a_in;
 #ifdef WM_CONV_TIMING_EXPERIMENT
-  { const char* e = wm_env("WM_CONV_DBG"); a.dbg = e ? atoi(e) : 0; }
+  a.dbg = wm_tune(WM_TUNE_CONV_DBG, 0);   // (tools/conv_timing_experiment.py)
 #else
   a.dbg = 0;
 #endif

@@ -3,7 +3,6 @@
 // All are vectorised 16 B/lane where the layout allows and sized to ~8 blocks/CU (guides §6 G11/G13).
 #include "wm_common.h"
 #include "wm_kernels.h"
-#include <cstdlib>
 
 namespace {
 
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
 // the ps x W tile in LDS and writes it out as gw runs of ps * ps consecutive 16-bit elements (392 B).  The output-indexed kernel
 // above reads the image in 56-B patch-row segments: rocprofv3 showed 81 MB fetched for the 25.8 MB image of 8 views (3.2 x;
 // profiles/r02_hbm_by_kernel.md) — harmless in time (38 us per forward) but not the coalesced image read the design promises.
-// Same arithmetic, same rounding point (every e2e golden runs through it; WM_IM2COL_ROWS=0 selects the output-indexed kernel for an A/B).
+// Same arithmetic, same rounding point (every e2e golden runs through it; the output-indexed kernel stays for the shapes this one does not take).
 // Needs ps * W * 2 bytes of LDS and an even W.
 template <int T>
 WM_NO_PACKED_FP32 __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restrict__ img, u16* __restrict__ out, int N, int C,
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(256) void gs_splat_kernel(const float* __restrict__
     float tc[3];
     for (int a = 0; a < 3; ++a) tc[a] = -(R[0 * 3 + a] * v[0] + R[1 * 3 + a] * v[1] + R[2 * 3 + a] * v[2]);
     for (int a = 0; a < 3; ++a) means[i * 3 + a] = R[0 * 3 + a] * xc + R[1 * 3 + a] * yc + R[2 * 3 + a] * zc + tc[a];
-#ifdef WM_DBG_SPLAT_BUILD   // diagnostic builds only (-DWM_DBG_SPLAT_BUILD, then WM_DBG_SPLAT=1): dump the camera vector this thread READ in
+#ifdef WM_DBG_SPLAT_BUILD   // diagnostic builds only (-DWM_DBG_SPLAT_BUILD, then tuning dbg_splat = 1): dump the camera vector this thread READ in
     if (dbg) {              // place of the other attributes (tools/dbg_c5.py) — a product build cannot be made to corrupt its splats
       opac[i] = v[0]; wts[i] = v[1]; scales[i * 3 + 0] = v[2]; scales[i * 3 + 1] = v[7]; scales[i * 3 + 2] = v[8];
       quats[i * 4 + 0] = v[3]; quats[i * 4 + 1] = v[4]; quats[i * 4 + 2] = v[5]; quats[i * 4 + 3] = v[6];
@@ -572,7 +571,7 @@ hipError_t wm_launch_layernorm(const WmLnArgs& a, hipStream_t s) {
   if (a.D == nv * 256 && (nv == 4 || nv == 8) && a.w && a.b && !a.out_f32) {   // the backbone's LayerNorms (D = 1024) and the DPT heads' (D = 2048)
     // rows per wave: 1; 2 (tuning ln_rpw, D = 1024 only: one round of wave slots instead of 1.34 at 8 views) measured the same 12.5 us
     // (tools/bench_ln.py) and stays an A/B variant
-    const int rpw = nv == 4 && wm_tuning[WM_TUNE_LN_RPW] == 2 ? 2 : 1;
+    const int rpw = nv == 4 && wm_tune(WM_TUNE_LN_RPW, 1) == 2 ? 2 : 1;
     const dim3 g2((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)));
     if (nv == 4 && rpw == 2) {
       if (a.dtype == WM_T_BF16) hipLaunchKernelGGL((layernorm_fast_kernel<4, WM_T_BF16, 2>), g2, block, 0, s, a);
@@ -606,9 +605,8 @@ hipError_t wm_launch_im2col(const float* img, void* out, int N, int C, int H, in
                             int dtype, hipStream_t s) {
   const size_t total = (size_t)N * (H / ps) * (W / ps) * Kpad;
   if (!total) return hipSuccess;
-  static const bool rows_env = [] { const char* e = wm_env("WM_IM2COL_ROWS"); return !e || atoi(e) != 0; }();
   const size_t lds = (size_t)ps * W * sizeof(u16);
-  if (rows_env && ps % 2 == 0 && W % 2 == 0 && (C * ps * ps) % 2 == 0 && Kpad % 2 == 0 && lds <= 64 * 1024) {   // input-indexed form (coalesced image reads)
+  if (ps % 2 == 0 && W % 2 == 0 && (C * ps * ps) % 2 == 0 && Kpad % 2 == 0 && lds <= 64 * 1024) {   // input-indexed form (coalesced image reads)
     const dim3 grid((unsigned)(N * (H / ps) * C));
     if (dtype == WM_T_BF16) hipLaunchKernelGGL(im2col_rows_kernel<WM_T_BF16>, grid, dim3(256), lds, s, img, (u16*)out, N, C, H, W, ps, Kpad, normalize);
     else hipLaunchKernelGGL(im2col_rows_kernel<WM_T_F16>, grid, dim3(256), lds, s, img, (u16*)out, N, C, H, W, ps, Kpad, normalize);
@@ -633,7 +631,7 @@ hipError_t wm_launch_gs_splat(const float* gp, const float* img, const float* de
                               float* scales, float* opac, float* sh, float* wts, int N, int H, int W, hipStream_t s) {
   if (!N) return hipSuccess;
 #ifdef WM_DBG_SPLAT_BUILD
-  static const int dbg = wm_env("WM_DBG_SPLAT") ? 1 : 0;
+  const int dbg = wm_tune(WM_TUNE_DBG_SPLAT, 0) ? 1 : 0;   // (tools/micro/splat_hazard_repro.cpp)
 #else
   const int dbg = 0;
 #endif
@@ -669,8 +667,7 @@ hipError_t wm_launch_bilinear(const float* in, float* out, int N, int Hi, int Wi
   if (C % 8) return hipErrorInvalidValue;
   const size_t total = (size_t)N * Ho * Wo * (C / 4);
   if (!total) return hipSuccess;
-  static const int tiled_env = [] { const char* e = wm_env("WM_BILINEAR_TILED"); return e ? atoi(e) : 1; }();
-  if (tiled_env && bilinear_tiled_ok(Hi, Wi, Ho, Wo, C)) {
+  if (bilinear_tiled_ok(Hi, Wi, Ho, Wo, C)) {
     hipLaunchKernelGGL(bilinear_tiled_kernel<0>, dim3((unsigned)(N * ((Ho + 15) / 16) * ((Wo + 15) / 16))), dim3(256), 0, s, in, (void*)out, N, Hi, Wi, Ho, Wo, C, addx, addy);
     return hipGetLastError();
   }
@@ -683,8 +680,7 @@ hipError_t wm_launch_bilinear16(const float* in, void* out16, int N, int Hi, int
   if (C % 4) return hipErrorInvalidValue;
   const size_t total = (size_t)N * Ho * Wo * (C / 4);
   if (!total) return hipSuccess;
-  static const int tiled_env = [] { const char* e = wm_env("WM_BILINEAR_TILED"); return e ? atoi(e) : 1; }();
-  if (tiled_env && bilinear_tiled_ok(Hi, Wi, Ho, Wo, C)) {
+  if (bilinear_tiled_ok(Hi, Wi, Ho, Wo, C)) {
     const dim3 grid((unsigned)(N * ((Ho + 15) / 16) * ((Wo + 15) / 16)));
     if (dtype == WM_T_BF16) hipLaunchKernelGGL(bilinear_tiled_kernel<1>, grid, dim3(256), 0, s, in, out16, N, Hi, Wi, Ho, Wo, C, addx, addy);
     else hipLaunchKernelGGL(bilinear_tiled_kernel<2>, grid, dim3(256), 0, s, in, out16, N, Hi, Wi, Ho, Wo, C, addx, addy);

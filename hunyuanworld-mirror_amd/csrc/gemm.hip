@@ -17,10 +17,7 @@
 #include "wm_common.h"
 #include "wm_kernels.h"
 
-#include <cstdlib>
 #include <type_traits>
-
-int wm_tuning[WM_TUNE_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 
 namespace {
 
@@ -1506,7 +1503,7 @@ template <int T, int EPI>
 hipError_t launch_pp_E(const WmGemmArgs& a, int cfg, hipStream_t s) {
   // gemm_pp tuning: 3 = v1, 4 = v3 (half the barriers: bit-identical, measured +0.1 - 0.3 % on the forward, i.e. nothing — kept
   // selectable and under test as the record of that experiment), anything else = v2 (a barrier on both sides of every MFMA stage)
-  const int ver = EPI == WM_EPI_CONV ? 2 : wm_tuning[WM_TUNE_GEMM_PP];   // the pixel-row addressing of WM_EPI_CONV lives in v2 only
+  const int ver = EPI == WM_EPI_CONV ? 2 : wm_tune(WM_TUNE_GEMM_PP, 1);   // the pixel-row addressing of WM_EPI_CONV lives in v2 only
   if constexpr (EPI == WM_EPI_CONV) {
     return cfg == 4 ? launch_pp2<T, EPI>(a, s) : launch_pp2<T, EPI, 0, 3>(a, s);
   } else {
@@ -1537,11 +1534,9 @@ hipError_t launch_E(const WmGemmArgs& a, int cfg, hipStream_t s) {
 template <int T>
 hipError_t launch_T(const WmGemmArgs& a, int cfg, hipStream_t s) {
   // 16x16x32 MFMA main loop: measured +3..8 % on the N=1024 GEMMs (proj, fc2) and +0..2 % on QKV, neutral/negative
-  // on fc1 (tools/bench_gemm.py (rounds 1-2; git history)); WM_GEMM_MFMA16 = 0 / 2 forces it off / on for every backbone epilogue
-  static const int mf16_env = [] { const char* e = wm_env("WM_GEMM_MFMA16"); return e ? atoi(e) : 1; }();
-  static const int pp_env = [] { const char* e = wm_env("WM_GEMM_PP"); return e ? atoi(e) : 1; }();
-  const int mf16 = wm_tuning[WM_TUNE_GEMM_MFMA16] >= 0 ? wm_tuning[WM_TUNE_GEMM_MFMA16] : mf16_env;
-  const int pp = wm_tuning[WM_TUNE_GEMM_PP] >= 0 ? wm_tuning[WM_TUNE_GEMM_PP] : pp_env;
+  // on fc1 (tools/bench_gemm.py (rounds 1-2; git history)); gemm_mfma16 = 0 / 2 forces it off / on for every backbone epilogue
+  const int mf16 = wm_tune(WM_TUNE_GEMM_MFMA16, 1);
+  const int pp = wm_tune(WM_TUNE_GEMM_PP, 1);   // 0: no ping-pong kernel, 1 / 2: v2, 3: v1, 4: v3
 #ifdef WM_GEMM_PP_DEBUG  // timing experiments only (results are wrong): 11 no DMA, 12 no ds_read, 13 no barriers
   if (pp > 10 && a.epi == WM_EPI_F32 && T == WM_T_BF16)
     if (pp == 14) return launch_pp2<T, WM_EPI_F32, 4>(a, s);
@@ -1593,9 +1588,8 @@ hipError_t launch_T(const WmGemmArgs& a, int cfg, hipStream_t s) {
 }
 
 int pick_cfg(const WmGemmArgs& a) {
-  static const int forced = [] { const char* e = wm_env("WM_GEMM_CFG"); return e ? atoi(e) : -1; }();
+  const int forced = wm_tune(WM_TUNE_GEMM_CFG, -1);   // -1: choose below
   const bool conv = a.epi == WM_EPI_CONV;   // lives in the ping-pong v2 kernel only: tile 4 or 5 whatever the size
-  if (wm_tuning[WM_TUNE_GEMM_CFG] >= 0 && (!conv || wm_tuning[WM_TUNE_GEMM_CFG] == 4 || wm_tuning[WM_TUNE_GEMM_CFG] == 5)) return wm_tuning[WM_TUNE_GEMM_CFG];
   if (forced >= 0 && (!conv || forced == 4 || forced == 5)) return forced;
   if (!conv && (a.M <= 128 || a.N <= 128)) return 0;
   // minimise (rounds over the CUs) x (tile area / relative tile efficiency): tile quantisation is the
@@ -1670,7 +1664,7 @@ bool wm_gemm_fuses_ln(const WmGemmArgs& a) {
   // and between -0.15 and +0.87 ms on the 8-view forward by box (interleaved: 52.38 / 52.50 fused vs 52.39 / 52.74 on one box, 53.49 vs 52.62 on
   // another): the rendezvous' signal -> poll -> partial loads chain costs what the LayerNorm kernel's second read of a stream that the residual
   // epilogue has just left in the memory-side cache costs.  No gain to ship a second synchronisation structure for: off by default.
-  if (wm_tuning[WM_TUNE_LN_FUSE] != 1 || (a.ln_ld & 7) || (a.ldc & 3)) return false;
+  if (wm_tune(WM_TUNE_LN_FUSE, 0) != 1 || (a.ln_ld & 7) || (a.ldc & 3)) return false;
   int cfg, sched_b; bool pp2;
   plan_gemm(a, cfg, sched_b, pp2);
   if (!pp2 || cfg != 5) return false;   // the 192-row tile's kernel carries the fused epilogue
@@ -1698,24 +1692,22 @@ static void plan_gemm(const WmGemmArgs& a, int& cfg, int& sched_b, bool& pp2_out
   {
     // ping-pong v2 launches only (launch_T): backbone epilogues on the 256- / 192-row tiles
     const int ncu = wm_ncu();
-    const int pp = wm_tuning[WM_TUNE_GEMM_PP];
-    const bool pp2 = (cfg == 4 || cfg == 5) && (pp < 0 || pp == 1 || pp == 2 || pp == 4 || a.epi == WM_EPI_CONV) && (a.epi == WM_EPI_F32 || a.epi == WM_EPI_T16 || a.epi == WM_EPI_GELU_T16 || a.epi == WM_EPI_RESID || a.epi == WM_EPI_QKV || a.epi == WM_EPI_CONV);
-    const int ts = wm_tuning[WM_TUNE_GEMM_SCHED];   // -1 choose, 0 off (full-height tiles), > 0 that many bands
+    const int pp = wm_tune(WM_TUNE_GEMM_PP, 1);
+    const bool pp2 = (cfg == 4 || cfg == 5) && (pp == 1 || pp == 2 || pp == 4 || a.epi == WM_EPI_CONV) && (a.epi == WM_EPI_F32 || a.epi == WM_EPI_T16 || a.epi == WM_EPI_GELU_T16 || a.epi == WM_EPI_RESID || a.epi == WM_EPI_QKV || a.epi == WM_EPI_CONV);
+    const int ts = wm_tune(WM_TUNE_GEMM_SCHED, -1);   // -1 choose, 0 off (full-height tiles), > 0 that many bands
     if (pp2 && ts != 0) {
       // Measured (profiles/r04_gemm_timeline.md, `sched` rows): at M = 11008 the schedule takes 2.4 - 5.1 % off all four backbone
       // GEMMs (2.7 -> 3.0 and 0.9 -> 1.0 rounds of shorter blocks); at M = 44032 (8 - 11 rounds, where a ragged last round
       // costs at most a tenth) it measured +5 / +4 / +1.6 / -2.3 %.  So: only launches of at most three rounds.
       const long legacy_tiles = (long)((a.M + (cfg == 4 ? 255 : 191)) / (cfg == 4 ? 256 : 192)) * ((a.N + 255) / 256);
       if (ts > 0) sched_b = ts;
-      else if (legacy_tiles <= 3L * ncu && a.M <= 16384) pick_sched(a, ncu, wm_tuning[WM_TUNE_GEMM_CFG], cfg, sched_b);
+      else if (legacy_tiles <= 3L * ncu && a.M <= 16384) pick_sched(a, ncu, wm_tune(WM_TUNE_GEMM_CFG, -1), cfg, sched_b);
       const int U = (a.M + 15) / 16, full = cfg == 4 ? 16 : 12;
       if (sched_b > U) sched_b = U;
       // bands taller than the tile, or shorter than the kernel's instantiations go (a wave group drops at most 2 units): full-height grid
       if (sched_b <= 0 || (U + sched_b - 1) / sched_b > full || U / sched_b < full - 4) sched_b = 0;
     }
-    pp2_out = pp2 && wm_tuning[WM_TUNE_GEMM_PP] != 0;
-    static const int pp_env = [] { const char* e = wm_env("WM_GEMM_PP"); return e ? atoi(e) : 1; }();
-    if (wm_tuning[WM_TUNE_GEMM_PP] < 0 && !pp_env) pp2_out = false;
+    pp2_out = pp2 && pp != 0;
     if (a.epi == WM_EPI_CONV) pp2_out = true;
   }
 }
@@ -1735,7 +1727,7 @@ hipError_t wm_launch_gemm(const WmGemmArgs& a, hipStream_t s) {
   bool is_pp2;
   plan_gemm(a, cfg, sched_b, is_pp2);
   const bool fuse_ln = wm_gemm_fuses_ln(a);
-  const int gb = wm_tuning[WM_TUNE_GEMM_GROUP] >= 0 ? wm_tuning[WM_TUNE_GEMM_GROUP] : 6;  // row bands per supertile: 6 measured 2-3 % ahead of 4 / 8 at 32 views, equal at 8 (tools/bench_gemm_group.py)
+  const int gb = wm_tune(WM_TUNE_GEMM_GROUP, 6);  // row bands per supertile: 6 measured 2-3 % ahead of 4 / 8 at 32 views, equal at 8 (tools/bench_gemm_group.py)
   if (a.epi == WM_EPI_QKV) {
     if (a.qkv.tokens_per_view <= 0 || a.qkv.grid_w <= 0 || a.M >= (1 << 20) || a.qkv.tokens_per_view >= (1 << 16)) return hipErrorInvalidValue;
     WmGemmArgs b = a;
@@ -1748,7 +1740,7 @@ hipError_t wm_launch_gemm(const WmGemmArgs& a, hipStream_t s) {
   WmGemmArgs c = a;
   c.group_bands = gb;
   c.sched_bands = sched_b; c.sched_units = (a.M + 15) / 16;
-  c.pf_c = a.epi == WM_EPI_RESID && wm_tuning[WM_TUNE_RESID_PREFETCH] == 1 ? 1 : 0;
+  c.pf_c = a.epi == WM_EPI_RESID && wm_tune(WM_TUNE_RESID_PREFETCH, 0) == 1 ? 1 : 0;
   if (!fuse_ln) c.ln_out = nullptr;   // the kernel takes the fused epilogue iff ln_out is set
   return c.dtype == WM_T_BF16 ? launch_T<WM_T_BF16>(c, cfg, s) : launch_T<WM_T_F16>(c, cfg, s);
 }

@@ -7,8 +7,6 @@
 #include "wm_common.h"
 #include "wm_kernels.h"
 
-#include <cstdlib>
-
 namespace {
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
@@ -341,7 +339,7 @@ hipError_t wm_launch_linear_f32(const float* X, const float* W, const float* b, 
                                 int ldy, int pre_act, int post_act, const float* gamma, int accumulate, hipStream_t s) {
   if (M <= 0 || N <= 0) return hipSuccess;
   if (ldx % 4) return hipErrorInvalidValue;
-  if (M <= 64 && N % 16 == 0 && K % 1024 == 0 && wm_tuning[WM_TUNE_LIN_MFMA] != 0) {  // fp32-MFMA weight streaming
+  if (M <= 64 && N % 16 == 0 && K % 1024 == 0 && wm_tune(WM_TUNE_LIN_MFMA, 1) != 0) {  // fp32-MFMA weight streaming
     // waves per block (they split K) chosen so that the launch has ~2000 waves: N / 16 blocks alone would leave the
     // 2048-column layers at 2 waves per CU; row tiles of 16 (M <= 16 / 32 / 64)
 #define WM_LINM(KW_, MT_) hipLaunchKernelGGL((linear_f32_mfma_kernel<KW_, MT_>), dim3(N / 16), dim3(KW_ * 64), 0, s, X, W, b, Y, M, N, K, ldx, ldy, pre_act, post_act, gamma, accumulate)
@@ -357,19 +355,10 @@ hipError_t wm_launch_linear_f32(const float* X, const float* W, const float* b, 
 #define WM_STREAM(MT)                                                                                              \
   hipLaunchKernelGGL((linear_f32_stream_kernel<MT, 4>), dim3((N + 3) / 4, (M + MT - 1) / MT), dim3(256), 0, s, X, W, b, Y, \
                      M, N, K, ldx, ldy, pre_act, post_act, gamma, accumulate)
-    static const int nc_force = [] { const char* e = wm_env("WM_LIN_NC"); return e ? atoi(e) : 0; }();
-    const int nc = nc_force ? nc_force : 2;  // measured best (tools/bench_lin.py): ~2 TB/s
-    if (M <= 8 && nc == 8) {
-      hipLaunchKernelGGL((linear_f32_stream_kernel<8, 8>), dim3((N + 7) / 8, 1), dim3(256), 0, s, X, W, b, Y, M, N, K, ldx, ldy,
-                         pre_act, post_act, gamma, accumulate);
-    } else if (M <= 8 && nc == 2) {
+    if (M <= 8) {   // two columns per block: measured best of 1 / 2 / 4 / 8 (tools/bench_lin.py): ~2 TB/s
       hipLaunchKernelGGL((linear_f32_stream_kernel<8, 2>), dim3((N + 1) / 2, 1), dim3(256), 0, s, X, W, b, Y, M, N, K, ldx, ldy,
                          pre_act, post_act, gamma, accumulate);
-    } else if (M <= 8 && nc == 1) {
-      hipLaunchKernelGGL((linear_f32_stream_kernel<8, 1>), dim3(N, 1), dim3(256), 0, s, X, W, b, Y, M, N, K, ldx, ldy,
-                         pre_act, post_act, gamma, accumulate);
-    } else if (M <= 8) WM_STREAM(8);
-    else if (M <= 16) WM_STREAM(16);
+    } else if (M <= 16) WM_STREAM(16);
     else WM_STREAM(32);
 #undef WM_STREAM
     return hipGetLastError();

@@ -281,7 +281,7 @@ hipError_t wm_launch_repack_tap_major(const void* w16, void* wt16, int Co, int C
 
 hipError_t wm_launch_upconv_gather(const void* y16, const float* bias, float* out, int N, int Hi, int Wi, int Ho, int Wo, int Co, hipStream_t s) {
   if (N <= 0) return hipSuccess;
-  const bool lds_ok = wm_tuning[WM_TUNE_UP1_GATHER] != 2;   // 2: the direct (cache-fed) kernel on every shape (A/B)
+  const bool lds_ok = wm_tune(WM_TUNE_UP1_GATHER, 1) != 2;   // 2: the direct (cache-fed) kernel on every shape (A/B)
   if (Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1 || (Co != 128 && Co != 64 && Co != 32)) return hipErrorInvalidValue;
   if ((unsigned long long)N * Hi * Wi * 9ull * Co * 2ull >= (1ull << 32)) return hipErrorInvalidValue;   // the kernel's 32-bit byte offsets
   // resizes by about two per side (the rows / columns an 8 x 16 output tile samples fit the LDS tile): the LDS-staged kernel

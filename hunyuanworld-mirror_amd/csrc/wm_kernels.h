@@ -5,17 +5,7 @@
 #include <stddef.h>
 
 // The shipped library reads NO environment variable: kernel variants are chosen by the launchers and, for tests and A/B tools,
-// through wm_set_tuning.  The historical WM_* environment switches only exist in diagnostic builds (make EXTRA=-DWM_DIAG_ENV).
-#include <cstdlib>
-inline const char* wm_env(const char* name) {
-#ifdef WM_DIAG_ENV
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
+// through wm_set_tuning (the table at the end of this file).
 
 // ------------------------------------------------------------------ GEMM (gemm.hip)
 enum {
@@ -135,7 +125,7 @@ hipError_t wm_launch_attention_combine(const WmAttnArgs& a, int slots, hipStream
 hipError_t wm_launch_attention(const WmAttnArgs& a, hipStream_t s);
 int wm_attention_variant(const WmAttnArgs& a);                                            // which kernel the launch takes (attention.hip)
 void wm_attention_geometry(const WmAttnArgs& a, int* unit_rows, int* blocks_per_cu);   // its unit size and residency
-hipError_t wm_launch_attention_v3(const WmAttnArgs& a, int grid, int* flags, int minw, hipStream_t s);
+hipError_t wm_launch_attention_v3(const WmAttnArgs& a, int grid, int* flags, hipStream_t s);
 // one wave per SIMD, 128 query rows per wave, 512-row units (attention_v4.hip): bf16 (no max) and f16 (lazy integer max)
 hipError_t wm_launch_attention_v4(const WmAttnArgs& a, int grid, int* flags, hipStream_t s);
 // upper bound of the launch grid (units x splits) for sizing unit_flags
@@ -227,7 +217,6 @@ struct WmConvArgs {
   int dbg;             // timing experiments only (builds with -DWM_CONV_TIMING_EXPERIMENT; results are wrong): 1 no halo refill, 2 no epilogue, 4 no weight refill
 };
 bool wm_conv3x3_applicable(const WmConvArgs& a);
-bool wm_conv_force_generic();                     // WM_CONV_GENERIC set
 bool wm_conv3x3_out16_ok(const WmConvArgs& a);   // the launch would take a kernel that implements out16
 // 3x3 / s1 / p1 conv with 32 output channels on a 16-bit NHWC input (conv_n32.hip); zero: >= 16 B of device zeros
 struct WmConvN32Args {
@@ -263,8 +252,6 @@ hipError_t wm_launch_cam_update(float* pred, const float* delta, float* out, int
 // camera_params [S][9] -> c2w [S][16], K [S][9]  (camera_utils.py:46-75, worldmirror.py:165-175)
 hipError_t wm_launch_cam_matrices(const float* params, float* poses, float* intrs, int S, int H, int W, hipStream_t s);
 
-// Process-wide tuning overrides (wm_set_tuning in the C ABI; tests and A/B tools).  -1 = not set: the kernel's
-// launcher falls back to its environment variable, then to its built-in choice.
 // ------------------------------------------------------------------ 3D-Gaussian rasteriser (raster.hip)
 struct WmRasterArgs {
   const float* means; const float* quats; const float* scales; const float* opacities;  // [N,3] [N,4 wxyz] [N,3] [N]
@@ -296,6 +283,48 @@ hipError_t wm_launch_prune_gs(const float* means, const float* quats, const floa
                               const float* weights, int N, float voxel, float* o_means, float* o_quats, float* o_scales, float* o_opac,
                               float* o_sh, int* K_out, void* workspace, size_t ws_bytes, hipStream_t s);
 
-enum { WM_TUNE_GEMM_CFG = 0, WM_TUNE_GEMM_PP, WM_TUNE_GEMM_MFMA16, WM_TUNE_ATTN_QB, WM_TUNE_OP_LDPAD, WM_TUNE_ATTN_SPLITS, WM_TUNE_CONV_FUSE_UP, WM_TUNE_CONV_NARROW, WM_TUNE_CONV_BN, WM_TUNE_CONV_RS, WM_TUNE_LIN_MFMA, WM_TUNE_CONV_TPX, WM_TUNE_ATTN_TAIL, WM_TUNE_GEMM_GROUP, WM_TUNE_COMM_OVERLAP, WM_TUNE_HEADS_CONC, WM_TUNE_RCU_MID16, WM_TUNE_GEMM_SCHED, WM_TUNE_FORCE_GATHER, WM_TUNE_ATTN_OP_POLICY, WM_TUNE_COMM_P2P, WM_TUNE_LN_RPW, WM_TUNE_LN_FUSE, WM_TUNE_HEADS_MAIN, WM_TUNE_CONV_GEMM, WM_TUNE_RESID_PREFETCH, WM_TUNE_UP1_GATHER, WM_TUNE_TCONV, WM_TUNE_UP1_COMP, WM_TUNE_COUNT };
-extern int wm_tuning[WM_TUNE_COUNT];
+// ------------------------------------------------------------------ tuning table (wm_set_tuning in the C ABI; tests and A/B tools)
+// One line per key: enum name, key string.  Process-wide; -1 = not set: a consumer reads wm_tune(key, default) and states its
+// built-in choice there (INTEGRATION.md lists every key with its default, in this order).  The last three select timing / dump modes
+// with wrong results: only -DWM_ATTN_TIMING_EXPERIMENT, -DWM_CONV_TIMING_EXPERIMENT and -DWM_DBG_SPLAT_BUILD builds consult them.
+#define WM_TUNE_KEYS(X) \
+  X(GEMM_CFG, "gemm_cfg") \
+  X(GEMM_PP, "gemm_pp") \
+  X(GEMM_MFMA16, "gemm_mfma16") \
+  X(ATTN_QB, "attn_qb") \
+  X(OP_LDPAD, "op_ldpad") \
+  X(ATTN_SPLITS, "attn_splits") \
+  X(CONV_FUSE_UP, "conv_fuse_up") \
+  X(CONV_NARROW, "conv_narrow") \
+  X(CONV_BN, "conv_bn") \
+  X(CONV_RS, "conv_rs") \
+  X(LIN_MFMA, "lin_mfma") \
+  X(CONV_TPX, "conv_tpx") \
+  X(ATTN_TAIL, "attn_tail") \
+  X(GEMM_GROUP, "gemm_group") \
+  X(COMM_OVERLAP, "comm_overlap") \
+  X(HEADS_CONC, "heads_concurrent") \
+  X(RCU_MID16, "rcu_mid16") \
+  X(GEMM_SCHED, "gemm_sched") \
+  X(FORCE_GATHER, "force_gather") \
+  X(ATTN_OP_POLICY, "attn_op_policy") \
+  X(COMM_P2P, "comm_p2p") \
+  X(LN_RPW, "ln_rpw") \
+  X(LN_FUSE, "ln_fuse") \
+  X(HEADS_MAIN, "heads_main") \
+  X(CONV_GEMM, "conv_gemm") \
+  X(RESID_PREFETCH, "resid_prefetch") \
+  X(UP1_GATHER, "up1_gather") \
+  X(TCONV, "tconv") \
+  X(UP1_COMP, "up1_comp") \
+  X(CONV_BM, "conv_bm") \
+  X(RASTER_PPL, "raster_ppl") \
+  X(ATTN_DEBUG_SKIP, "attn_debug_skip") \
+  X(CONV_DBG, "conv_dbg") \
+  X(DBG_SPLAT, "dbg_splat")
+#define WM_TUNE_ENUM(name_, key_) WM_TUNE_##name_,
+enum { WM_TUNE_KEYS(WM_TUNE_ENUM) WM_TUNE_COUNT };
+#undef WM_TUNE_ENUM
+extern int wm_tuning[WM_TUNE_COUNT];   // defined beside wm_set_tuning (wm_model.cpp)
+inline int wm_tune(int key, int dflt) { return wm_tuning[key] < 0 ? dflt : wm_tuning[key]; }
 

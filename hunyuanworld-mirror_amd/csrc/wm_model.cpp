@@ -477,10 +477,14 @@ extern "C" void wm_host_resample_pos(const float* in, int gs, int D, int gh, int
     }
 }
 
+#define WM_TUNE_UNSET(name_, key_) -1,
+#define WM_TUNE_NAME(name_, key_) key_,
+int wm_tuning[WM_TUNE_COUNT] = {WM_TUNE_KEYS(WM_TUNE_UNSET)};
+static const char* const wm_tuning_keys[WM_TUNE_COUNT] = {WM_TUNE_KEYS(WM_TUNE_NAME)};
+
 extern "C" int wm_set_tuning(const char* key, int value) {
-  static const char* keys[WM_TUNE_COUNT] = {"gemm_cfg", "gemm_pp", "gemm_mfma16", "attn_qb", "op_ldpad", "attn_splits", "conv_fuse_up", "conv_narrow", "conv_bn", "conv_rs", "lin_mfma", "conv_tpx", "attn_tail", "gemm_group", "comm_overlap", "heads_concurrent", "rcu_mid16", "gemm_sched", "force_gather", "attn_op_policy", "comm_p2p", "ln_rpw", "ln_fuse", "heads_main", "conv_gemm", "resid_prefetch", "up1_gather", "tconv", "up1_comp"};
   for (int i = 0; i < WM_TUNE_COUNT; ++i)
-    if (key && strcmp(key, keys[i]) == 0) { wm_tuning[i] = value; return 0; }
+    if (key && strcmp(key, wm_tuning_keys[i]) == 0) { wm_tuning[i] = value; return 0; }
   return -1;
 }
 
@@ -839,10 +843,10 @@ struct ProfScope {
 
 // ---------------------------------------------------------------- collective
 wm_status comm_allgather(wm_handle* h, const void* send, void* recv, size_t bytes, hipStream_t s) {
-  ProfScope ps(h, 12, s);   // timing kind 12: the collective, on the queue it runs on (the compute queue unless WM_COMM_OVERLAP=1)
+  ProfScope ps(h, 12, s);   // timing kind 12: the collective, on the queue it runs on (the compute queue unless tuning comm_overlap = 1)
   Comm& cm = h->comm;
   if (cm.kind == 1) {
-    if (wm_tuning[WM_TUNE_COMM_P2P] == 1) {
+    if (wm_tune(WM_TUNE_COMM_P2P, 0) == 1) {
       // Direct all-gather (opt-in, tuning comm_p2p = 1 / bench.py --gather p2p): every rank sends its chunk to every peer and
       // receives every peer's chunk as ONE group of point-to-point operations, so each of the 7 xGMI links of a GPU carries one
       // chunk in each direction at once (~0.29 ms per layer link-bound at C4, against ~2.1 ms if the all-gather
@@ -963,14 +967,13 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
     WmAttnArgs a;
     memset(&a, 0, sizeof(a));
     a.Q = Q16; a.O = O16; a.H = heads; a.q_rows = M; a.q_head_stride = M; a.dtype = dt;
-    const bool force_gather = wm_tuning[WM_TUNE_FORCE_GATHER] > 0;  // 1-rank test of the collective path (tests/test_gpu_sharded.py)
-    // Opt-in (WM_COMM_OVERLAP=1 / tuning comm_overlap = 1; default: the gather on the compute queue): the overlapped form is
+    const bool force_gather = wm_tune(WM_TUNE_FORCE_GATHER, 0) > 0;  // 1-rank test of the collective path (tests/test_gpu_sharded.py)
+    // Opt-in (tuning comm_overlap = 1; default: the gather on the compute queue): the overlapped form is
     // exercised by 8 in-process ranks on one GPU (tests/test_gpu_fullsize.py), but RCCL has not run it on real links yet
     // (no multi-GPU node was available to any round): the simpler event-free path is the default until one 8-GPU run of both,
     // compared bit for bit, is on record.  The second queue is safe here: between fork and join the compute queue runs only
     // the attention kernels, which contain no packed-fp32 instruction (the hazard described at the DPT heads below needs one;
     // tests/test_kernel_resources_cpu.py disassembles them)
-    static const bool overlap_env = [] { const char* e = wm_env("WM_COMM_OVERLAP"); return e && atoi(e) != 0; }();
     a.part_o = B<float>(h, "ATT_PO"); a.part_ml = B<float>(h, "ATT_ML"); a.max_splits = WM_ATTN_MAX_SPLITS;
     a.unit_flags = B<int>(h, "ATT_FLAGS");
     const size_t hint_n = wm_attention_max_blocks((int)d.Mx, d.P < d.Td ? d.P : d.Td, d.heads);
@@ -990,7 +993,7 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
     }
     const bool sharded = is_global && (d.world > 1 || (force_gather && h->comm.kind != 0));
     const int ntpc = (M + 63) / 64;  // key tiles per rank chunk
-    const bool overlap = wm_tuning[WM_TUNE_COMM_OVERLAP] >= 0 ? wm_tuning[WM_TUNE_COMM_OVERLAP] != 0 : overlap_env;
+    const bool overlap = wm_tune(WM_TUNE_COMM_OVERLAP, 0) != 0;
     // every launch argument set of the overlapped form is checked BEFORE the fork: a rank that returned between the fork and
     // the collective would leave its peers waiting in the all-gather
     bool overlap_ok = sharded && overlap && d.world > 1 && ntpc >= 16;
@@ -1309,8 +1312,7 @@ wm_status conv(Ctx& c, const float* x, const std::string& wname, bool bias, cons
   a.Ho = (Hi + 2 * pad - ks) / stride + 1; a.Wo = (Wi + 2 * pad - ks) / stride + 1;
   a.relu_in = relu_in; a.resid_relu = resid_relu; a.relu_out = relu_out ? 1 : 0; a.in16 = in16 ? 1 : 0; a.dtype = c.hdt;
   if (out16) {  // the caller can take y as a 16-bit tensor (its only consumer rounds it to the operand type anyway): granted when the kernel can
-    static const int o16_env = [] { const char* e = wm_env("WM_OUTCONV_GEMM"); return e ? atoi(e) : 1; }();
-    *out16 = o16_env != 0 && wm_conv3x3_out16_ok(a);
+    *out16 = wm_conv3x3_out16_ok(a);
     a.out16 = *out16 ? 1 : 0;
   }
   // timing kinds by kernel instantiation: the F -> F 3x3 convs of the two large pyramid levels, output_conv1 with its fused
@@ -1318,7 +1320,7 @@ wm_status conv(Ctx& c, const float* x, const std::string& wname, bool bias, cons
   const bool pyr = ks == 3 && stride == 1 && up_hs == 0 && a.Cin == a.Cout && a.Cin >= 128;
   const int kind = up_hs > 0 ? 10 : pyr && Hi == 4 * c.d.gh ? 8 : pyr && Hi == 2 * c.d.gh ? 9 : 3;
   ProfScope ps(c.h, kind, c.s);
-  if (wm_tuning[WM_TUNE_CONV_GEMM] == 1 && in16 && ks == 3 && stride == 1 && pad == 1 && up_hs == 0 && a.Cin % 64 == 0 && a.Cout % 8 == 0 &&
+  if (wm_tune(WM_TUNE_CONV_GEMM, 0) == 1 && in16 && ks == 3 && stride == 1 && pad == 1 && up_hs == 0 && a.Cin % 64 == 0 && a.Cout % 8 == 0 &&
       (long)N * Hi * Wi >= 4096) {
     // a 16-bit NHWC input: the conv IS the ping-pong GEMM over (pixels) x (tap, channel), the A pieces DMA-ed from the shifted pixels
     WmGemmArgs g;
@@ -1337,10 +1339,9 @@ wm_status conv(Ctx& c, const float* x, const std::string& wname, bool bias, cons
 // y16: when non-null the caller can take y as a 16-bit tensor; *y16 tells whether it got one
 // conv1's output has ONE consumer, conv2's input staging, which applies ReLU and rounds to the operand type: where the kernel can, conv1
 // writes exactly that — relu(conv1) as a 16-bit tensor — and conv2 stages it unconverted (bit-identical values; a quarter of the
-// bytes written, a quarter read: 268 MB less traffic per RCU at 148^2 x 8 views).  WM_RCU_MID16=0: the fp32 intermediate (A/B).
+// bytes written, a quarter read: 268 MB less traffic per RCU at 148^2 x 8 views).  Tuning rcu_mid16 = 0: the fp32 intermediate (A/B).
 wm_status rcu(Ctx& c, const std::string& p, const float* x, const float* extra, float* tmp, float* y, int N, int Hh, int Ww, bool* y16 = nullptr) {
-  static const bool mid16_env = [] { const char* e = wm_env("WM_RCU_MID16"); return !e || atoi(e) != 0; }();
-  const bool want = wm_tuning[WM_TUNE_RCU_MID16] >= 0 ? wm_tuning[WM_TUNE_RCU_MID16] != 0 : mid16_env;
+  const bool want = wm_tune(WM_TUNE_RCU_MID16, 1) != 0;
   bool mid16 = false;
   wm_status st = conv(c, x, p + "conv1", true, nullptr, false, nullptr, tmp, N, Hh, Ww, 3, 1, 1, true, 0, 0, nullptr, nullptr, want ? &mid16 : nullptr, want);
   if (st) return st;
@@ -1390,7 +1391,7 @@ wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, b
         st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, W16(h, pj + ".weight"), D2, P16, oc[i], F(h, pj + ".bias"), nullptr, n * hw, oc[i], D2, &ex);
         if (st) return st;
         auto tc = h->tconv.find(p + std::to_string(i));
-        tconv_done[i] = wm_tuning[WM_TUNE_TCONV] != 0 && !is_gs && F_ == 256 && tc != h->tconv.end() && tc->second.w16 != nullptr;
+        tconv_done[i] = wm_tune(WM_TUNE_TCONV, 1) != 0 && !is_gs && F_ == 256 && tc != h->tconv.end() && tc->second.w16 != nullptr;
         if (tconv_done[i]) {   // ConvTranspose and layer{i+1}_rn as one GEMM at the token resolution, straight into rn[i]
           ProfScope ps(h, i == 0 ? 8 : 3, c.s);
           LCHK(c, launch_tconv(tc->second, c.hdt, P16, HB(i == 0 ? "dpt_rn1" : "dpt_rn2"), n, gh, gw, B<uint16_t>(h, "ZERO256"), c.s));
@@ -1431,19 +1432,19 @@ wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, b
     LCHK(c, wm_launch_bilinear(S0, S2, n, Hs[3], Ws[3], Hs[2], Ws[2], F_, nullptr, nullptr, c.s));
     float* cur = S2;  // output of the previous fusion block at level L
     // the two big resizes feed only a 3x3 conv: fuse them into that conv's input staging when the halo kernel applies
-    const bool fuse_on = wm_tuning[WM_TUNE_CONV_FUSE_UP] != 0 && wm_env("WM_CONV_GENERIC") == nullptr;
+    const bool fuse_on = wm_tune(WM_TUNE_CONV_FUSE_UP, 1) != 0;
     const bool fuse_up1 = fuse_on && F_ % 64 == 0 && 4 * Hs[0] * Ws[0] >= 256;
     const bool fuse_up2 = fuse_on && !is_gs && (F_ / 2) % 64 == 0;
     // output_conv1 on the resized tensor as nine 1x1 products at the LOW resolution + a bilinear gather (upconv.hip): a quarter of the MFMA work
     const Weight* w_oc1 = W(h, sc + "output_conv1.weight");
-    const bool gather_on = wm_tuning[WM_TUNE_UP1_GATHER] != 0 && c.hdt == WM_DT_F16 && w_oc1 && w_oc1->tap_major && F_ % 64 == 0 &&
+    const bool gather_on = wm_tune(WM_TUNE_UP1_GATHER, 1) != 0 && c.hdt == WM_DT_F16 && w_oc1 && w_oc1->tap_major && F_ % 64 == 0 &&
                            (int)w_oc1->shape[1] == F_ && ((int)w_oc1->shape[0] == 128 || (int)w_oc1->shape[0] == 64 || (int)w_oc1->shape[0] == 32) &&
                            (unsigned long long)n * Hs[0] * Ws[0] * 9ull * (unsigned long long)w_oc1->shape[0] * 2ull < (1ull << 32);   // the gather's 32-bit offsets
     bool up1_gather = false;
     const Up1Comp* comp = nullptr;
     {
       auto it = h->up1comp.find(p);
-      if (gather_on && wm_tuning[WM_TUNE_UP1_COMP] != 0 && it != h->up1comp.end() && it->second.w16 && it->second.co == (int)w_oc1->shape[0]) comp = &it->second;
+      if (gather_on && wm_tune(WM_TUNE_UP1_COMP, 1) != 0 && it != h->up1comp.end() && it->second.w16 && it->second.co == (int)w_oc1->shape[0]) comp = &it->second;
     }
     for (int L = 2; L >= 0; --L) {  // refinenet3 (level 2), refinenet2 (level 1), refinenet1 (level 0)
       const std::string rp = sc + "refinenet" + std::to_string(L + 1) + ".";
@@ -1491,9 +1492,8 @@ wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, b
     // output_conv2[0] un-fused (measured: 16-bit LDS-tiled resize 260 us + DMA-fed 32-channel conv 255 us vs 600-630 us for the
     // fused-resize kernel at 8 views, tools/bench_up_conv_n32.py): resize into `fused` as 16-bit, conv reads it by LDS-DMA
     bool tail_done = false;
-    static const int up2_env = [] { const char* e = wm_env("WM_UP2_UNFUSED"); return e ? atoi(e) : 1; }();
     const Weight* w_oc2 = W(h, sc + "output_conv2.0.weight");
-    const bool up2_unfused = up2_env && !is_gs && (F_ / 2) % 64 == 0 && F_ / 2 <= 128 && w_oc2 && w_oc2->shape[0] == 32 && w_oc2->w16 != nullptr;
+    const bool up2_unfused = !is_gs && (F_ / 2) % 64 == 0 && F_ / 2 <= 128 && w_oc2 && w_oc2->shape[0] == 32 && w_oc2->w16 != nullptr;
     if (up2_unfused) {
       LCHK(c, wm_launch_bilinear16(others[0], fused, n, H8, W8, Ho, Wo, F_ / 2, posx, posy, c.hdt, c.s));
       WmConvN32Args a;
@@ -1650,7 +1650,7 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
 
   // The camera head and the DPT heads are independent of each other: each runs on one of the handle's own queues, forked from and
   // joined back to the caller's stream (-1.15 ms per forward at 8 x 518^2, -5 ms at 32 views: the HBM-bound camera head and the under-filled small DPT
-  // levels run beside the MFMA-bound convs).  WM_HEADS_CONCURRENT=0 (tuning heads_concurrent = 0) keeps one queue.
+  // levels run beside the MFMA-bound convs).  Tuning heads_concurrent = 0 keeps one queue.
   // History: round 1 saw sparse wrong lanes with several queues active and fenced this off; round 2 traced it to packed-fp32 VALU
   // instructions (compiler-generated v_pk_mul_f32 / v_pk_fma_f32, op_sel forms) dropping one half's result in 16-lane groups when a
   // kernel of another kind shares the SIMD from another queue — reproduced without torch on the ROCm 7.2 runtime with the library's own
@@ -1659,8 +1659,7 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
   // WM_NO_PACKED_FP32 in wm_common.h; held by tests/test_kernel_resources_cpu.py, which disassembles every object), and those
   // GELU GEMMs of the backbone have finished before this fork.  tools/stress_concurrent_heads.py: 4 900 concurrent forwards (C2, C3, C5 flag set) bit-identical
   // to the serial one.
-  static const bool conc_env = [] { const char* e = wm_env("WM_HEADS_CONCURRENT"); return !e || atoi(e) != 0; }();
-  const bool serial = !(wm_tuning[WM_TUNE_HEADS_CONC] >= 0 ? wm_tuning[WM_TUNE_HEADS_CONC] != 0 : conc_env) || h->prof;
+  const bool serial = wm_tune(WM_TUNE_HEADS_CONC, 1) == 0 || h->prof;
   if (!h->hfork) LCHK(c, hipEventCreateWithFlags(&h->hfork, hipEventDisableTiming));
   if (!serial) LCHK(c, hipEventRecord(h->hfork, s));
   // ---- a11-a12: camera head.  864 MB of fp32 weights streamed 4 times for <= 64 rows: HBM-bound (1.3 ms at 8 views), so it runs
@@ -1684,7 +1683,7 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
       LCHK(c, wm_launch_cam_matrices(B<float>(h, "cam_params"), out->camera_poses, out->camera_intrs, nt, H, W_, cc.s));
     if (cam_async) LCHK(c, hipEventRecord(h->camjoin, cc.s));
   }
-  // ---- a13: DPT heads (worldmirror.py:74-98): independent of each other; one per queue only with WM_HEADS_CONCURRENT=1 (see above).
+  // ---- a13: DPT heads (worldmirror.py:74-98): independent of each other; one per queue unless tuning heads_concurrent = 0 (see above).
   {
     struct HeadJob { const char* p; int F; int od; int act; bool gs; float* attr; float* conf; };
     std::vector<HeadJob> jobs;
@@ -1702,7 +1701,7 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
     // a hardware queue and ran one after the other — the kernel trace of a timed forward showed one head done after 7.5 ms and the other
     // two, serialised, after 12.3 ms (profiles/r04_head_phase_queues.md).  Side heads are enqueued first, the caller's stream joins them
     // only behind its own head's launches.
-    const size_t main_k = jobs.empty() || wm_tuning[WM_TUNE_HEADS_MAIN] == 0 ? (size_t)-1 : jobs.size() - 1;   // (tuning heads_main = 0: every head forks, round 3's form — A/B)
+    const size_t main_k = jobs.empty() || wm_tune(WM_TUNE_HEADS_MAIN, 1) == 0 ? (size_t)-1 : jobs.size() - 1;   // (tuning heads_main = 0: every head forks, round 3's form — A/B)
     auto run_head = [&](size_t k, hipStream_t hs) -> wm_status {
       Ctx hc = c;
       hc.s = hs;
@@ -1840,7 +1839,8 @@ extern "C" wm_status wm_op_gemm(int dtype, int epi, const void* A, const void* W
   WmGemmArgs a;
   memset(&a, 0, sizeof(a));
   a.A = A; a.W = Wp; a.C = C; a.bias = bias; a.gamma = gamma; a.M = M; a.N = N; a.K = K; a.lda = K; a.ldw = K; a.ldc = N;
-  if (wm_tuning[WM_TUNE_OP_LDPAD] > 0) a.lda = a.ldw = K + wm_tuning[WM_TUNE_OP_LDPAD];  // wm_op_gemm only: operand row pitch (elements)
+  const int ldpad = wm_tune(WM_TUNE_OP_LDPAD, 0);   // wm_op_gemm only: operand row pitch K + ldpad (elements)
+  if (ldpad > 0) a.lda = a.ldw = K + ldpad;
   a.dtype = dtype; a.epi = epi;
   return wm_launch_gemm(a, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
@@ -1913,7 +1913,7 @@ extern "C" wm_status wm_op_attention_ex(int dtype, const void* Q, const void* K,
     a.unit_hint = unit_flags + nb;
     a.unit_stat = unit_flags + 2 * nb;
     // the forward's host policy (backbone_block) for ONE buffer at a time, when the tuning key attn_op_policy is 1 (tools/bench_attn_v4.py)
-    const bool policy = wm_tuning[WM_TUNE_ATTN_OP_POLICY] == 1;
+    const bool policy = wm_tune(WM_TUNE_ATTN_OP_POLICY, 0) == 1;
     static int* mirror = nullptr;
     static const int* key = nullptr;
     static int seen = 0, ttl = 0;

@@ -389,8 +389,8 @@ wm_status wm_rasterize_splats_backward(const float* means, const float* quats, c
                                        float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
                                        void* grad_workspace, size_t grad_workspace_bytes, void* stream);
 
-/* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  key: "gemm_cfg"
- * (tile config id), "gemm_pp" (0/1 ping-pong GEMM), "gemm_mfma16" (0/1/2), "attn_qb" (attention variant);
+/* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
+ * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
 int wm_set_tuning(const char* key, int value);
 

@@ -33,17 +33,59 @@ def test_exports_match_header(L):
 
 def test_shipped_library_reads_no_wm_environment_switch(L):
     """The product build must not be steerable from the environment (a WM_ATTN_DEBUG_SKIP in the shipped library could
-    return wrong results): every historical WM_* switch goes through wm_env(), which is compiled out without -DWM_DIAG_ENV, so no
-    such name may be left among the library's strings.  (getenv itself is still imported: rocPRIM's headers in raster / splat_prune.)"""
+    return wrong results).  The environment layer that every historical WM_* switch went through is gone from the sources — neither its
+    accessor nor the build flag that enabled it may come back anywhere under csrc/, the Makefile included — so no such name may be
+    left among the library's strings.  (getenv itself is still imported: rocPRIM's headers in raster / splat_prune.)"""
     data = open(LIB, "rb").read()
     names = set(m.decode() for m in re.findall(rb"WM_[A-Z][A-Z0-9_]{3,}", data))
     names -= {"WM_OK"}
     envlike = sorted(n for n in names if not n.startswith(("WM_ERR", "WM_EPI", "WM_T_", "WM_ACT", "WM_TUNE", "WM_RCCL")))
     assert not envlike, envlike
     src = os.path.join(ROOT, "hunyuanworld-mirror_amd", "csrc")
+    retired = ("wm_" + "env", "WM_DIAG_" + "ENV")    # (spelled in two parts: this file is searched for them too)
     for f in os.listdir(src):
+        path = os.path.join(src, f)
+        if not os.path.isfile(path) or f.endswith((".o", ".so")):
+            continue
+        text = open(path, errors="replace").read()
         if f.endswith((".hip", ".cpp")):
-            assert "getenv(" not in open(os.path.join(src, f)).read(), f
+            assert "getenv(" not in text, f
+        for name in retired:
+            assert name not in text, (f, name)
+
+
+# the key strings of wm_set_tuning before the table became a single list (wm_model.cpp of that commit): tests, tools and bench.py
+# call them by these spellings
+TUNING_KEYS_BEFORE_TABLE = ["gemm_cfg", "gemm_pp", "gemm_mfma16", "attn_qb", "op_ldpad", "attn_splits", "conv_fuse_up", "conv_narrow", "conv_bn",
+                            "conv_rs", "lin_mfma", "conv_tpx", "attn_tail", "gemm_group", "comm_overlap", "heads_concurrent", "rcu_mid16", "gemm_sched",
+                            "force_gather", "attn_op_policy", "comm_p2p", "ln_rpw", "ln_fuse", "heads_main", "conv_gemm", "resid_prefetch", "up1_gather",
+                            "tconv", "up1_comp"]
+
+
+def test_tuning_table_is_one_list(L):
+    """wm_kernels.h declares the tuning keys once (WM_TUNE_KEYS: enum name, key string); the enum, the name array of wm_set_tuning
+    and the all-unset initialiser are generated from it.  Every listed key is accepted (setting -1 = not set changes nothing), an
+    unknown key is refused with -1, INTEGRATION.md documents every key, and none of the 29 earlier key strings has been lost."""
+    hdr = open(os.path.join(ROOT, "hunyuanworld-mirror_amd", "csrc", "wm_kernels.h")).read()
+    body = hdr[hdr.index("#define WM_TUNE_KEYS(X)"):]
+    body = body[:body.index("#define WM_TUNE_ENUM")]
+    pairs = re.findall(r'^\s*X\((\w+),\s*"(\w+)"\)', body, flags=re.M)
+    keys = [k for _, k in pairs]
+    assert len(keys) >= 29 and len(set(keys)) == len(keys) and len(set(n for n, _ in pairs)) == len(pairs), pairs
+    assert len(pairs) == body.count("X("), "a line of the table the pattern does not read"
+    assert len(TUNING_KEYS_BEFORE_TABLE) == 29
+    assert set(TUNING_KEYS_BEFORE_TABLE) <= set(keys), set(TUNING_KEYS_BEFORE_TABLE) - set(keys)
+    assert keys[:29] == TUNING_KEYS_BEFORE_TABLE      # and in their order: new keys are appended
+    L.wm_set_tuning.restype = C.c_int
+    L.wm_set_tuning.argtypes = [C.c_char_p, C.c_int]
+    for k in keys:
+        assert L.wm_set_tuning(k.encode(), -1) == 0, k
+    assert L.wm_set_tuning(b"no_such_key", -1) == -1
+    assert L.wm_set_tuning(b"", -1) == -1 and L.wm_set_tuning(None, -1) == -1
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for k in keys:
+        assert "`" + k + "`" in doc, k
+    assert [doc.index("| `" + k + "` |") for k in keys] == sorted(doc.index("| `" + k + "` |") for k in keys), "INTEGRATION.md: table order"
 
 
 def test_config_struct_layout_matches_header():

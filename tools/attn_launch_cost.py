@@ -1,7 +1,8 @@
 """What the passes around the fast cross-view attention kernel cost per call: the recompute pass (the general kernel launched over the
-same grid, every block leaving at its flag) and the combine pass of the tail split.  Each variant is a process of its own (the
-switch is read once): python tools/attn_launch_cost.py [views] with WM_ATTN_DEBUG_SKIP = 0 / 1 / 2 / 3.  Timing only."""
-import ctypes as C, json, os, sys
+same grid, every block leaving at its flag) and the combine pass of the tail split.  Needs a library built with
+`make -C hunyuanworld-mirror_amd/csrc stamps` (-DWM_ATTN_TIMING_EXPERIMENT; WM_HIP_LIB=...libwm_hip_stamps.so): there the tuning
+`attn_debug_skip` = 1 skips the recompute pass, 2 the combine pass, 3 both (wrong results).  python tools/attn_launch_cost.py [views].  Timing only."""
+import ctypes as C, json, sys
 import torch
 sys.path.insert(0, '.')
 from hunyuanworld_mirror_amd import _lib
@@ -22,12 +23,15 @@ for nv in [int(x) for x in sys.argv[1:]] or [8, 32]:
         assert L.wm_op_attention_ex(0, p(q), p(k), p(v), p(o), H, M, M, 1, 0, 0, p(po), p(pml), p(flags), s) == 0
     for _ in range(10): run()
     torch.cuda.synchronize()
-    res = []
-    for rep in range(3):
-        n = 40 if nv <= 8 else 10
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n): run()
-        e1.record(); torch.cuda.synchronize()
-        res.append(round(e0.elapsed_time(e1) / n * 1e3, 1))
-    print(json.dumps({"views": nv, "skip": int(os.environ.get("WM_ATTN_DEBUG_SKIP", "0")), "us_per_call": res}), flush=True)
+    for skip in (0, 1, 2, 3):
+        assert L.wm_set_tuning(b"attn_debug_skip", skip) == 0
+        res = []
+        for rep in range(3):
+            n = 40 if nv <= 8 else 10
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n): run()
+            e1.record(); torch.cuda.synchronize()
+            res.append(round(e0.elapsed_time(e1) / n * 1e3, 1))
+        print(json.dumps({"views": nv, "skip": skip, "us_per_call": res}), flush=True)
+    L.wm_set_tuning(b"attn_debug_skip", -1)

@@ -1,7 +1,7 @@
 """Where does the 3x3 conv's time go?  Needs a library built with `make -C hunyuanworld-mirror_amd/csrc EXTRA=-DWM_CONV_TIMING_EXPERIMENT`
-(the switches exist only in that build; results of the switched runs are wrong by design).  WM_CONV_DBG bits: 1 = no halo refill in
+(the switches exist only in that build; results of the switched runs are wrong by design).  Tuning `conv_dbg` bits: 1 = no halo refill in
 the loop, 2 = no epilogue, 4 = no weight refill.  usage: python tools/conv_timing_experiment.py"""
-import ctypes as C, sys, json, math, os
+import ctypes as C, sys, json, math
 import torch
 sys.path.insert(0, '.')
 from hunyuanworld_mirror_amd import _lib
@@ -15,7 +15,7 @@ for (N, H, W, Cin, Cout, resid) in [(8, 148, 148, 256, 256, 0), (8, 148, 148, 25
     res = {}
     for rep in range(2):
         for dbg in (0, 1, 2, 4, 3, 7):
-            os.environ["WM_CONV_DBG"] = str(dbg)
+            assert L.wm_set_tuning(b"conv_dbg", dbg) == 0
             run = lambda: L.wm_op_conv(1, p(x), p(w16), p(b), p(r1) if resid else None, p(r2) if resid > 1 else None, p(y), N, H, W, Cin, Cout, 3, 1, 1, 1, 1 if resid else 0, s)
             for _ in range(2): run()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -24,3 +24,4 @@ for (N, H, W, Cin, Cout, resid) in [(8, 148, 148, 256, 256, 0), (8, 148, 148, 25
             e1.record(); torch.cuda.synchronize()
             res.setdefault(f"dbg{dbg}", []).append(round(e0.elapsed_time(e1) / 10 * 1e3, 1))
     print(json.dumps({"shape": [N, H, W, Cin, Cout], "residuals": resid, "GF": round(fl / 1e9, 1), "us": res}), flush=True)
+L.wm_set_tuning(b"conv_dbg", -1)

@@ -1,5 +1,5 @@
 // In-situ reproducer of the multi-queue finding with the library's own kernels, NO torch, NO Python:
-// queue 0 runs gs_splat_kernel (WM_DBG_SPLAT=1: it also dumps the camera vector each thread READ and the tc it COMPUTED),
+// queue 0 runs gs_splat_kernel (library built with -DWM_DBG_SPLAT_BUILD, tuning dbg_splat = 1: it also dumps the camera vector each thread READ and the tc it COMPUTED),
 // queues 1..NQ-1 run conv3x3 -> conv3x3 -> bilinear chains.  Checked per thread: camera vector read == the input (always, so far)
 // and tc == -(R^T t) recomputed on the host.  Build + run: tools/micro/run_splat_hazard.sh [rounds] [queues]
 #include <hip/hip_runtime.h>
@@ -13,7 +13,7 @@
 #define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { fprintf(stderr, "HIP error %s at line %d\n", hipGetErrorString(_e), __LINE__); exit(2); } } while (0)
 int main(int argc, char** argv) {
   const int rounds = argc > 1 ? atoi(argv[1]) : 30, NQ = argc > 2 ? atoi(argv[2]) : 5;
-  setenv("WM_DBG_SPLAT", "1", 1);
+  if (wm_set_tuning("dbg_splat", 1) != 0) return 2;
   const int N = 8, H = 518, W = 518, Cc = 128, Hh = 296, Nc = 4;
   const size_t npix = (size_t)N * H * W;
   std::mt19937 g(7);
