@@ -56,6 +56,7 @@ EXPORTS = [
     "wm_op_im2col", "wm_op_im2col7", "wm_op_dino_tokens", "wm_op_vgt_special", "wm_op_gemm_rowmap", "wm_op_gemm_convt", "wm_op_layernorm_rows",
     "wm_op_bilinear_add", "wm_op_bilinear16", "wm_op_copy2d", "wm_op_small_attention", "wm_op_adaln", "wm_op_cam_update", "wm_op_cam_matrices",
     "wm_op_linear_f32_ex", "wm_op_dpt_tail", "wm_op_up_conv_n32_tail",
+    "wm_photometric_loss_workspace_bytes", "wm_photometric_loss_forward_workspace_bytes", "wm_photometric_loss", "wm_photometric_loss_backward",
 ]
 
 _lib = None
@@ -155,6 +156,15 @@ def lib() -> C.CDLL:
     L.wm_rasterize_splats_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.wm_rasterize_splats_backward.restype = i32
+    i64p = C.POINTER(C.c_int64)
+    L.wm_photometric_loss_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.wm_photometric_loss_workspace_bytes.restype = C.c_size_t
+    L.wm_photometric_loss_forward_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.wm_photometric_loss_forward_workspace_bytes.restype = C.c_size_t
+    L.wm_photometric_loss.argtypes = [vp, i64p, vp, i64p, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]
+    L.wm_photometric_loss.restype = i32
+    L.wm_photometric_loss_backward.argtypes = [vp, i64p, vp, i64p, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.wm_photometric_loss_backward.restype = i32
     L.wm_preprocess_image_size.argtypes = [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.wm_preprocess_image_size.restype = i32
     L.wm_preprocess_image_workspace_bytes.argtypes = [i32, i32, i32, i32]

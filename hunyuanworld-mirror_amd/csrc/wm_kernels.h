@@ -277,6 +277,21 @@ struct WmRasterBwdArgs {
 size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects);
 hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s);
 
+// ------------------------------------------------------------------ L1 + SSIM photometric loss (photoloss.hip)
+// images [B,C,H,W] by element strides (sB, sC, sH, sW): NCHW and the permuted view of a channels-last tensor are read in place
+struct WmPhotoLossArgs {
+  const float* img1; const float* img2;
+  const int64_t* strides1; const int64_t* strides2;   // host, 4 each
+  int B, C, H, W, padding_valid;
+  void* workspace; size_t workspace_bytes;
+};
+size_t wm_photoloss_workspace_bytes(int B, int C, int H, int W);
+size_t wm_photoloss_forward_only_bytes(int B, int H, int W);   // 16 bytes per 32 x 32 tile: enough when want_backward = 0
+// forward: the two means to device floats; want_backward also leaves the three derivative maps in the workspace
+hipError_t wm_launch_photoloss_fwd(const WmPhotoLossArgs& a, int want_backward, float* out_ssim, float* out_l1, hipStream_t s);
+// backward: g_ssim / g_l1 device floats; grad_img1 is written with img1's strides
+hipError_t wm_launch_photoloss_bwd(const WmPhotoLossArgs& a, const float* g_ssim, const float* g_l1, float* grad_img1, hipStream_t s);
+
 // ------------------------------------------------------------------ voxel merge of splats (splat_prune.hip)
 size_t wm_prune_workspace_bytes(size_t N);
 hipError_t wm_launch_prune_gs(const float* means, const float* quats, const float* scales, const float* opac, const float* sh,

@@ -2029,6 +2029,40 @@ extern "C" wm_status wm_rasterize_splats_backward(const float* means, const floa
   if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
   return e == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
+extern "C" size_t wm_photometric_loss_workspace_bytes(int B, int C, int H, int W) { return wm_photoloss_workspace_bytes(B, C, H, W); }
+extern "C" size_t wm_photometric_loss_forward_workspace_bytes(int B, int C, int H, int W) {
+  return C > 0 ? wm_photoloss_forward_only_bytes(B, H, W) : 0;
+}
+static bool photo_args(WmPhotoLossArgs& a, const float* img1, const int64_t* strides1, const float* img2, const int64_t* strides2, int B, int C,
+                       int H, int W, int padding_valid, void* workspace, size_t workspace_bytes, bool maps) {
+  if (!img1 || !img2 || !strides1 || !strides2 || !workspace || B <= 0 || C <= 0 || H <= 0 || W <= 0) return false;
+  if (padding_valid && (H < 11 || W < 11)) return false;                 // fused_ssim would take the mean of an empty map
+  if (workspace_bytes < (maps ? wm_photoloss_workspace_bytes(B, C, H, W) : wm_photoloss_forward_only_bytes(B, H, W))) return false;
+  memset(&a, 0, sizeof(a));
+  a.img1 = img1; a.img2 = img2; a.strides1 = strides1; a.strides2 = strides2; a.B = B; a.C = C; a.H = H; a.W = W;
+  a.padding_valid = padding_valid; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  return true;
+}
+extern "C" wm_status wm_photometric_loss(const float* img1, const int64_t* strides1, const float* img2, const int64_t* strides2, int B, int C,
+                                         int H, int W, int padding_valid, int want_backward, float* out_ssim, float* out_l1,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  WmPhotoLossArgs a;
+  if (!out_ssim || !out_l1 ||
+      !photo_args(a, img1, strides1, img2, strides2, B, C, H, W, padding_valid, workspace, workspace_bytes, want_backward != 0))
+    return WM_ERR_INVALID;
+  const hipError_t e = wm_launch_photoloss_fwd(a, want_backward, out_ssim, out_l1, (hipStream_t)stream);
+  return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
+}
+extern "C" wm_status wm_photometric_loss_backward(const float* img1, const int64_t* strides1, const float* img2, const int64_t* strides2, int B,
+                                                  int C, int H, int W, int padding_valid, const float* g_ssim, const float* g_l1,
+                                                  float* grad_img1, const void* workspace, size_t workspace_bytes, void* stream) {
+  WmPhotoLossArgs a;
+  if (!g_ssim || !g_l1 || !grad_img1 ||
+      !photo_args(a, img1, strides1, img2, strides2, B, C, H, W, padding_valid, const_cast<void*>(workspace), workspace_bytes, true))
+    return WM_ERR_INVALID;
+  const hipError_t e = wm_launch_photoloss_bwd(a, g_ssim, g_l1, grad_img1, (hipStream_t)stream);
+  return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
+}
 extern "C" wm_status wm_op_layernorm(const float* x, void* y, const float* w, const float* b, int rows, int D, float eps, int out_f32,
                                      int dtype, void* stream) {
   WmLnArgs a;

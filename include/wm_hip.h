@@ -389,6 +389,37 @@ wm_status wm_rasterize_splats_backward(const float* means, const float* quats, c
                                        float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
                                        void* grad_workspace, size_t grad_workspace_bytes, void* stream);
 
+/* Fused L1 + SSIM photometric loss and its backward: the loss of the reference's "Post 3DGS Optimization" (README; gsplat's
+ * simple_trainer_worldmirror.py:785-792: F.l1_loss(colors, pixels) and 1 - fused_ssim(colors, pixels, padding="valid"), mixed with
+ * ssim_lambda = 0.2 by the caller).  fused_ssim is a CUDA-only extension; this is the published definition it implements:
+ *   window: 1-D Gaussian of 11 taps, sigma 1.5, normalised to sum 1; the 2-D window G is its outer product; all five filters
+ *   below are depthwise with zero padding 5.  For a = img1 (the render), b = img2 (the target):
+ *   mu1 = G*a, mu2 = G*b, s1 = G*(a a) - mu1^2, s2 = G*(b b) - mu2^2, s12 = G*(a b) - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2,
+ *   map = (2 mu1 mu2 + C1)(2 s12 + C2) / ((mu1^2 + mu2^2 + C1)(s1 + s2 + C2)).
+ *   *out_ssim = mean of map over B C H W (padding_valid = 0, "same") or over the map cropped by 5 on every side, B C (H-10) (W-10)
+ *   elements (padding_valid = 1); *out_l1 = mean |a - b| over B C H W.
+ * img1 / img2: fp32 [B,C,H,W] addressed by ELEMENT strides strides1 / strides2 = (sB, sC, sH, sW) (host arrays, read during the
+ * call): contiguous NCHW and the permuted view of a channels-last [B,H,W,C] tensor are both read in place.  out_ssim, out_l1:
+ * device floats.  want_backward = 1 also leaves d map / d mu1, d map / d s1 and d map / d s12 (zero outside the counted region) in
+ * the workspace for the backward call; want_backward = 0 gives the same two values, bit for bit.
+ * Backward: grad_img1 (fp32, img1's strides, overwritten) = *g_ssim * d ssim / d img1 + *g_l1 * sign(a - b) / (B C H W), sign(0) = 0;
+ * g_ssim, g_l1: device floats.  img2 gets no gradient.  CONTRACT: the same images, sizes, padding_valid and workspace as the
+ * forward call with want_backward = 1, the workspace UNTOUCHED in between.
+ * workspace: wm_photometric_loss_workspace_bytes bytes (12 bytes per image element + 16 per 32 x 32 tile) for the forward with
+ * want_backward = 1 and for the backward; a forward with want_backward = 0 touches the per-tile part only and accepts a workspace
+ * of wm_photometric_loss_forward_workspace_bytes bytes.
+ * Both calls are asynchronous on stream and never synchronise the host.  Sums run in a fixed order, no atomics: results are bitwise
+ * reproducible, and identical between layouts of the same values.  WM_ERR_INVALID: a size <= 0, padding_valid with H < 11 or
+ * W < 11 (the mean of an empty map), a workspace that is too small, a null pointer. */
+size_t wm_photometric_loss_workspace_bytes(int B, int C, int H, int W);
+size_t wm_photometric_loss_forward_workspace_bytes(int B, int C, int H, int W);
+wm_status wm_photometric_loss(const float* img1, const int64_t* strides1, const float* img2, const int64_t* strides2, int B, int C,
+                              int H, int W, int padding_valid, int want_backward, float* out_ssim, float* out_l1,
+                              void* workspace, size_t workspace_bytes, void* stream);
+wm_status wm_photometric_loss_backward(const float* img1, const int64_t* strides1, const float* img2, const int64_t* strides2, int B,
+                                       int C, int H, int W, int padding_valid, const float* g_ssim, const float* g_l1,
+                                       float* grad_img1, const void* workspace, size_t workspace_bytes, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
