@@ -6,3 +6,4 @@ from .geometry import (create_confidence_mask, depth_edge, depth_to_world_coords
 from .ingest import load_and_preprocess_images, preprocess_rgb  # noqa: F401
 from .rasterization import Rasterizer  # noqa: F401
 from .losses import fused_ssim, photometric_loss  # noqa: F401
+from .strategy import DefaultStrategy  # noqa: F401

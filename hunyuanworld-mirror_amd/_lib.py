@@ -57,6 +57,8 @@ EXPORTS = [
     "wm_op_bilinear_add", "wm_op_bilinear16", "wm_op_copy2d", "wm_op_small_attention", "wm_op_adaln", "wm_op_cam_update", "wm_op_cam_matrices",
     "wm_op_linear_f32_ex", "wm_op_dpt_tail", "wm_op_up_conv_n32_tail",
     "wm_photometric_loss_workspace_bytes", "wm_photometric_loss_forward_workspace_bytes", "wm_photometric_loss", "wm_photometric_loss_backward",
+    "wm_rasterize_backward_workspace_bytes_ex", "wm_rasterize_splats_backward_ex", "wm_rasterize_means2d",
+    "wm_densify_accumulate", "wm_densify_plan_workspace_bytes", "wm_densify_plan", "wm_densify_gather",
 ]
 
 _lib = None
@@ -156,6 +158,22 @@ def lib() -> C.CDLL:
     L.wm_rasterize_splats_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.wm_rasterize_splats_backward.restype = i32
+    L.wm_rasterize_backward_workspace_bytes_ex.argtypes = [i32, i32, i32, i32, C.c_size_t, i32]
+    L.wm_rasterize_backward_workspace_bytes_ex.restype = C.c_size_t
+    L.wm_rasterize_splats_backward_ex.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
+    L.wm_rasterize_splats_backward_ex.restype = i32
+    L.wm_rasterize_means2d.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, C.c_size_t, vp, vp, vp]
+    L.wm_rasterize_means2d.restype = i32
+    L.wm_densify_accumulate.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.wm_densify_accumulate.restype = i32
+    L.wm_densify_plan_workspace_bytes.argtypes = [C.c_size_t]
+    L.wm_densify_plan_workspace_bytes.restype = C.c_size_t
+    L.wm_densify_plan.argtypes = [vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, C.POINTER(i32 * 4), vp,
+                                  C.c_size_t, vp]
+    L.wm_densify_plan.restype = i32
+    L.wm_densify_gather.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.wm_densify_gather.restype = i32
     i64p = C.POINTER(C.c_int64)
     L.wm_photometric_loss_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.wm_photometric_loss_workspace_bytes.restype = C.c_size_t

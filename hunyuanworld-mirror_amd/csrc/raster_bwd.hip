@@ -11,18 +11,23 @@
 //              pixels, then over the 64 lanes by DPP adds, and written by 10 lanes as ONE 40-byte record.  Every (Gaussian, tile)
 //              pair has exactly one owner — this wave — and a slot of its own: the position the forward's emit pass gave it,
 //              pair offset of its (camera, Gaussian) + index of the tile inside the Gaussian's tile rectangle.  No atomics.
+//              With absgrad (gsplat's absgrad, RasterizeToPixels3DGSBwd.cu) the record is 12 floats: two more sums, of the absolute
+//              value of each pixel's 2-D mean terms, taken per pixel before any sum.  The record width is a template parameter
+//              (raster_bwd_composite.h); this file instantiates the 10-float kernel, raster_bwd_abs.hip the 12-float one.
 //   project    one thread per Gaussian, cameras in order: sums the Gaussian's contiguous pair records, pulls the sum back through
 //              conic -> 2-D covariance -> perspective projection -> camera -> world, then once through covariance -> quaternion, scale.
+//              On request it also writes the summed 2-D mean terms per (camera, Gaussian) before it folds them in: the gradient of
+//              the pixel-space means (and the absgrad sums) that a densification strategy reads.
+//   means2d    the pixel-space means the forward's projection left in its records, [C,N,2], zero where culled
 // Sums run in a fixed order everywhere, so gradients are bitwise reproducible run to run.
 #include "wm_common.h"
 #include "wm_kernels.h"
 #include "raster_common.h"
+#include "raster_bwd_composite.h"
 
 using namespace wm_raster;
 
 namespace {
-
-constexpr int PAIR_REC = 10;   // floats per (Gaussian, tile) pair: v_mx v_my | v_ca v_cb v_cc | v_opacity | v_r v_g v_b | v_depth
 
 // flag = 1 when keys0 is not in order (then the sorted list is in buffer 1).  Each radix pass is stable, so a buffer whose keys
 // are in order holds the final list whatever pass wrote it.
@@ -32,147 +37,17 @@ __global__ __launch_bounds__(256) void raster_locate_sorted_kernel(const unsigne
   if (i + 1 < n && keys0[i] > keys0[i + 1]) *flag = 1u;
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_of(float x) {   // lanes the row mask leaves out read 0
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, ROW_MASK, 0xf, false));
-}
-// sum over the 64 lanes; the total is valid in lanes 48-63
-__device__ __forceinline__ float wave_sum_hi(float v) {
-  v += dpp_of<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
-  v += dpp_of<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
-  v += dpp_of<0x141, 0xf>(v);   // row_half_mirror
-  v += dpp_of<0x140, 0xf>(v);   // row_mirror: every lane holds its row's sum
-  v += dpp_of<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-  v += dpp_of<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-  return v;
-}
-
-// Blending rules: raster.hip raster_composite_kernel (RasterizeToPixels3DGSFwd.cu:118-184); backward terms:
-// RasterizeToPixels3DGSBwd.cu (per pixel, last blended Gaussian to first).
-__global__ __launch_bounds__(64) void raster_composite_bwd_kernel(const G2D* __restrict__ g2d, const unsigned int* __restrict__ vals0,
-                                                                  const unsigned int* __restrict__ vals1, const unsigned int* __restrict__ which,
-                                                                  const unsigned int* __restrict__ offs, const unsigned long long* __restrict__ pair_offs,
-                                                                  int tw, int th, int width, int height, const float* __restrict__ out_depth,
-                                                                  const float* __restrict__ v_rgb, const float* __restrict__ v_depth,
-                                                                  const float* __restrict__ v_alpha, float* __restrict__ pair_grad) {
-  constexpr int PX = 2, PY = 2, NP = 4;
-  const int tile = blockIdx.x, cam = blockIdx.y;
-  const int ty = tile / tw, tx = tile - ty * tw;
-  const int lane = threadIdx.x;
-  const int i0 = ty * TILE + (lane >> 3) * PY, j0 = tx * TILE + (lane & 7) * PX;
-  const unsigned int begin = offs[cam * tw * th + tile], end = offs[cam * tw * th + tile + 1];
-  if (begin >= end) return;
-  const unsigned int* __restrict__ vals = __builtin_amdgcn_readfirstlane((int)*which) ? vals1 : vals0;
-  float px[NP], py[NP], T[NP];
-  int last[NP];
-  bool inimg[NP], open[NP];
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int i = i0 + q / PX, j = j0 + q % PX;
-    px[q] = (float)j + 0.5f; py[q] = (float)i + 0.5f;
-    inimg[q] = i < height && j < width;
-    open[q] = inimg[q];
-    T[q] = 1.0f; last[q] = -1;
-  }
-  // ---- front to back: the forward's decisions, transmittance only
-  unsigned int k = begin;
-  for (; k < end; ++k) {
-    const unsigned int v = __builtin_amdgcn_readfirstlane(vals[k]);
-    const G2D* __restrict__ rp = g2d + v;
-    const float mx = rp->mx, my = rp->my, ca = rp->ca, cb = rp->cb, cc = rp->cc, op = rp->opacity;
-    bool still = false;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const float dx = mx - px[q], dy = my - py[q];
-      const float sigma = 0.5f * (ca * dx * dx + cc * dy * dy) + cb * dx * dy;
-      const float alpha = fminf(0.999f, op * __expf(-sigma));
-      const bool hit = open[q] && !(sigma < 0.f) && !(alpha < ALPHA_THRESHOLD);
-      const float nT = T[q] * (1.0f - alpha);
-      const bool stop = hit && nT <= 1e-4f;
-      const bool blend = hit && !stop;
-      T[q] = blend ? nT : T[q];
-      last[q] = blend ? (int)k : last[q];
-      open[q] = open[q] && !stop;
-      still |= open[q];
-    }
-    if (__builtin_amdgcn_ballot_w64(still) == 0ull) { ++k; break; }
-  }
-  const unsigned int walked = k;   // entries [begin, walked) were looked at by the forward
-  // ---- cotangents of the four composited channels and of alpha; the expected-depth division D / max(alpha, 1e-10) is undone here
-  float vr[NP], vg[NP], vb[NP], vd[NP], tfv[NP], br[NP], bg[NP], bb[NP], bd[NP];
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const int i = i0 + q / PX, j = j0 + q % PX;
-    vr[q] = vg[q] = vb[q] = vd[q] = tfv[q] = 0.f;
-    br[q] = bg[q] = bb[q] = bd[q] = 0.f;
-    if (inimg[q]) {
-      const size_t pix = ((size_t)cam * height + i) * width + j;
-      const float al = 1.0f - T[q];
-      const float inv = 1.0f / fmaxf(al, 1e-10f);
-      const float ved = v_depth[pix];
-      vr[q] = v_rgb[3 * pix]; vg[q] = v_rgb[3 * pix + 1]; vb[q] = v_rgb[3 * pix + 2];
-      vd[q] = ved * inv;
-      const float val = v_alpha[pix] - (al > 1e-10f ? ved * out_depth[pix] * inv : 0.f);
-      tfv[q] = T[q] * val;
-    }
-  }
-  // ---- back to front
-  for (k = walked; k-- > begin;) {
-    const unsigned int v = __builtin_amdgcn_readfirstlane(vals[k]);
-    const G2D* __restrict__ rp = g2d + v;
-    const float mx = rp->mx, my = rp->my, ca = rp->ca, cb = rp->cb, cc = rp->cc, op = rp->opacity, depth = rp->depth;
-    const float cr = rp->r, cg = rp->g, cbl = rp->b;
-    float alpha[NP], vis[NP], dx[NP], dy[NP];
-    bool blend[NP], any = false;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      dx[q] = mx - px[q]; dy[q] = my - py[q];
-      const float sigma = 0.5f * (ca * dx[q] * dx[q] + cc * dy[q] * dy[q]) + cb * dx[q] * dy[q];
-      vis[q] = __expf(-sigma);
-      alpha[q] = fminf(0.999f, op * vis[q]);
-      blend[q] = inimg[q] && !(sigma < 0.f) && !(alpha[q] < ALPHA_THRESHOLD) && (int)k <= last[q];
-      any |= blend[q];
-    }
-    if (__builtin_amdgcn_ballot_w64(any) == 0ull) continue;   // nobody in the tile blended this Gaussian: its record stays zero
-    float s_mx = 0.f, s_my = 0.f, s_ca = 0.f, s_cb = 0.f, s_cc = 0.f, s_op = 0.f, s_r = 0.f, s_g = 0.f, s_b = 0.f, s_d = 0.f;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-      const float ra = __builtin_amdgcn_rcpf(1.0f - alpha[q]);
-      const float Tb = T[q] * ra;                       // transmittance in front of this Gaussian
-      const float fac = blend[q] ? alpha[q] * Tb : 0.f;
-      s_r += fac * vr[q]; s_g += fac * vg[q]; s_b += fac * vb[q]; s_d += fac * vd[q];
-      float va = (cr * Tb - br[q] * ra) * vr[q] + (cg * Tb - bg[q] * ra) * vg[q] + (cbl * Tb - bb[q] * ra) * vb[q] +
-                 (depth * Tb - bd[q] * ra) * vd[q] + tfv[q] * ra;
-      va = blend[q] ? va : 0.f;
-      br[q] += cr * fac; bg[q] += cg * fac; bb[q] += cbl * fac; bd[q] += depth * fac;
-      T[q] = blend[q] ? Tb : T[q];
-      const float ov = op * vis[q];
-      const float vs = ov <= 0.999f ? -ov * va : 0.f;   // the 0.999 cap passes no gradient
-      s_op += ov <= 0.999f ? vis[q] * va : 0.f;
-      s_ca += 0.5f * vs * dx[q] * dx[q]; s_cb += vs * dx[q] * dy[q]; s_cc += 0.5f * vs * dy[q] * dy[q];
-      s_mx += vs * (ca * dx[q] + cb * dy[q]); s_my += vs * (cb * dx[q] + cc * dy[q]);
-    }
-    s_mx = wave_sum_hi(s_mx); s_my = wave_sum_hi(s_my); s_ca = wave_sum_hi(s_ca); s_cb = wave_sum_hi(s_cb); s_cc = wave_sum_hi(s_cc);
-    s_op = wave_sum_hi(s_op); s_r = wave_sum_hi(s_r); s_g = wave_sum_hi(s_g); s_b = wave_sum_hi(s_b); s_d = wave_sum_hi(s_d);
-    // slot of this pair: where the forward's emit pass wrote it
-    const int rect = rp->rect;
-    const int x0 = rect & 255, y0 = (rect >> 8) & 255, x1 = (rect >> 16) & 255;
-    const unsigned long long slot = pair_offs[v] + (unsigned long long)((ty - y0) * (x1 - x0) + (tx - x0));
-    float o = s_mx;
-    o = lane == 49 ? s_my : o; o = lane == 50 ? s_ca : o; o = lane == 51 ? s_cb : o; o = lane == 52 ? s_cc : o; o = lane == 53 ? s_op : o;
-    o = lane == 54 ? s_r : o; o = lane == 55 ? s_g : o; o = lane == 56 ? s_b : o; o = lane == 57 ? s_d : o;
-    if (lane >= 48 && lane < 48 + PAIR_REC) pair_grad[slot * PAIR_REC + (lane - 48)] = o;
-  }
-}
-
 // _torch_impl.py:11-29,45-61 (quaternion, scale -> covariance), :250-283 (world -> camera), :78-133 (perspective), :329-355 (conic)
+// M2D: also write v_means2d [C,N,2] (and, with 12-float records, v_means2d_abs): the summed pair terms, zero where culled
+template <int REC, bool M2D>
 __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __restrict__ means, const float* __restrict__ quats,
                                                                  const float* __restrict__ scales, const float* __restrict__ colors_in, int is_sh,
                                                                  const float* __restrict__ viewmats, const float* __restrict__ Ks, int N, int C,
                                                                  int width, int height, const G2D* __restrict__ g2d,
                                                                  const unsigned long long* __restrict__ pair_offs, const float* __restrict__ pair_grad,
                                                                  float* __restrict__ v_means, float* __restrict__ v_quats, float* __restrict__ v_scales,
-                                                                 float* __restrict__ v_opac, float* __restrict__ v_colors) {
+                                                                 float* __restrict__ v_opac, float* __restrict__ v_colors,
+                                                                 float* __restrict__ v_means2d, float* __restrict__ v_means2d_abs) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= N) return;
   const float q0 = quats[4 * g], q1 = quats[4 * g + 1], q2 = quats[4 * g + 2], q3 = quats[4 * g + 3];
@@ -197,14 +72,24 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
     const size_t idx = (size_t)c * N + g;
     const int rect = g2d[idx].rect;
     const int cnt = (((rect >> 16) & 255) - (rect & 255)) * (((rect >> 24) & 255) - ((rect >> 8) & 255));
-    if (cnt <= 0) continue;   // culled for this camera
-    float p[PAIR_REC];
+    if (cnt <= 0) {           // culled for this camera
+      if constexpr (M2D) {
+        v_means2d[2 * idx] = 0.f; v_means2d[2 * idx + 1] = 0.f;
+        if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = 0.f; v_means2d_abs[2 * idx + 1] = 0.f; }
+      }
+      continue;
+    }
+    float p[REC];
 #pragma unroll
-    for (int i = 0; i < PAIR_REC; ++i) p[i] = 0.f;
-    const float* rec = pair_grad + pair_offs[idx] * PAIR_REC;
+    for (int i = 0; i < REC; ++i) p[i] = 0.f;
+    const float* rec = pair_grad + pair_offs[idx] * REC;
     for (int t = 0; t < cnt; ++t)
 #pragma unroll
-      for (int i = 0; i < PAIR_REC; ++i) p[i] += rec[(size_t)t * PAIR_REC + i];
+      for (int i = 0; i < REC; ++i) p[i] += rec[(size_t)t * REC + i];
+    if constexpr (M2D) {
+      v_means2d[2 * idx] = p[0]; v_means2d[2 * idx + 1] = p[1];
+      if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = p[10]; v_means2d_abs[2 * idx + 1] = p[11]; }
+    }
     const float v_mx = p[0], v_my = p[1], v_ca = p[2], v_cb = p[3], v_cc = p[4];
     a_op += p[5]; a_col[0] += p[6]; a_col[1] += p[7]; a_col[2] += p[8];
     // forward, as raster_project_kernel
@@ -315,11 +200,51 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
   }
 }
 
+// the forward's pixel-space means out of its projection records; zero where the camera culled the Gaussian (a radius of 0)
+__global__ __launch_bounds__(256) void raster_means2d_kernel(const G2D* __restrict__ g2d, const int* __restrict__ radii, size_t CN,
+                                                             float* __restrict__ means2d) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= CN) return;
+  const bool seen = radii[2 * i] > 0 && radii[2 * i + 1] > 0;
+  means2d[2 * i] = seen ? g2d[i].mx : 0.f;
+  means2d[2 * i + 1] = seen ? g2d[i].my : 0.f;
+}
+
+template <int REC, bool M2D>
+void launch_bwd_kernels(const WmRasterBwdArgs& b, const RasterWs& w, unsigned int* flag, float* pair_grad, int tw, int th, hipStream_t s) {
+  const WmRasterArgs& a = b.fwd;
+  const size_t N = a.N, C = a.C;
+  if (b.n_isects > 0) {
+    hipLaunchKernelGGL(raster_locate_sorted_kernel, dim3((unsigned)((b.n_isects + 255) / 256)), dim3(256), 0, s, w.keys[0], (unsigned int)b.n_isects, flag);
+    const dim3 grid((unsigned)(tw * th), (unsigned)C);
+    if constexpr (REC == PAIR_REC_ABS)
+      wm_launch_composite_bwd_abs(grid, s, w.g2d, w.vals[0], w.vals[1], flag, w.tile_offs, w.offsets, tw, th, a.width, a.height, b.out_depth, b.v_rgb,
+                                  b.v_depth, b.v_alpha, pair_grad);
+    else
+      hipLaunchKernelGGL(raster_composite_bwd_kernel<PAIR_REC>, grid, dim3(64), 0, s, w.g2d, w.vals[0], w.vals[1], flag, w.tile_offs, w.offsets, tw,
+                         th, a.width, a.height, b.out_depth, b.v_rgb, b.v_depth, b.v_alpha, pair_grad);
+  }
+  hipLaunchKernelGGL((raster_project_bwd_kernel<REC, M2D>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.means, a.quats, a.scales, a.colors,
+                     a.is_sh, a.viewmats, a.Ks, a.N, a.C, a.width, a.height, w.g2d, w.offsets, pair_grad, b.v_means, b.v_quats, b.v_scales,
+                     b.v_opacities, b.v_colors, b.v_means2d, b.v_means2d_abs);
+}
+
 }  // namespace
 
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects) {
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad) {
   (void)N; (void)C; (void)width; (void)height;
-  return align256(256) + align256(n_isects * PAIR_REC * sizeof(float));   // buffer flag | pair records
+  return align256(256) + align256(n_isects * (absgrad ? PAIR_REC_ABS : PAIR_REC) * sizeof(float));   // buffer flag | pair records
+}
+
+hipError_t wm_launch_rasterize_means2d(const void* workspace, size_t workspace_bytes, int N, int C, int width, int height, size_t max_isects,
+                                       const int* radii, float* means2d, hipStream_t s) {
+  const int tw = (width + TILE - 1) / TILE, th = (height + TILE - 1) / TILE;
+  if (N <= 0 || C <= 0 || tw > 255 || th > 255 || (size_t)N * C >= (1ull << 31)) return hipErrorInvalidValue;
+  RasterWs w = carve((char*)const_cast<void*>(workspace), N, C, tw * th, max_isects);
+  if (w.total > workspace_bytes) return hipErrorInvalidValue;
+  const size_t CN = (size_t)N * C;
+  hipLaunchKernelGGL(raster_means2d_kernel, dim3((unsigned)((CN + 255) / 256)), dim3(256), 0, s, w.g2d, radii, CN, means2d);
+  return hipGetLastError();
 }
 
 hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s) {
@@ -328,20 +253,17 @@ hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s) {
   if (a.N <= 0 || a.C <= 0 || tw > 255 || th > 255) return hipErrorInvalidValue;
   const size_t N = a.N, C = a.C, CN = N * C;
   if (CN >= (1ull << 31) || b.n_isects > a.max_isects || b.n_isects >= (1ull << 31)) return hipErrorInvalidValue;
+  if (b.absgrad && (!b.v_means2d || !b.v_means2d_abs)) return hipErrorInvalidValue;
   RasterWs w = carve((char*)a.workspace, N, C, tiles, a.max_isects);
   if (w.total > a.workspace_bytes) return hipErrorInvalidValue;
-  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects) > b.grad_workspace_bytes) return hipErrorInvalidValue;
+  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad) > b.grad_workspace_bytes) return hipErrorInvalidValue;
+  const int rec = b.absgrad ? PAIR_REC_ABS : PAIR_REC;
   unsigned int* flag = (unsigned int*)b.grad_workspace;
   float* pair_grad = (float*)((char*)b.grad_workspace + align256(256));
-  hipError_t e = hipMemsetAsync(b.grad_workspace, 0, align256(256) + b.n_isects * PAIR_REC * sizeof(float), s);
+  hipError_t e = hipMemsetAsync(b.grad_workspace, 0, align256(256) + b.n_isects * rec * sizeof(float), s);
   if (e != hipSuccess) return e;
-  if (b.n_isects > 0) {
-    hipLaunchKernelGGL(raster_locate_sorted_kernel, dim3((unsigned)((b.n_isects + 255) / 256)), dim3(256), 0, s, w.keys[0], (unsigned int)b.n_isects, flag);
-    hipLaunchKernelGGL(raster_composite_bwd_kernel, dim3((unsigned)tiles, (unsigned)C), dim3(64), 0, s, w.g2d, w.vals[0], w.vals[1], flag, w.tile_offs,
-                       w.offsets, tw, th, a.width, a.height, b.out_depth, b.v_rgb, b.v_depth, b.v_alpha, pair_grad);
-  }
-  hipLaunchKernelGGL(raster_project_bwd_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.means, a.quats, a.scales, a.colors, a.is_sh,
-                     a.viewmats, a.Ks, a.N, a.C, a.width, a.height, w.g2d, w.offsets, pair_grad, b.v_means, b.v_quats, b.v_scales, b.v_opacities,
-                     b.v_colors);
+  if (b.absgrad) launch_bwd_kernels<PAIR_REC_ABS, true>(b, w, flag, pair_grad, tw, th, s);
+  else if (b.v_means2d) launch_bwd_kernels<PAIR_REC, true>(b, w, flag, pair_grad, tw, th, s);
+  else launch_bwd_kernels<PAIR_REC, false>(b, w, flag, pair_grad, tw, th, s);
   return hipGetLastError();
 }

@@ -273,9 +273,34 @@ struct WmRasterBwdArgs {
   const float* v_rgb; const float* v_depth; const float* v_alpha;   // cotangents [C,H,W,3] [C,H,W] [C,H,W]
   float* v_means; float* v_quats; float* v_scales; float* v_opacities; float* v_colors;   // [N,3] [N,4] [N,3] [N] [N,3]
   void* grad_workspace; size_t grad_workspace_bytes;
+  // optional: gradient of the pixel-space means [C,N,2] (zero where culled) and, with absgrad = 1, the sums of per-pixel absolute values
+  float* v_means2d; float* v_means2d_abs; int absgrad;
 };
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects);
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad = 0);
 hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s);
+// the pixel-space means of the forward whose workspace this is, [C,N,2], zero where radii [C,N,2] has a 0
+hipError_t wm_launch_rasterize_means2d(const void* workspace, size_t workspace_bytes, int N, int C, int width, int height, size_t max_isects,
+                                       const int* radii, float* means2d, hipStream_t s);
+
+// ------------------------------------------------------------------ splat densification (densify.hip): gsplat DefaultStrategy
+struct WmDensifyPlanArgs {
+  const float* grad2d; const float* count; const float* radii_state;   // [N] running state (radii_state may be null)
+  const float* scales; const float* opacities;                         // [N,3] log scales, [N] logit opacities
+  int N;
+  float grow_grad2d, grow_scale3d, grow_scale2d, prune_opa, prune_scale3d, prune_scale2d;   // the two 3-D limits already times scene_scale
+  int use_scale2d, prune_big, revised_opacity;   // step < refine_scale2d_stop_iter | step > reset_every | revised opacity of split children
+  int* src; int* kind; int* rank;                // [3 N] rows of the plan; [0, n_out) are valid
+  int* counts;                                   // host: n_dupli, n_split, n_prune, n_out
+  void* workspace; size_t workspace_bytes;
+};
+enum { WM_DENSIFY_KEEP = 0, WM_DENSIFY_DUP = 1, WM_DENSIFY_SPLIT0 = 2, WM_DENSIFY_SPLIT1 = 3 };
+enum { WM_GATHER_COPY = 0, WM_GATHER_ZERO_NEW = 1, WM_GATHER_MEANS = 2, WM_GATHER_SCALES = 3, WM_GATHER_OPACITIES_REVISED = 4 };
+hipError_t wm_launch_densify_accumulate(const float* v_means2d, const int* radii, int N, int C, int width, int height, float* grad2d,
+                                        float* count, float* radii_state, hipStream_t s);
+size_t wm_densify_plan_ws_bytes(size_t N);
+hipError_t wm_launch_densify_plan(const WmDensifyPlanArgs& a, hipStream_t s);
+hipError_t wm_launch_densify_gather(const float* in, float* out, int N, int R, int mode, const int* src, const int* kind, const int* rank,
+                                    int n_out, const float* quats, const float* scales, const float* noise, hipStream_t s);
 
 // ------------------------------------------------------------------ L1 + SSIM photometric loss (photoloss.hip)
 // images [B,C,H,W] by element strides (sB, sC, sH, sW): NCHW and the permuted view of a channels-last tensor are read in place

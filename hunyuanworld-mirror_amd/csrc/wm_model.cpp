@@ -2029,6 +2029,74 @@ extern "C" wm_status wm_rasterize_splats_backward(const float* means, const floa
   if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
   return e == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
+extern "C" size_t wm_rasterize_backward_workspace_bytes_ex(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad) {
+  return wm_raster_bwd_workspace_bytes(n_gaussians, n_cameras, width, height, n_isects, want_absgrad ? 1 : 0);
+}
+extern "C" wm_status wm_rasterize_splats_backward_ex(const float* means, const float* quats, const float* scales, const float* opacities,
+                                                     const float* colors, int colors_are_sh0, int n_gaussians, const float* viewmats,
+                                                     const float* Ks, int n_cameras, int width, int height, const void* workspace,
+                                                     size_t workspace_bytes, size_t max_isects, size_t n_isects, const float* out_rgb,
+                                                     const float* out_depth, const float* out_alpha, const float* v_rgb, const float* v_depth,
+                                                     const float* v_alpha, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                                                     float* v_colors, float* v_means2d, float* v_means2d_abs, int want_absgrad,
+                                                     void* grad_workspace, size_t grad_workspace_bytes, void* stream) {
+  (void)out_rgb; (void)out_alpha;
+  if (!means || !quats || !scales || !opacities || !colors || !viewmats || !Ks || !workspace || !out_depth || !v_rgb || !v_depth || !v_alpha ||
+      !v_means || !v_quats || !v_scales || !v_opacities || !v_colors || !grad_workspace)
+    return WM_ERR_INVALID;
+  if (want_absgrad && (!v_means2d || !v_means2d_abs)) return WM_ERR_INVALID;
+  if (n_isects > max_isects) return WM_ERR_STATE;
+  WmRasterBwdArgs b;
+  memset(&b, 0, sizeof(b));
+  WmRasterArgs& a = b.fwd;
+  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = colors; a.is_sh = colors_are_sh0;
+  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
+  a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
+  b.n_isects = n_isects; b.out_depth = out_depth; b.v_rgb = v_rgb; b.v_depth = v_depth; b.v_alpha = v_alpha;
+  b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_opacities = v_opacities; b.v_colors = v_colors;
+  b.v_means2d = v_means2d; b.v_means2d_abs = want_absgrad ? v_means2d_abs : nullptr; b.absgrad = want_absgrad ? 1 : 0;
+  b.grad_workspace = grad_workspace; b.grad_workspace_bytes = grad_workspace_bytes;
+  const hipError_t e = wm_launch_rasterize_bwd(b, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
+  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+}
+extern "C" wm_status wm_rasterize_means2d(const void* workspace, size_t workspace_bytes, int n_gaussians, int n_cameras, int width, int height,
+                                          size_t max_isects, const int* radii, float* means2d, void* stream) {
+  if (!workspace || !radii || !means2d) return WM_ERR_INVALID;
+  const hipError_t e = wm_launch_rasterize_means2d(workspace, workspace_bytes, n_gaussians, n_cameras, width, height, max_isects, radii, means2d,
+                                                   (hipStream_t)stream);
+  return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
+}
+extern "C" wm_status wm_densify_accumulate(const float* v_means2d, const int* radii, int n_gaussians, int n_cameras, int width, int height,
+                                           float* grad2d, float* count, float* radii_state, void* stream) {
+  if (!v_means2d || !radii || !grad2d || !count) return WM_ERR_INVALID;
+  const hipError_t e = wm_launch_densify_accumulate(v_means2d, radii, n_gaussians, n_cameras, width, height, grad2d, count, radii_state,
+                                                    (hipStream_t)stream);
+  return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
+}
+extern "C" size_t wm_densify_plan_workspace_bytes(size_t n_gaussians) { return wm_densify_plan_ws_bytes(n_gaussians); }
+extern "C" wm_status wm_densify_plan(const float* grad2d, const float* count, const float* radii_state, const float* scales,
+                                     const float* opacities, int n_gaussians, float grow_grad2d, float grow_scale3d, float grow_scale2d,
+                                     float prune_opa, float prune_scale3d, float prune_scale2d, int use_scale2d, int prune_big,
+                                     int revised_opacity, int* src, int* kind, int* rank, int* counts, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  if (!grad2d || !count || !scales || !opacities || !src || !kind || !rank || !counts || !workspace) return WM_ERR_INVALID;
+  WmDensifyPlanArgs a;
+  memset(&a, 0, sizeof(a));
+  a.grad2d = grad2d; a.count = count; a.radii_state = radii_state; a.scales = scales; a.opacities = opacities; a.N = n_gaussians;
+  a.grow_grad2d = grow_grad2d; a.grow_scale3d = grow_scale3d; a.grow_scale2d = grow_scale2d;
+  a.prune_opa = prune_opa; a.prune_scale3d = prune_scale3d; a.prune_scale2d = prune_scale2d;
+  a.use_scale2d = use_scale2d ? 1 : 0; a.prune_big = prune_big ? 1 : 0; a.revised_opacity = revised_opacity ? 1 : 0;
+  a.src = src; a.kind = kind; a.rank = rank; a.counts = counts; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  const hipError_t e = wm_launch_densify_plan(a, (hipStream_t)stream);
+  return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
+}
+extern "C" wm_status wm_densify_gather(const float* in, float* out, int n_gaussians, int row, int mode, const int* src, const int* kind,
+                                       const int* rank, int n_out, const float* quats, const float* scales, const float* noise, void* stream) {
+  if (n_out > 0 && (!src || !kind || !rank || !in || !out)) return WM_ERR_INVALID;   // an empty result has no rows to point at
+  const hipError_t e = wm_launch_densify_gather(in, out, n_gaussians, row, mode, src, kind, rank, n_out, quats, scales, noise, (hipStream_t)stream);
+  return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
+}
 extern "C" size_t wm_photometric_loss_workspace_bytes(int B, int C, int H, int W) { return wm_photoloss_workspace_bytes(B, C, H, W); }
 extern "C" size_t wm_photometric_loss_forward_workspace_bytes(int B, int C, int H, int W) {
   return C > 0 ? wm_photoloss_forward_only_bytes(B, H, W) : 0;

@@ -6,12 +6,17 @@ argument order and return triples, so ``model.gs_renderer.rasterizer.rasterize_b
 
 Differentiable: when autograd is recording and any of means / quats / scales / opacities / colors requires grad, the call goes
 through ``wm_rasterize_splats_backward`` on ``.backward()`` (what gsplat's CUDA extension gives the reference's post-3DGS
-optimisation).  Cameras (``camtoworlds``, ``Ks``) get no gradient (``None``); no absgrad, no packed / sparse gradients."""
+optimisation).  Cameras (``camtoworlds``, ``Ks``) get no gradient (``None``); no packed / sparse gradients.
+
+``rasterize_splats(..., return_info=True)`` also returns what gsplat.rasterization's ``info`` gives a densification strategy
+(strategy.DefaultStrategy): the projected ``means2d`` as part of the graph, so that ``retain_grad()`` works and ``.grad`` (and,
+with absgrad, the plain attribute ``.absgrad``) is there after ``loss.backward()``, and the per-(camera, Gaussian) ``radii``.
+``means2d`` receives gradient from the rendered images only; unlike gsplat's, it does not pass gradient on to the splats, so a loss
+computed from ``means2d`` itself raises ``NotImplementedError`` in ``backward()`` rather than being dropped."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
-
+import weakref
 import torch
 
 from . import _lib
@@ -37,35 +42,109 @@ class _RasterizeSplats(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
-        L = _lib.lib()
-        means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n = ctx.state
         (depth,) = ctx.saved_tensors
-        is_sh, width, height = ctx.geom
-        dev = means.device
-        N, V = int(means.shape[0]), int(viewmats.shape[0])
-        cot = [torch.zeros((V, height, width, ch), device=dev) if v is None else _f32(v) for v, ch in zip((v_rgb, v_depth, v_alpha), (3, 1, 1))]
-        g_means, g_quats, g_scales = torch.empty_like(means), torch.empty_like(quats), torch.empty_like(scales)
-        g_opac, g_col = torch.empty_like(opacities), torch.empty_like(cin)
+        grads, _, _ = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False)
+        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[6:11]))   # cameras: no gradient
+
+
+def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad):
+    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs (None unless asked for).
+    Without want_means2d this is wm_rasterize_splats_backward; the _ex entry gives the same five gradients bit for bit."""
+    L = _lib.lib()
+    means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n = state
+    is_sh, width, height = geom
+    dev = means.device
+    N, V = int(means.shape[0]), int(viewmats.shape[0])
+    cot = [torch.zeros((V, height, width, ch), device=dev) if v is None else _f32(v) for v, ch in zip(cotangents, (3, 1, 1))]
+    g_means, g_quats, g_scales = torch.empty_like(means), torch.empty_like(quats), torch.empty_like(scales)
+    g_opac, g_col = torch.empty_like(opacities), torch.empty_like(cin)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    v2d = v2d_abs = None
+    if not want_means2d:
         gws = torch.empty(L.wm_rasterize_backward_workspace_bytes(N, V, width, height, n), device=dev, dtype=torch.uint8)
-        p = lambda t: C.c_void_p(t.data_ptr())
         st = L.wm_rasterize_splats_backward(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
                                             p(ws), ws.numel(), cap, n, None, p(depth), None, p(cot[0]), p(cot[1]), p(cot[2]),
-                                            p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col), p(gws), gws.numel(),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if st != 0:
-            raise RuntimeError(f"wm_rasterize_splats_backward failed with status {st}")
-        grads = [g_means, g_quats, g_scales, g_opac, g_col]
-        out = []
-        for i, (g, (shape, dtype)) in enumerate(zip(grads, ctx.meta)):
-            if not ctx.needs_input_grad[6 + i]:
-                out.append(None)
-                continue
-            if i == 4 and is_sh:     # SH coefficients [N, K, 3]: only degree 0 is rendered
-                full = torch.zeros(shape, device=dev, dtype=torch.float32)
-                full[:, 0, :] = g
-                g = full
-            out.append(g.reshape(shape).to(dtype))
-        return (None, None, None, None, None, None, *out)   # cameras: no gradient
+                                            p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col), p(gws), gws.numel(), stream)
+    else:
+        v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
+        v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
+        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_ex(N, V, width, height, n, int(want_absgrad)), device=dev, dtype=torch.uint8)
+        st = L.wm_rasterize_splats_backward_ex(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
+                                               p(ws), ws.numel(), cap, n, None, p(depth), None, p(cot[0]), p(cot[1]), p(cot[2]),
+                                               p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col), p(v2d), p(v2d_abs), int(want_absgrad),
+                                               p(gws), gws.numel(), stream)
+    if st != 0:
+        raise RuntimeError(f"wm_rasterize_splats_backward failed with status {st}")
+    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs
+
+
+def _shape_grads(grads, meta, is_sh, needed):
+    out = []
+    for i, (g, (shape, dtype)) in enumerate(zip(grads, meta)):
+        if not needed[i]:
+            out.append(None)
+            continue
+        if i == 4 and is_sh:     # SH coefficients [N, K, 3]: only degree 0 is rendered
+            full = torch.zeros(shape, device=g.device, dtype=torch.float32)
+            full[:, 0, :] = g
+            g = full
+        out.append(g.reshape(shape).to(dtype))
+    return out
+
+
+class _ProjectMeans2d(torch.autograd.Function):
+    """First half of the return_info route: runs the forward, keeps what it made in `shared` and returns the projected means
+    [C,N,2] as a graph tensor (gsplat: the means2d output of _FullyFusedProjection).  Its own backward passes nothing on: the
+    parameter gradients all come from the one fused backward of _CompositeWithInfo, so nothing is counted twice."""
+
+    @staticmethod
+    def forward(ctx, rz, shared, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors):
+        cin = colors[:, 0, :] if is_sh else colors
+        radii = torch.empty((int(camtoworlds.shape[0]), int(means.shape[0]), 2), device=means.device, dtype=torch.int32)
+        rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=True,
+                                               radii=radii)
+        shared.update(out=(rgb, depth, alpha), state=state, radii=radii)
+        ctx.shared = shared
+        m2 = rz._means2d(state, radii, width, height)
+        return m2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v_means2d):
+        # what arrives here must be exactly what _CompositeWithInfo.backward handed to means2d.  Anything else is a loss that used
+        # means2d itself: gsplat would carry that on to the parameters, this route does not, so it refuses instead of dropping it.
+        sent = ctx.shared.get("v_means2d")
+        if sent is None or not (v_means2d.data_ptr() == sent.data_ptr() or torch.equal(v_means2d, sent)):
+            raise NotImplementedError("info['means2d'] carries gradient only from the rendered images to itself (.grad / .absgrad for a "
+                                      "densification strategy): a loss computed from means2d directly is not propagated to the splats")
+        return (None,) * 12
+
+
+class _CompositeWithInfo(torch.autograd.Function):
+    """Second half: hands out the images of the forward _ProjectMeans2d ran, with means2d as an input.  Its backward is the one
+    fused backward call: the five parameter gradients, and v_means2d as the gradient of the means2d input (-> means2d.grad
+    under retain_grad()); with absgrad, means2d.absgrad is set as a plain attribute, as gsplat's _RasterizeToPixels.backward does."""
+
+    @staticmethod
+    def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors):
+        rgb, depth, alpha = shared.pop("out")
+        ctx.state, ctx.geom, ctx.want_absgrad = shared.pop("state"), geom, want_absgrad
+        ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
+        ctx.means2d_ref, ctx.shared = shared["means2d_ref"], shared
+        ctx.save_for_backward(depth)
+        return rgb, depth, alpha
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v_rgb, v_depth, v_alpha):
+        (depth,) = ctx.saved_tensors
+        grads, v2d, v2d_abs = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad)
+        m2 = ctx.means2d_ref()
+        if ctx.want_absgrad and m2 is not None:
+            m2.absgrad = v2d_abs
+        ctx.shared["v_means2d"] = v2d
+        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[4:9]))
 
 
 class Rasterizer:
@@ -81,7 +160,10 @@ class Rasterizer:
 
     # rasterization.py:29-66
     def rasterize_splats(self, means, quats, scales, opacities, colors, camtoworlds, Ks, width: int, height: int,
-                         sh_degree=None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                         sh_degree=None, return_info: bool = False, absgrad: bool | None = None, **kwargs):
+        """-> (rgb, depth, alpha), or with return_info=True (rgb, depth, alpha, info): info["means2d"] [C,N,2] fp32 (zero where
+        culled, part of the graph), info["radii"] [C,N,2] int32, "width", "height", "n_cameras", "gaussian_ids" = None (the layout
+        is always the unpacked [C,N,...] one).  absgrad (None: self.abs_grad) is read on the return_info route only."""
         if kwargs:
             raise TypeError(f"unsupported gsplat.rasterization arguments: {sorted(kwargs)}")
         if means.device.type != "cuda":
@@ -95,14 +177,46 @@ class Rasterizer:
                 raise ValueError("colors [N, 3] go with sh_degree = None")
             cin, is_sh = colors, 0
         splat_in = (means, quats, scales, opacities, colors)
+        if return_info:
+            return self._with_info(splat_in, cin, is_sh, camtoworlds, Ks, int(width), int(height), self.abs_grad if absgrad is None else absgrad)
+        if absgrad:
+            raise ValueError("absgrad is reported through info: pass return_info=True")
         if torch.is_grad_enabled() and any(t.requires_grad for t in splat_in):
             return _RasterizeSplats.apply(self, is_sh, int(width), int(height), camtoworlds, Ks, *splat_in)
         rgb, depth, alpha, _ = self._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False)
         return rgb, depth, alpha
 
-    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace):
+    def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad):
+        V, N = int(camtoworlds.shape[0]), int(splat_in[0].shape[0])
+        if torch.is_grad_enabled() and any(t.requires_grad for t in splat_in):
+            shared = {}
+            m2 = _ProjectMeans2d.apply(self, shared, is_sh, width, height, camtoworlds, Ks, *splat_in)
+            shared["means2d_ref"] = weakref.ref(m2)
+            radii = shared.pop("radii")
+            rgb, depth, alpha = _CompositeWithInfo.apply(shared, (is_sh, width, height), bool(want_absgrad), m2, *splat_in)
+        else:
+            radii = torch.empty((V, N, 2), device=splat_in[0].device, dtype=torch.int32)
+            rgb, depth, alpha, state = self._forward(*splat_in[:4], cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False, radii=radii)
+            m2 = self._means2d(state, radii, width, height)
+        info = {"means2d": m2, "radii": radii, "width": width, "height": height, "n_cameras": V, "gaussian_ids": None}
+        return rgb, depth, alpha, info
+
+    @staticmethod
+    def _means2d(state, radii, width, height):
+        """the pixel-space means of the forward that left `state`, [C,N,2], zero where culled"""
+        means, viewmats, ws, cap = state[0], state[5], state[7], state[8]
+        N, V = int(means.shape[0]), int(viewmats.shape[0])
+        m2 = torch.empty((V, N, 2), device=means.device, dtype=torch.float32)
+        st = _lib.lib().wm_rasterize_means2d(C.c_void_p(ws.data_ptr()), ws.numel(), N, V, width, height, cap, C.c_void_p(radii.data_ptr()),
+                                             C.c_void_p(m2.data_ptr()), C.c_void_p(torch.cuda.current_stream(means.device).cuda_stream))
+        if st != 0:
+            raise RuntimeError(f"wm_rasterize_means2d failed with status {st}")
+        return m2
+
+    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, radii=None):
         """One wm_rasterize_splats call.  own_workspace: a workspace of this call's own (kept by the autograd node until its
-        backward has run) instead of the rasteriser's reusable one.  -> rgb, depth, alpha, state for the backward."""
+        backward has run) instead of the rasteriser's reusable one.  radii: optional [C,N,2] int32 output.
+        -> rgb, depth, alpha, state for the backward."""
         L = _lib.lib()
         dev = means.device
         N, V = int(means.shape[0]), int(camtoworlds.shape[0])
@@ -125,7 +239,7 @@ class Rasterizer:
                 self._ws = ws
             self._cap = cap
             st = L.wm_rasterize_splats(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
-                                       p(rgb), p(depth), p(alpha), None, p(ws), ws.numel(), cap, C.byref(n), stream)
+                                       p(rgb), p(depth), p(alpha), None if radii is None else p(radii), p(ws), ws.numel(), cap, C.byref(n), stream)
             if st == 0:
                 break
             if st == 3 and n.value > cap:   # WM_ERR_STATE: more (Gaussian, tile) pairs than the workspace holds
@@ -139,6 +253,8 @@ class Rasterizer:
 
     # rasterization.py:68-93 (NB: the reference passes what it calls `viewmats` on as `camtoworlds`)
     def rasterize_batches(self, means, quats, scales, opacities, colors, viewmats, Ks, width, height, **kwargs):
+        if kwargs.get("return_info") or kwargs.get("absgrad"):
+            raise TypeError("rasterize_batches returns the stacked (rgb, depth, alpha) only: call rasterize_splats(..., return_info=True) per batch element")
         rc, rd, ra = [], [], []
         for i in range(len(means)):
             c, d, a = self.rasterize_splats(means[i], quats[i], scales[i], opacities[i], colors[i], viewmats[i], Ks[i], width, height, **kwargs)

@@ -371,7 +371,7 @@ wm_status wm_rasterize_splats(const float* means, const float* quats, const floa
  * _QuatScaleToCovarPreci.backward), which the reference's "Post 3DGS Optimization" (README; gsplat's simple_trainer) runs on.
  * Gradients of out_rgb / out_depth / out_alpha of ONE wm_rasterize_splats call with respect to means [N,3], quats [N,4] (through
  * the normalisation), scales [N,3], opacities [N] and colors [N,3] (the degree-0 SH coefficients when colors_are_sh0: zero where
- * 0.2820948 sh + 0.5 <= 0).  No gradient for viewmats or Ks, no absgrad, no packed / sparse layout.
+ * 0.2820948 sh + 0.5 <= 0).  No gradient for viewmats or Ks, no packed / sparse layout; the 2-D mean gradient and absgrad: the _ex entry below.
  * CONTRACT: pass the same inputs, sizes, workspace, workspace_bytes and max_isects as the forward call and the *n_isects it
  * reported; the workspace must be UNTOUCHED between that forward and this call (no other wm_rasterize_splats on it): the
  * backward reads the projection records, the sorted pair list and the tile offsets the forward left there.  out_depth is the
@@ -388,6 +388,65 @@ wm_status wm_rasterize_splats_backward(const float* means, const float* quats, c
                                        const float* out_alpha, const float* v_rgb, const float* v_depth, const float* v_alpha,
                                        float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
                                        void* grad_workspace, size_t grad_workspace_bytes, void* stream);
+
+/* The same backward with what a densification strategy reads (gsplat: info["means2d"].grad / .absgrad, strategy/default.py:220-226).
+ * Arguments and the five gradients as wm_rasterize_splats_backward, bit for bit; in addition
+ *   v_means2d     [C,N,2] optional: gradient of the pixel-space means, per (camera, Gaussian) the sum over its tiles of the tiles'
+ *                 sums; zero where the camera culled the Gaussian.
+ *   v_means2d_abs [C,N,2], required with want_absgrad = 1 (then v_means2d is required too): over all pixels that blended the pair,
+ *                 the sum of the ABSOLUTE value of the pixel's two 2-D mean terms, taken per pixel before any sum (gsplat's
+ *                 absgrad, RasterizeToPixels3DGSBwd.cu); zero where culled.  Not written with want_absgrad = 0.
+ * grad_workspace: wm_rasterize_backward_workspace_bytes_ex bytes: 40 bytes per (Gaussian, tile) pair, 48 with want_absgrad.
+ * Fixed summation order, no atomics, bitwise reproducible; v_means2d is the same bits with and without want_absgrad. */
+size_t wm_rasterize_backward_workspace_bytes_ex(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad);
+wm_status wm_rasterize_splats_backward_ex(const float* means, const float* quats, const float* scales, const float* opacities,
+                                          const float* colors, int colors_are_sh0, int n_gaussians, const float* viewmats, const float* Ks,
+                                          int n_cameras, int width, int height, const void* workspace, size_t workspace_bytes,
+                                          size_t max_isects, size_t n_isects, const float* out_rgb, const float* out_depth,
+                                          const float* out_alpha, const float* v_rgb, const float* v_depth, const float* v_alpha,
+                                          float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
+                                          float* v_means2d, float* v_means2d_abs, int want_absgrad,
+                                          void* grad_workspace, size_t grad_workspace_bytes, void* stream);
+/* The pixel-space means [C,N,2] of ONE wm_rasterize_splats call, read out of the workspace it left (same sizes and max_isects,
+ * workspace untouched since); radii: that call's radii_out.  Zero where a radius is 0 (culled).  Asynchronous on stream. */
+wm_status wm_rasterize_means2d(const void* workspace, size_t workspace_bytes, int n_gaussians, int n_cameras, int width, int height,
+                               size_t max_isects, const int* radii, float* means2d, void* stream);
+
+/* Splat densification: gsplat's DefaultStrategy (gsplat/strategy/default.py, ops.py), which the reference's post-3DGS trainer
+ * (simple_trainer_worldmirror.py:776, :961) runs around every optimisation step.  Device fp32 / int32 buffers, no atomics, fixed order.
+ * wm_densify_accumulate (every step; _update_state, default.py:220-260): for every Gaussian g, cameras c in order, where
+ *   radii [C,N,2] has both entries > 0:  grad2d[g] += hypot(v_means2d[c,g,0] * width / 2 * C, v_means2d[c,g,1] * height / 2 * C),
+ *   count[g] += 1, and, when radii_state is given, radii_state[g] = max(radii_state[g], max(rx, ry) / float(max(width, height)))
+ *   (a true maximum over the cameras: the scatter-max default.py:255 names as intended; its indexed assignment keeps the last camera).
+ *   v_means2d: the gradient or the absgrad of the backward above.  grad2d, count, radii_state [N] are updated in place.
+ *   Asynchronous on stream, no workspace.
+ * wm_densify_plan (at a refinement; _grow_gs + _prune_gs, default.py:263-339): with mean = grad2d / max(count, 1) and
+ *   smax = max exp(scales [N,3]):  duplicate = mean > grow_grad2d and smax <= grow_scale3d;  split = (mean > grow_grad2d and
+ *   smax > grow_scale3d) or (use_scale2d and radii_state > grow_scale2d).  grow_scale3d and prune_scale3d are passed already
+ *   multiplied by the scene scale; use_scale2d = step < refine_scale2d_stop_iter (then radii_state is required);
+ *   prune_big = step > reset_every.  Every entry that duplicate -> split would produce is then tested on ITS OWN values:
+ *   pruned when sigmoid(opacity) < prune_opa, or, with prune_big, when its smax > prune_scale3d or (use_scale2d and its parent's
+ *   radii_state > prune_scale2d); a split child has smax / 1.6 and, with revised_opacity, opacity 1 - sqrt(1 - sigmoid(o)).
+ *   The survivors are laid out as ops.py:93-210 leaves them: un-split originals, duplicates, first split children, second split
+ *   children, each in index order.  Per output row: src (source index), kind (0 keep, 1 duplicate, 2 / 3 first / second split
+ *   child) and rank (for split rows: the parent's rank among ALL split Gaussians, pruned or not = its row of the noise); the three
+ *   arrays have room for 3 N rows.  counts (HOST, 4 ints): n_dupli, n_split, n_prune, n_out, read back after ONE stream
+ *   synchronisation (gsplat's .item()).  workspace: wm_densify_plan_workspace_bytes bytes.
+ * wm_densify_gather: out [n_out,row] from in [N,row] by the plan.  mode 0 copy: every row = its source row (any parameter).
+ *   1 zero_new: kind 0 rows copied, all others zero (Adam exp_avg / exp_avg_sq).  2 means (row 3): split children =
+ *   mean + R(q / max(|q|, 1e-12)) (exp(s) * noise[b, rank]), b = 0 / 1 for kind 2 / 3, noise [2,N,3] standard normal draws
+ *   supplied by the caller (rows [0, n_split) of each half are read), quats [N,4] wxyz, scales [N,3] log.  3 scales (row 3):
+ *   split children = log(exp(s) / 1.6).  4 opacities_revised (row 1): split children = logit(1 - sqrt(1 - sigmoid(o))).
+ *   quats / scales / noise are read in mode 2 only.  Asynchronous on stream, no workspace. */
+wm_status wm_densify_accumulate(const float* v_means2d, const int* radii, int n_gaussians, int n_cameras, int width, int height,
+                                float* grad2d, float* count, float* radii_state, void* stream);
+size_t wm_densify_plan_workspace_bytes(size_t n_gaussians);
+wm_status wm_densify_plan(const float* grad2d, const float* count, const float* radii_state, const float* scales, const float* opacities,
+                          int n_gaussians, float grow_grad2d, float grow_scale3d, float grow_scale2d, float prune_opa, float prune_scale3d,
+                          float prune_scale2d, int use_scale2d, int prune_big, int revised_opacity, int* src, int* kind, int* rank,
+                          int* counts, void* workspace, size_t workspace_bytes, void* stream);
+wm_status wm_densify_gather(const float* in, float* out, int n_gaussians, int row, int mode, const int* src, const int* kind,
+                            const int* rank, int n_out, const float* quats, const float* scales, const float* noise, void* stream);
 
 /* Fused L1 + SSIM photometric loss and its backward: the loss of the reference's "Post 3DGS Optimization" (README; gsplat's
  * simple_trainer_worldmirror.py:785-792: F.l1_loss(colors, pixels) and 1 - fused_ssim(colors, pixels, padding="valid"), mixed with
