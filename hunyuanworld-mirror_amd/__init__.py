@@ -7,3 +7,4 @@ from .ingest import load_and_preprocess_images, preprocess_rgb  # noqa: F401
 from .rasterization import Rasterizer  # noqa: F401
 from .losses import fused_ssim, photometric_loss  # noqa: F401
 from .strategy import DefaultStrategy  # noqa: F401
+from .strategy_mcmc import MCMCStrategy  # noqa: F401

@@ -59,6 +59,7 @@ EXPORTS = [
     "wm_photometric_loss_workspace_bytes", "wm_photometric_loss_forward_workspace_bytes", "wm_photometric_loss", "wm_photometric_loss_backward",
     "wm_rasterize_backward_workspace_bytes_ex", "wm_rasterize_splats_backward_ex", "wm_rasterize_means2d",
     "wm_densify_accumulate", "wm_densify_plan_workspace_bytes", "wm_densify_plan", "wm_densify_gather",
+    "wm_mcmc_inject_noise", "wm_mcmc_partition_workspace_bytes", "wm_mcmc_partition", "wm_mcmc_relocation", "wm_mcmc_scatter", "wm_mcmc_zero_rows",
 ]
 
 _lib = None
@@ -174,6 +175,18 @@ def lib() -> C.CDLL:
     L.wm_densify_plan.restype = i32
     L.wm_densify_gather.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     L.wm_densify_gather.restype = i32
+    L.wm_mcmc_inject_noise.argtypes = [vp, vp, vp, vp, vp, f32, i32, vp]
+    L.wm_mcmc_inject_noise.restype = i32
+    L.wm_mcmc_partition_workspace_bytes.argtypes = [C.c_size_t]
+    L.wm_mcmc_partition_workspace_bytes.restype = C.c_size_t
+    L.wm_mcmc_partition.argtypes = [vp, vp, i32, f32, vp, vp, C.POINTER(i32 * 2), vp, C.c_size_t, vp]
+    L.wm_mcmc_partition.restype = i32
+    L.wm_mcmc_relocation.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]
+    L.wm_mcmc_relocation.restype = i32
+    L.wm_mcmc_scatter.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
+    L.wm_mcmc_scatter.restype = i32
+    L.wm_mcmc_zero_rows.argtypes = [vp, i32, i32, vp, i32, vp]
+    L.wm_mcmc_zero_rows.restype = i32
     i64p = C.POINTER(C.c_int64)
     L.wm_photometric_loss_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.wm_photometric_loss_workspace_bytes.restype = C.c_size_t

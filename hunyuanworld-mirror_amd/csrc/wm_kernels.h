@@ -302,6 +302,19 @@ hipError_t wm_launch_densify_plan(const WmDensifyPlanArgs& a, hipStream_t s);
 hipError_t wm_launch_densify_gather(const float* in, float* out, int N, int R, int mode, const int* src, const int* kind, const int* rank,
                                     int n_out, const float* quats, const float* scales, const float* noise, hipStream_t s);
 
+// ------------------------------------------------------------------ MCMC relocation, growth, position noise (mcmc.hip): gsplat MCMCStrategy
+hipError_t wm_launch_mcmc_inject_noise(float* means, const float* quats, const float* scales, const float* opacities, const float* noise,
+                                       float scaler, int N, hipStream_t s);
+size_t wm_mcmc_partition_ws_bytes(size_t N);
+// mask (one byte per Gaussian, non-zero = dead) replaces the opacity test when it is given; counts_host: n_dead, n_alive
+hipError_t wm_launch_mcmc_partition(const float* opacities, const unsigned char* mask, int N, float min_opacity, int* dead_idx, int* alive_idx,
+                                    int* counts_host, void* workspace, size_t workspace_bytes, hipStream_t s);
+hipError_t wm_launch_mcmc_relocation(const float* opacities, const float* scales, const int* sampled, int n_sampled, int N, float min_opacity,
+                                     float* new_opacities, float* new_scales, int* hist, hipStream_t s);
+hipError_t wm_launch_mcmc_scatter(float* t, int rows, int R, const int* sampled, const int* dest, const float* values, int n_sampled,
+                                  hipStream_t s);
+hipError_t wm_launch_mcmc_zero_rows(float* t, int rows, int R, const int* idx, int n, hipStream_t s);
+
 // ------------------------------------------------------------------ L1 + SSIM photometric loss (photoloss.hip)
 // images [B,C,H,W] by element strides (sB, sC, sH, sW): NCHW and the permuted view of a channels-last tensor are read in place
 struct WmPhotoLossArgs {

@@ -2097,6 +2097,34 @@ extern "C" wm_status wm_densify_gather(const float* in, float* out, int n_gaussi
   const hipError_t e = wm_launch_densify_gather(in, out, n_gaussians, row, mode, src, kind, rank, n_out, quats, scales, noise, (hipStream_t)stream);
   return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
 }
+static wm_status mcmc_status(hipError_t e) { return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP; }
+extern "C" wm_status wm_mcmc_inject_noise(float* means, const float* quats, const float* scales, const float* opacities, const float* noise,
+                                          float scaler, int n_gaussians, void* stream) {
+  if (n_gaussians > 0 && (!means || !quats || !scales || !opacities || !noise)) return WM_ERR_INVALID;
+  return mcmc_status(wm_launch_mcmc_inject_noise(means, quats, scales, opacities, noise, scaler, n_gaussians, (hipStream_t)stream));
+}
+extern "C" size_t wm_mcmc_partition_workspace_bytes(size_t n_gaussians) { return wm_mcmc_partition_ws_bytes(n_gaussians); }
+extern "C" wm_status wm_mcmc_partition(const float* opacities, const unsigned char* mask, int n_gaussians, float min_opacity, int* dead_idx,
+                                       int* alive_idx, int* counts, void* workspace, size_t workspace_bytes, void* stream) {
+  if ((!opacities && !mask) || !dead_idx || !alive_idx || !counts || !workspace) return WM_ERR_INVALID;
+  return mcmc_status(wm_launch_mcmc_partition(opacities, mask, n_gaussians, min_opacity, dead_idx, alive_idx, counts, workspace, workspace_bytes,
+                                              (hipStream_t)stream));
+}
+extern "C" wm_status wm_mcmc_relocation(const float* opacities, const float* scales, const int* sampled, int n_sampled, int n_gaussians,
+                                        float min_opacity, float* new_opacities, float* new_scales, int* hist, void* stream) {
+  if (n_sampled > 0 && (!opacities || !scales || !sampled || !new_opacities || !new_scales || !hist)) return WM_ERR_INVALID;
+  return mcmc_status(wm_launch_mcmc_relocation(opacities, scales, sampled, n_sampled, n_gaussians, min_opacity, new_opacities, new_scales, hist,
+                                               (hipStream_t)stream));
+}
+extern "C" wm_status wm_mcmc_scatter(float* t, int rows, int row, const int* sampled, const int* dest, const float* values, int n_sampled,
+                                     void* stream) {
+  if (n_sampled > 0 && (!t || !sampled || !dest)) return WM_ERR_INVALID;
+  return mcmc_status(wm_launch_mcmc_scatter(t, rows, row, sampled, dest, values, n_sampled, (hipStream_t)stream));
+}
+extern "C" wm_status wm_mcmc_zero_rows(float* t, int rows, int row, const int* idx, int n, void* stream) {
+  if (n > 0 && (!t || !idx)) return WM_ERR_INVALID;
+  return mcmc_status(wm_launch_mcmc_zero_rows(t, rows, row, idx, n, (hipStream_t)stream));
+}
 extern "C" size_t wm_photometric_loss_workspace_bytes(int B, int C, int H, int W) { return wm_photoloss_workspace_bytes(B, C, H, W); }
 extern "C" size_t wm_photometric_loss_forward_workspace_bytes(int B, int C, int H, int W) {
   return C > 0 ? wm_photoloss_forward_only_bytes(B, H, W) : 0;

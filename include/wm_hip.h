@@ -448,6 +448,39 @@ wm_status wm_densify_plan(const float* grad2d, const float* count, const float* 
 wm_status wm_densify_gather(const float* in, float* out, int n_gaussians, int row, int mode, const int* src, const int* kind,
                             const int* rank, int n_out, const float* quats, const float* scales, const float* noise, void* stream);
 
+/* MCMC relocation, growth and position noise: gsplat's MCMCStrategy (gsplat/strategy/mcmc.py, ops.py:240-369; arXiv:2404.09591), the
+ * other strategy of the reference's post-3DGS trainer.  Device fp32 / int32 buffers, log scales [N,3], logit opacities [N], quats [N,4]
+ * wxyz; no float atomics, results independent of the launch order; asynchronous on stream except wm_mcmc_partition.
+ * wm_mcmc_inject_noise (every step; inject_noise_to_position, ops.py:343-369): in place, for every Gaussian g
+ *   means[g] += Sigma_g (noise[g] * gate_g * scaler),  Sigma = R diag(exp(s))^2 R^T,  R the rotation of q / max(|q|, 1e-12),
+ *   gate = 1 / (1 + exp(-100 ((1 - sigmoid(o)) - 0.995))).  noise [N,3]: standard normal draws supplied by the caller.  No workspace.
+ * wm_mcmc_partition (at a refinement; mcmc.py:154-155, ops.py:258-259): dead = sigmoid(o) <= min_opacity, or, when mask (one byte
+ *   per Gaussian) is given, dead = mask != 0 and opacities is not read.  dead_idx and alive_idx (room for N ints each) receive the
+ *   indices of the dead and of the other Gaussians, each in ascending order (as nonzero gives them).  counts (HOST, 2 ints):
+ *   n_dead, n_alive, read back after ONE stream synchronisation (gsplat's .item()).  workspace: wm_mcmc_partition_workspace_bytes.
+ * wm_mcmc_relocation (compute_relocation, relocation.py / RelocationCUDA.cu:26-43, with the ratios and the clamp of ops.py:272-278):
+ *   for every j < n_sampled, g = sampled[j]:  ratio = clamp(number of entries of sampled equal to g, +1, 1, 51);  o = sigmoid(opacities[g]);
+ *   x = 1 - (1 - o)^(1 / ratio);  denom = sum_{i=1..ratio} sum_{k=0..i-1} C(i-1, k) (-1)^k / sqrt(k+1) x^(k+1)  (paper eq. 9; evaluated
+ *   in fp64 in its collapsed form sum_{k=0..ratio-1} C(ratio, k+1) (-1)^k / sqrt(k+1) x^(k+1), no table);
+ *   new_scales[j] = log((o / denom) exp(scales[g]))  [n_sampled,3];  new_opacities[j] = logit(clamp(x, min_opacity, 1 - FLT_EPSILON))
+ *   [n_sampled], clamped after the scale is computed.  hist: n_gaussians ints of scratch (zeroed here; integer atomics).
+ * wm_mcmc_scatter (param_fn of relocate, ops.py:280-286, and of sample_add, ops.py:322-328): t [rows,row] in place; for every j
+ *   v = values ? values[j] : t[sampled[j]];  t[sampled[j]] = v;  t[dest[j]] = v   (values [n_sampled,row] or null).
+ *   dest holds distinct rows, none of which is in sampled.  sampled may repeat: every writer of a repeated row writes the same value
+ *   (values of equal sources are equal by construction).  relocate: dest = the dead indices; sample_add: dest = N + j in a buffer of
+ *   N + n rows whose first N rows the caller copied.  An index outside [0, rows) is skipped.
+ * wm_mcmc_zero_rows (optimizer_fn of relocate, ops.py:288-290): t[idx[j]] = 0 for every j < n, t [rows,row]; idx may repeat. */
+wm_status wm_mcmc_inject_noise(float* means, const float* quats, const float* scales, const float* opacities, const float* noise,
+                               float scaler, int n_gaussians, void* stream);
+size_t wm_mcmc_partition_workspace_bytes(size_t n_gaussians);
+wm_status wm_mcmc_partition(const float* opacities, const unsigned char* mask, int n_gaussians, float min_opacity, int* dead_idx,
+                            int* alive_idx, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+wm_status wm_mcmc_relocation(const float* opacities, const float* scales, const int* sampled, int n_sampled, int n_gaussians,
+                             float min_opacity, float* new_opacities, float* new_scales, int* hist, void* stream);
+wm_status wm_mcmc_scatter(float* t, int rows, int row, const int* sampled, const int* dest, const float* values, int n_sampled,
+                          void* stream);
+wm_status wm_mcmc_zero_rows(float* t, int rows, int row, const int* idx, int n, void* stream);
+
 /* Fused L1 + SSIM photometric loss and its backward: the loss of the reference's "Post 3DGS Optimization" (README; gsplat's
  * simple_trainer_worldmirror.py:785-792: F.l1_loss(colors, pixels) and 1 - fused_ssim(colors, pixels, padding="valid"), mixed with
  * ssim_lambda = 0.2 by the caller).  fused_ssim is a CUDA-only extension; this is the published definition it implements:
