@@ -8,3 +8,4 @@ from .rasterization import Rasterizer  # noqa: F401
 from .losses import fused_ssim, photometric_loss  # noqa: F401
 from .strategy import DefaultStrategy  # noqa: F401
 from .strategy_mcmc import MCMCStrategy  # noqa: F401
+from .pose import CameraOptModule  # noqa: F401

@@ -1,7 +1,8 @@
 // 3D-Gaussian-splat rasteriser backward — the gradient gsplat.rasterization gives the reference's "Post 3DGS Optimization"
 // through its CUDA extension (gsplat/cuda/csrc/RasterizeToPixels3DGSBwd.cu for the compositing, the torch restatement
 // gsplat/cuda/_torch_impl.py:11-133,250-375 for the projection), for the configuration raster.hip renders: classic, pinhole,
-// RGB + expected depth, degree-0 SH or given colours.  Gradients for means, quats, scales, opacities, colours; none for cameras.
+// RGB + expected depth, degree-0 SH or given colours.  Gradients for means, quats, scales, opacities, colours and, on request, the
+// world-to-camera matrices (gsplat: the viewmats gradient of _FullyFusedProjection.backward); none for the intrinsics.
 //
 // It reads what the forward left in the caller's workspace (records, sorted list, tile offsets, per-Gaussian pair offsets):
 //   locate     which of the sort's two value buffers holds the sorted list (the one whose keys are in order)
@@ -18,6 +19,9 @@
 //              conic -> 2-D covariance -> perspective projection -> camera -> world, then once through covariance -> quaternion, scale.
 //              On request it also writes the summed 2-D mean terms per (camera, Gaussian) before it folds them in: the gradient of
 //              the pixel-space means (and the absgrad sums) that a densification strategy reads.
+//              With CAM it folds the same per-(camera, Gaussian) terms the other way as well: the 12 viewmats terms of a pair
+//              (v_R 9, v_t 3) are summed over the wave's 64 lanes in fp64 and stored by one lane as the wave's partial.
+//   camreduce  with CAM: per (camera, component) the waves' partials are added in a fixed order, in fp64 -> v_viewmats [C,4,4]
 //   means2d    the pixel-space means the forward's projection left in its records, [C,N,2], zero where culled
 // Sums run in a fixed order everywhere, so gradients are bitwise reproducible run to run.
 #include "wm_common.h"
@@ -37,9 +41,30 @@ __global__ __launch_bounds__(256) void raster_locate_sorted_kernel(const unsigne
   if (i + 1 < n && keys0[i] > keys0[i + 1]) *flag = 1u;
 }
 
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_of_f64(double x) {   // as dpp_of, on both halves
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROW_MASK, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROW_MASK, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+// sum over the 64 lanes in the order of wave_sum_hi; the total is valid in lanes 48-63
+__device__ __forceinline__ double wave_sum_hi_f64(double v) {
+  v += dpp_of_f64<0xB1, 0xf>(v);
+  v += dpp_of_f64<0x4E, 0xf>(v);
+  v += dpp_of_f64<0x141, 0xf>(v);
+  v += dpp_of_f64<0x140, 0xf>(v);
+  v += dpp_of_f64<0x142, 0xa>(v);
+  v += dpp_of_f64<0x143, 0xc>(v);
+  return v;
+}
+
 // _torch_impl.py:11-29,45-61 (quaternion, scale -> covariance), :250-283 (world -> camera), :78-133 (perspective), :329-355 (conic)
 // M2D: also write v_means2d [C,N,2] (and, with 12-float records, v_means2d_abs): the summed pair terms, zero where culled
-template <int REC, bool M2D>
+// CAM: also write cam_part [C][12][waves] (fp64): per wave the sum over its Gaussians of the pair's viewmats terms, component 4 i + j =
+//      v_R[i][j] (j < 3) or v_t[i] (j = 3).  v_t += (v_tx, v_ty, v_tz) (from mc = Rv m + t); v_R += outer(v_t, m) + (vS + vS^T) Rv cov
+//      (from S = Rv cov Rv^T, cov symmetric).  Lanes past N and culled pairs take part in the wave's sum with zeros; a wave with no
+//      Gaussian at all leaves, and the reducer does not read its slot.
+template <int REC, bool M2D, bool CAM>
 __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __restrict__ means, const float* __restrict__ quats,
                                                                  const float* __restrict__ scales, const float* __restrict__ colors_in, int is_sh,
                                                                  const float* __restrict__ viewmats, const float* __restrict__ Ks, int N, int C,
@@ -47,9 +72,17 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
                                                                  const unsigned long long* __restrict__ pair_offs, const float* __restrict__ pair_grad,
                                                                  float* __restrict__ v_means, float* __restrict__ v_quats, float* __restrict__ v_scales,
                                                                  float* __restrict__ v_opac, float* __restrict__ v_colors,
-                                                                 float* __restrict__ v_means2d, float* __restrict__ v_means2d_abs) {
-  const int g = blockIdx.x * 256 + threadIdx.x;
-  if (g >= N) return;
+                                                                 float* __restrict__ v_means2d, float* __restrict__ v_means2d_abs,
+                                                                 double* __restrict__ cam_part) {
+  int g = blockIdx.x * 256 + threadIdx.x;
+  bool live = true;
+  if constexpr (CAM) {
+    if ((g & ~63) >= N) return;   // the whole wave is past N
+    live = g < N;
+    g = live ? g : N - 1;         // a lane past N reads the last Gaussian, adds zeros to the wave's sums and stores nothing
+  } else {
+    if (g >= N) return;
+  }
   const float q0 = quats[4 * g], q1 = quats[4 * g + 1], q2 = quats[4 * g + 2], q3 = quats[4 * g + 3];
   const float qn = fmaxf(sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3), 1e-12f);
   const float qw = q0 / qn, qx = q1 / qn, qy = q2 / qn, qz = q3 / qn;
@@ -72,104 +105,132 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
     const size_t idx = (size_t)c * N + g;
     const int rect = g2d[idx].rect;
     const int cnt = (((rect >> 16) & 255) - (rect & 255)) * (((rect >> 24) & 255) - ((rect >> 8) & 255));
+    float cv[CAM ? 12 : 1];
+    if constexpr (CAM) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) cv[i] = 0.f;
+    }
     if (cnt <= 0) {           // culled for this camera
       if constexpr (M2D) {
-        v_means2d[2 * idx] = 0.f; v_means2d[2 * idx + 1] = 0.f;
-        if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = 0.f; v_means2d_abs[2 * idx + 1] = 0.f; }
+        if (live) {
+          v_means2d[2 * idx] = 0.f; v_means2d[2 * idx + 1] = 0.f;
+          if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = 0.f; v_means2d_abs[2 * idx + 1] = 0.f; }
+        }
       }
-      continue;
+      if constexpr (!CAM) continue;
     }
-    float p[REC];
+    if (!CAM || (live && cnt > 0)) {
+      float p[REC];
 #pragma unroll
-    for (int i = 0; i < REC; ++i) p[i] = 0.f;
-    const float* rec = pair_grad + pair_offs[idx] * REC;
-    for (int t = 0; t < cnt; ++t)
+      for (int i = 0; i < REC; ++i) p[i] = 0.f;
+      const float* rec = pair_grad + pair_offs[idx] * REC;
+      for (int t = 0; t < cnt; ++t)
 #pragma unroll
-      for (int i = 0; i < REC; ++i) p[i] += rec[(size_t)t * REC + i];
-    if constexpr (M2D) {
-      v_means2d[2 * idx] = p[0]; v_means2d[2 * idx + 1] = p[1];
-      if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = p[10]; v_means2d_abs[2 * idx + 1] = p[11]; }
+        for (int i = 0; i < REC; ++i) p[i] += rec[(size_t)t * REC + i];
+      if constexpr (M2D) {
+        v_means2d[2 * idx] = p[0]; v_means2d[2 * idx + 1] = p[1];
+        if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = p[10]; v_means2d_abs[2 * idx + 1] = p[11]; }
+      }
+      const float v_mx = p[0], v_my = p[1], v_ca = p[2], v_cb = p[3], v_cc = p[4];
+      a_op += p[5]; a_col[0] += p[6]; a_col[1] += p[7]; a_col[2] += p[8];
+      // forward, as raster_project_kernel
+      const float* V = viewmats + 16 * c;
+      const float Rv[9] = {V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
+      const float tx = Rv[0] * m[0] + Rv[1] * m[1] + Rv[2] * m[2] + V[3];
+      const float ty = Rv[3] * m[0] + Rv[4] * m[1] + Rv[5] * m[2] + V[7];
+      const float tz = Rv[6] * m[0] + Rv[7] * m[1] + Rv[8] * m[2] + V[11];
+      float RC[9], S[9];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) RC[3 * i + k] = Rv[3 * i] * cov[k] + Rv[3 * i + 1] * cov[3 + k] + Rv[3 * i + 2] * cov[6 + k];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int l = 0; l < 3; ++l) S[3 * i + l] = RC[3 * i] * Rv[3 * l] + RC[3 * i + 1] * Rv[3 * l + 1] + RC[3 * i + 2] * Rv[3 * l + 2];
+      const float* K = Ks + 9 * c;
+      const float fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+      const float tfx = 0.5f * width / fx, tfy = 0.5f * height / fy;
+      const float lxp = (width - cx) / fx + 0.3f * tfx, lxn = cx / fx + 0.3f * tfx;
+      const float lyp = (height - cy) / fy + 0.3f * tfy, lyn = cy / fy + 0.3f * tfy;
+      const float rz = 1.0f / tz, rz2 = rz * rz;
+      const float ux = tx * rz, uy = ty * rz;
+      const bool free_x = ux >= -lxn && ux <= lxp, free_y = uy >= -lyn && uy <= lyp;   // torch.clamp: no gradient outside the limits
+      const float u = fminf(fmaxf(ux, -lxn), lxp), w = fminf(fmaxf(uy, -lyn), lyp);
+      const float J0 = fx * rz, J2 = -fx * u * rz, J4 = fy * rz, J5 = -fy * w * rz;   // J = [[J0 0 J2] [0 J4 J5]]
+      const float a0 = J0 * S[0] + J2 * S[6], a1 = J0 * S[1] + J2 * S[7], a2 = J0 * S[2] + J2 * S[8];   // A = J S (2 x 3)
+      const float b0 = J4 * S[3] + J5 * S[6], b1 = J4 * S[4] + J5 * S[7], b2 = J4 * S[5] + J5 * S[8];
+      const float c00 = a0 * J0 + a2 * J2 + 0.3f, c01 = a1 * J4 + a2 * J5, c10 = b0 * J0 + b2 * J2, c11 = b1 * J4 + b2 * J5 + 0.3f;
+      const float det_raw = c00 * c11 - c01 * c10;
+      const float det = fmaxf(det_raw, 1e-10f), rdet = 1.0f / det;
+      const float ka = c11 * rdet, kb = -(c01 + c10) * 0.5f * rdet, kc = c00 * rdet;
+      // conic -> 2-D covariance G = d loss / d cov2d
+      float g00 = v_cc * rdet, g11 = v_ca * rdet, g01 = -0.5f * v_cb * rdet, g10 = g01;
+      if (det_raw >= 1e-10f) {
+        const float v_det = -(v_ca * ka + v_cb * kb + v_cc * kc) * rdet;
+        g00 += v_det * c11; g11 += v_det * c00; g01 -= v_det * c10; g10 -= v_det * c01;
+      }
+      // cov2d = J S J^T:  v_S = J^T G J,  v_J = G J S^T + G^T J S
+      const float Jm[6] = {J0, 0.f, J2, 0.f, J4, J5};
+      float GJ[6], vS[9];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { GJ[j] = g00 * Jm[j] + g01 * Jm[3 + j]; GJ[3 + j] = g10 * Jm[j] + g11 * Jm[3 + j]; }
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) vS[3 * i + j] = Jm[i] * GJ[j] + Jm[3 + i] * GJ[3 + j];
+      float GtJ[6];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) { GtJ[j] = g00 * Jm[j] + g10 * Jm[3 + j]; GtJ[3 + j] = g01 * Jm[j] + g11 * Jm[3 + j]; }
+      float vJ[6];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          vJ[3 * i + j] = GJ[3 * i] * S[3 * j] + GJ[3 * i + 1] * S[3 * j + 1] + GJ[3 * i + 2] * S[3 * j + 2] +
+                          GtJ[3 * i] * S[j] + GtJ[3 * i + 1] * S[3 + j] + GtJ[3 * i + 2] * S[6 + j];
+      // J, 2-D mean, depth -> camera-space mean
+      float v_tx = 0.f, v_ty = 0.f;
+      float v_tz = p[9] - (vJ[0] * fx + vJ[4] * fy) * rz2 + (vJ[2] * fx * u + vJ[5] * fy * w) * rz2;
+      const float v_u = -vJ[2] * fx * rz, v_w = -vJ[5] * fy * rz;
+      if (free_x) { v_tx += v_u * rz; v_tz -= v_u * tx * rz2; }
+      if (free_y) { v_ty += v_w * rz; v_tz -= v_w * ty * rz2; }
+      v_tx += (K[0] * v_mx + K[3] * v_my) * rz;
+      v_ty += (K[1] * v_mx + K[4] * v_my) * rz;
+      v_tz -= ((K[0] * tx + K[1] * ty) * v_mx + (K[3] * tx + K[4] * ty) * v_my) * rz2;
+      // camera -> world
+#pragma unroll
+      for (int j = 0; j < 3; ++j) a_m[j] += Rv[j] * v_tx + Rv[3 + j] * v_ty + Rv[6 + j] * v_tz;
+      float RtS[9];   // Rv^T vS
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) RtS[3 * i + j] = Rv[i] * vS[j] + Rv[3 + i] * vS[3 + j] + Rv[6 + i] * vS[6 + j];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a_cov[3 * i + j] += RtS[3 * i] * Rv[j] + RtS[3 * i + 1] * Rv[3 + j] + RtS[3 * i + 2] * Rv[6 + j];
+      if constexpr (CAM) {      // camera -> viewmat: RC = Rv cov is still there
+        const float vt[3] = {v_tx, v_ty, v_tz};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+          for (int j = 0; j < 3; ++j)
+            cv[4 * i + j] = vt[i] * m[j] + (vS[3 * i] + vS[i]) * RC[j] + (vS[3 * i + 1] + vS[3 + i]) * RC[3 + j] + (vS[3 * i + 2] + vS[6 + i]) * RC[6 + j];
+          cv[4 * i + 3] = vt[i];
+        }
+      }
     }
-    const float v_mx = p[0], v_my = p[1], v_ca = p[2], v_cb = p[3], v_cc = p[4];
-    a_op += p[5]; a_col[0] += p[6]; a_col[1] += p[7]; a_col[2] += p[8];
-    // forward, as raster_project_kernel
-    const float* V = viewmats + 16 * c;
-    const float Rv[9] = {V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
-    const float tx = Rv[0] * m[0] + Rv[1] * m[1] + Rv[2] * m[2] + V[3];
-    const float ty = Rv[3] * m[0] + Rv[4] * m[1] + Rv[5] * m[2] + V[7];
-    const float tz = Rv[6] * m[0] + Rv[7] * m[1] + Rv[8] * m[2] + V[11];
-    float RC[9], S[9];
+    if constexpr (CAM) {
+      const size_t waves = ((size_t)N + 63) / 64, wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int k = 0; k < 3; ++k) RC[3 * i + k] = Rv[3 * i] * cov[k] + Rv[3 * i + 1] * cov[3 + k] + Rv[3 * i + 2] * cov[6 + k];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int l = 0; l < 3; ++l) S[3 * i + l] = RC[3 * i] * Rv[3 * l] + RC[3 * i + 1] * Rv[3 * l + 1] + RC[3 * i + 2] * Rv[3 * l + 2];
-    const float* K = Ks + 9 * c;
-    const float fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    const float tfx = 0.5f * width / fx, tfy = 0.5f * height / fy;
-    const float lxp = (width - cx) / fx + 0.3f * tfx, lxn = cx / fx + 0.3f * tfx;
-    const float lyp = (height - cy) / fy + 0.3f * tfy, lyn = cy / fy + 0.3f * tfy;
-    const float rz = 1.0f / tz, rz2 = rz * rz;
-    const float ux = tx * rz, uy = ty * rz;
-    const bool free_x = ux >= -lxn && ux <= lxp, free_y = uy >= -lyn && uy <= lyp;   // torch.clamp: no gradient outside the limits
-    const float u = fminf(fmaxf(ux, -lxn), lxp), w = fminf(fmaxf(uy, -lyn), lyp);
-    const float J0 = fx * rz, J2 = -fx * u * rz, J4 = fy * rz, J5 = -fy * w * rz;   // J = [[J0 0 J2] [0 J4 J5]]
-    const float a0 = J0 * S[0] + J2 * S[6], a1 = J0 * S[1] + J2 * S[7], a2 = J0 * S[2] + J2 * S[8];   // A = J S (2 x 3)
-    const float b0 = J4 * S[3] + J5 * S[6], b1 = J4 * S[4] + J5 * S[7], b2 = J4 * S[5] + J5 * S[8];
-    const float c00 = a0 * J0 + a2 * J2 + 0.3f, c01 = a1 * J4 + a2 * J5, c10 = b0 * J0 + b2 * J2, c11 = b1 * J4 + b2 * J5 + 0.3f;
-    const float det_raw = c00 * c11 - c01 * c10;
-    const float det = fmaxf(det_raw, 1e-10f), rdet = 1.0f / det;
-    const float ka = c11 * rdet, kb = -(c01 + c10) * 0.5f * rdet, kc = c00 * rdet;
-    // conic -> 2-D covariance G = d loss / d cov2d
-    float g00 = v_cc * rdet, g11 = v_ca * rdet, g01 = -0.5f * v_cb * rdet, g10 = g01;
-    if (det_raw >= 1e-10f) {
-      const float v_det = -(v_ca * ka + v_cb * kb + v_cc * kc) * rdet;
-      g00 += v_det * c11; g11 += v_det * c00; g01 -= v_det * c10; g10 -= v_det * c01;
+      for (int i = 0; i < 12; ++i) {
+        const double sum = wave_sum_hi_f64((double)cv[i]);
+        if ((threadIdx.x & 63) == 63) cam_part[((size_t)c * 12 + i) * waves + wave] = sum;
+      }
     }
-    // cov2d = J S J^T:  v_S = J^T G J,  v_J = G J S^T + G^T J S
-    const float Jm[6] = {J0, 0.f, J2, 0.f, J4, J5};
-    float GJ[6], vS[9];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { GJ[j] = g00 * Jm[j] + g01 * Jm[3 + j]; GJ[3 + j] = g10 * Jm[j] + g11 * Jm[3 + j]; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) vS[3 * i + j] = Jm[i] * GJ[j] + Jm[3 + i] * GJ[3 + j];
-    float GtJ[6];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { GtJ[j] = g00 * Jm[j] + g10 * Jm[3 + j]; GtJ[3 + j] = g01 * Jm[j] + g11 * Jm[3 + j]; }
-    float vJ[6];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        vJ[3 * i + j] = GJ[3 * i] * S[3 * j] + GJ[3 * i + 1] * S[3 * j + 1] + GJ[3 * i + 2] * S[3 * j + 2] +
-                        GtJ[3 * i] * S[j] + GtJ[3 * i + 1] * S[3 + j] + GtJ[3 * i + 2] * S[6 + j];
-    // J, 2-D mean, depth -> camera-space mean
-    float v_tx = 0.f, v_ty = 0.f;
-    float v_tz = p[9] - (vJ[0] * fx + vJ[4] * fy) * rz2 + (vJ[2] * fx * u + vJ[5] * fy * w) * rz2;
-    const float v_u = -vJ[2] * fx * rz, v_w = -vJ[5] * fy * rz;
-    if (free_x) { v_tx += v_u * rz; v_tz -= v_u * tx * rz2; }
-    if (free_y) { v_ty += v_w * rz; v_tz -= v_w * ty * rz2; }
-    v_tx += (K[0] * v_mx + K[3] * v_my) * rz;
-    v_ty += (K[1] * v_mx + K[4] * v_my) * rz;
-    v_tz -= ((K[0] * tx + K[1] * ty) * v_mx + (K[3] * tx + K[4] * ty) * v_my) * rz2;
-    // camera -> world
-#pragma unroll
-    for (int j = 0; j < 3; ++j) a_m[j] += Rv[j] * v_tx + Rv[3 + j] * v_ty + Rv[6 + j] * v_tz;
-    float RtS[9];   // Rv^T vS
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) RtS[3 * i + j] = Rv[i] * vS[j] + Rv[3 + i] * vS[3 + j] + Rv[6 + i] * vS[6 + j];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) a_cov[3 * i + j] += RtS[3 * i] * Rv[j] + RtS[3 * i + 1] * Rv[3 + j] + RtS[3 * i + 2] * Rv[6 + j];
   }
+  if (!live) return;
   // covariance = M M^T, M = R diag(s):  v_M = (v_cov + v_cov^T) M
   float vM[9], vR[9], vs[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -200,6 +261,24 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
   }
 }
 
+// v_viewmats [C,4,4]: one block per (component, camera) adds the waves' partials, thread t those of waves t, t + 256, ... in order, then
+// the 256 thread sums pairwise in a fixed tree.  The bottom row is written as zeros.
+__global__ __launch_bounds__(256) void raster_cam_reduce_kernel(const double* __restrict__ cam_part, size_t waves, float* __restrict__ v_viewmats) {
+  __shared__ double sh[256];
+  const int comp = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
+  const double* part = cam_part + ((size_t)c * 12 + comp) * waves;
+  double acc = 0.0;
+  for (size_t w = t; w < waves; w += 256) acc += part[w];
+  sh[t] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) sh[t] += sh[t + o];
+    __syncthreads();
+  }
+  if (t == 0) v_viewmats[16 * c + comp] = (float)sh[0];
+  if (comp == 0 && t < 4) v_viewmats[16 * c + 12 + t] = 0.f;
+}
+
 // the forward's pixel-space means out of its projection records; zero where the camera culled the Gaussian (a radius of 0)
 __global__ __launch_bounds__(256) void raster_means2d_kernel(const G2D* __restrict__ g2d, const int* __restrict__ radii, size_t CN,
                                                              float* __restrict__ means2d) {
@@ -210,8 +289,9 @@ __global__ __launch_bounds__(256) void raster_means2d_kernel(const G2D* __restri
   means2d[2 * i + 1] = seen ? g2d[i].my : 0.f;
 }
 
-template <int REC, bool M2D>
-void launch_bwd_kernels(const WmRasterBwdArgs& b, const RasterWs& w, unsigned int* flag, float* pair_grad, int tw, int th, hipStream_t s) {
+template <int REC, bool M2D, bool CAM>
+void launch_bwd_kernels(const WmRasterBwdArgs& b, const RasterWs& w, unsigned int* flag, float* pair_grad, double* cam_part, int tw, int th,
+                        hipStream_t s) {
   const WmRasterArgs& a = b.fwd;
   const size_t N = a.N, C = a.C;
   if (b.n_isects > 0) {
@@ -224,16 +304,20 @@ void launch_bwd_kernels(const WmRasterBwdArgs& b, const RasterWs& w, unsigned in
       hipLaunchKernelGGL(raster_composite_bwd_kernel<PAIR_REC>, grid, dim3(64), 0, s, w.g2d, w.vals[0], w.vals[1], flag, w.tile_offs, w.offsets, tw,
                          th, a.width, a.height, b.out_depth, b.v_rgb, b.v_depth, b.v_alpha, pair_grad);
   }
-  hipLaunchKernelGGL((raster_project_bwd_kernel<REC, M2D>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.means, a.quats, a.scales, a.colors,
+  hipLaunchKernelGGL((raster_project_bwd_kernel<REC, M2D, CAM>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.means, a.quats, a.scales, a.colors,
                      a.is_sh, a.viewmats, a.Ks, a.N, a.C, a.width, a.height, w.g2d, w.offsets, pair_grad, b.v_means, b.v_quats, b.v_scales,
-                     b.v_opacities, b.v_colors, b.v_means2d, b.v_means2d_abs);
+                     b.v_opacities, b.v_colors, b.v_means2d, b.v_means2d_abs, cam_part);
+  if constexpr (CAM)
+    hipLaunchKernelGGL(raster_cam_reduce_kernel, dim3(12, (unsigned)C), dim3(256), 0, s, cam_part, (N + 63) / 64, b.v_viewmats);
 }
 
 }  // namespace
 
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad) {
-  (void)N; (void)C; (void)width; (void)height;
-  return align256(256) + align256(n_isects * (absgrad ? PAIR_REC_ABS : PAIR_REC) * sizeof(float));   // buffer flag | pair records
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad, int cam) {
+  (void)width; (void)height;
+  const size_t base = align256(256) + align256(n_isects * (absgrad ? PAIR_REC_ABS : PAIR_REC) * sizeof(float));   // buffer flag | pair records
+  if (!cam || N <= 0 || C <= 0) return base;
+  return base + align256((size_t)C * 12 * (((size_t)N + 63) / 64) * sizeof(double));   // | per-wave viewmats partials [C][12][waves]
 }
 
 hipError_t wm_launch_rasterize_means2d(const void* workspace, size_t workspace_bytes, int N, int C, int width, int height, size_t max_isects,
@@ -256,14 +340,20 @@ hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s) {
   if (b.absgrad && (!b.v_means2d || !b.v_means2d_abs)) return hipErrorInvalidValue;
   RasterWs w = carve((char*)a.workspace, N, C, tiles, a.max_isects);
   if (w.total > a.workspace_bytes) return hipErrorInvalidValue;
-  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad) > b.grad_workspace_bytes) return hipErrorInvalidValue;
+  const int cam = b.v_viewmats ? 1 : 0;
+  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam) > b.grad_workspace_bytes) return hipErrorInvalidValue;
   const int rec = b.absgrad ? PAIR_REC_ABS : PAIR_REC;
   unsigned int* flag = (unsigned int*)b.grad_workspace;
   float* pair_grad = (float*)((char*)b.grad_workspace + align256(256));
+  double* cam_part = (double*)((char*)pair_grad + align256(b.n_isects * rec * sizeof(float)));   // every slot the reducer reads is written
   hipError_t e = hipMemsetAsync(b.grad_workspace, 0, align256(256) + b.n_isects * rec * sizeof(float), s);
   if (e != hipSuccess) return e;
-  if (b.absgrad) launch_bwd_kernels<PAIR_REC_ABS, true>(b, w, flag, pair_grad, tw, th, s);
-  else if (b.v_means2d) launch_bwd_kernels<PAIR_REC, true>(b, w, flag, pair_grad, tw, th, s);
-  else launch_bwd_kernels<PAIR_REC, false>(b, w, flag, pair_grad, tw, th, s);
+  if (cam) {
+    if (b.absgrad) launch_bwd_kernels<PAIR_REC_ABS, true, true>(b, w, flag, pair_grad, cam_part, tw, th, s);
+    else if (b.v_means2d) launch_bwd_kernels<PAIR_REC, true, true>(b, w, flag, pair_grad, cam_part, tw, th, s);
+    else launch_bwd_kernels<PAIR_REC, false, true>(b, w, flag, pair_grad, cam_part, tw, th, s);
+  } else if (b.absgrad) launch_bwd_kernels<PAIR_REC_ABS, true, false>(b, w, flag, pair_grad, nullptr, tw, th, s);
+  else if (b.v_means2d) launch_bwd_kernels<PAIR_REC, true, false>(b, w, flag, pair_grad, nullptr, tw, th, s);
+  else launch_bwd_kernels<PAIR_REC, false, false>(b, w, flag, pair_grad, nullptr, tw, th, s);
   return hipGetLastError();
 }

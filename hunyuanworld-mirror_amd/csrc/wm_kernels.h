@@ -275,8 +275,10 @@ struct WmRasterBwdArgs {
   void* grad_workspace; size_t grad_workspace_bytes;
   // optional: gradient of the pixel-space means [C,N,2] (zero where culled) and, with absgrad = 1, the sums of per-pixel absolute values
   float* v_means2d; float* v_means2d_abs; int absgrad;
+  // optional: gradient of viewmats [C,4,4] (rows 0-2: v_R | v_t, row 3 zero); needs the larger workspace (cam = 1)
+  float* v_viewmats;
 };
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad = 0);
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad = 0, int cam = 0);
 hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s);
 // the pixel-space means of the forward whose workspace this is, [C,N,2], zero where radii [C,N,2] has a 0
 hipError_t wm_launch_rasterize_means2d(const void* workspace, size_t workspace_bytes, int N, int C, int width, int height, size_t max_isects,

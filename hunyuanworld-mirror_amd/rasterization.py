@@ -6,7 +6,14 @@ argument order and return triples, so ``model.gs_renderer.rasterizer.rasterize_b
 
 Differentiable: when autograd is recording and any of means / quats / scales / opacities / colors requires grad, the call goes
 through ``wm_rasterize_splats_backward`` on ``.backward()`` (what gsplat's CUDA extension gives the reference's post-3DGS
-optimisation).  Cameras (``camtoworlds``, ``Ks``) get no gradient (``None``); no packed / sparse gradients.
+optimisation).  No packed / sparse gradients.
+
+Cameras: by default ``camtoworlds`` and ``Ks`` get no gradient (``None``).  ``Rasterizer(camera_grad=True)`` makes ``camtoworlds``
+differentiable (gsplat: the ``viewmats`` gradient of ``_FullyFusedProjection``, which the reference trainer's ``--pose_opt`` trains a
+pose.CameraOptModule on): the inverse ``viewmats = inv(camtoworlds)`` is then taken once in the graph, the kernels see its values,
+``wm_rasterize_splats_backward_cam`` returns the gradient of the rendered images with respect to ``viewmats`` and torch's own inverse
+backward carries it on to ``camtoworlds`` and whatever produced it.  It works on both routes and when no splat tensor requires grad
+(pose-only refinement); forward outputs are the same bits either way.  ``Ks`` gets ``None`` in every case, as in gsplat.
 
 ``rasterize_splats(..., return_info=True)`` also returns what gsplat.rasterization's ``info`` gives a densification strategy
 (strategy.DefaultStrategy): the projected ``means2d`` as part of the graph, so that ``retain_grad()`` works and ``.grad`` (and,
@@ -31,9 +38,11 @@ class _RasterizeSplats(torch.autograd.Function):
     .backward).  The node owns the forward's workspace: a later rasterize_splats call cannot disturb it before .backward()."""
 
     @staticmethod
-    def forward(ctx, rz, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors):
+    def forward(ctx, rz, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats):
+        # viewmats: None, or with camera_grad inv(camtoworlds) as a graph tensor: the input that receives the camera gradient
         cin = colors[:, 0, :] if is_sh else colors
-        rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=True)
+        rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=True,
+                                               viewmats=viewmats)
         ctx.state, ctx.geom = state, (is_sh, width, height)
         ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
         ctx.save_for_backward(depth)     # the one forward output the backward reads
@@ -43,13 +52,15 @@ class _RasterizeSplats(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
         (depth,) = ctx.saved_tensors
-        grads, _, _ = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False)
-        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[6:11]))   # cameras: no gradient
+        grads, _, _, v_vm = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False, ctx.needs_input_grad[11])
+        # camtoworlds, Ks: no gradient of their own (camtoworlds gets its through viewmats)
+        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[6:11]), v_vm)
 
 
-def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad):
-    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs (None unless asked for).
-    Without want_means2d this is wm_rasterize_splats_backward; the _ex entry gives the same five gradients bit for bit."""
+def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_cam=False):
+    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs, v_viewmats (None unless
+    asked for).  Without want_means2d this is wm_rasterize_splats_backward; the _ex entry gives the same five gradients bit for bit, and
+    so does the _cam entry that want_cam selects (v_viewmats [C,4,4]: gradient of the world-to-camera matrices)."""
     L = _lib.lib()
     means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n = state
     is_sh, width, height = geom
@@ -60,8 +71,19 @@ def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad):
     g_opac, g_col = torch.empty_like(opacities), torch.empty_like(cin)
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    v2d = v2d_abs = None
-    if not want_means2d:
+    v2d = v2d_abs = v_vm = None
+    if want_cam:
+        if want_means2d:
+            v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
+            v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
+        want_absgrad = bool(want_means2d and want_absgrad)
+        v_vm = torch.empty((V, 4, 4), device=dev, dtype=torch.float32)
+        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_cam(N, V, width, height, n, int(want_absgrad)), device=dev, dtype=torch.uint8)
+        st = L.wm_rasterize_splats_backward_cam(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
+                                                p(ws), ws.numel(), cap, n, None, p(depth), None, p(cot[0]), p(cot[1]), p(cot[2]),
+                                                p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col), p(v2d), p(v2d_abs), int(want_absgrad),
+                                                p(v_vm), p(gws), gws.numel(), stream)
+    elif not want_means2d:
         gws = torch.empty(L.wm_rasterize_backward_workspace_bytes(N, V, width, height, n), device=dev, dtype=torch.uint8)
         st = L.wm_rasterize_splats_backward(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
                                             p(ws), ws.numel(), cap, n, None, p(depth), None, p(cot[0]), p(cot[1]), p(cot[2]),
@@ -76,7 +98,7 @@ def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad):
                                                p(gws), gws.numel(), stream)
     if st != 0:
         raise RuntimeError(f"wm_rasterize_splats_backward failed with status {st}")
-    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs
+    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs, v_vm
 
 
 def _shape_grads(grads, meta, is_sh, needed):
@@ -99,11 +121,11 @@ class _ProjectMeans2d(torch.autograd.Function):
     parameter gradients all come from the one fused backward of _CompositeWithInfo, so nothing is counted twice."""
 
     @staticmethod
-    def forward(ctx, rz, shared, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors):
+    def forward(ctx, rz, shared, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats):
         cin = colors[:, 0, :] if is_sh else colors
         radii = torch.empty((int(camtoworlds.shape[0]), int(means.shape[0]), 2), device=means.device, dtype=torch.int32)
         rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=True,
-                                               radii=radii)
+                                               radii=radii, viewmats=viewmats)
         shared.update(out=(rgb, depth, alpha), state=state, radii=radii)
         ctx.shared = shared
         m2 = rz._means2d(state, radii, width, height)
@@ -118,16 +140,17 @@ class _ProjectMeans2d(torch.autograd.Function):
         if sent is None or not (v_means2d.data_ptr() == sent.data_ptr() or torch.equal(v_means2d, sent)):
             raise NotImplementedError("info['means2d'] carries gradient only from the rendered images to itself (.grad / .absgrad for a "
                                       "densification strategy): a loss computed from means2d directly is not propagated to the splats")
-        return (None,) * 12
+        return (None,) * 13
 
 
 class _CompositeWithInfo(torch.autograd.Function):
     """Second half: hands out the images of the forward _ProjectMeans2d ran, with means2d as an input.  Its backward is the one
     fused backward call: the five parameter gradients, and v_means2d as the gradient of the means2d input (-> means2d.grad
-    under retain_grad()); with absgrad, means2d.absgrad is set as a plain attribute, as gsplat's _RasterizeToPixels.backward does."""
+    under retain_grad()); with absgrad, means2d.absgrad is set as a plain attribute, as gsplat's _RasterizeToPixels.backward does.
+    viewmats (None, or with camera_grad the graph's inv(camtoworlds)) receives the camera gradient of the same call."""
 
     @staticmethod
-    def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors):
+    def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors, viewmats):
         rgb, depth, alpha = shared.pop("out")
         ctx.state, ctx.geom, ctx.want_absgrad = shared.pop("state"), geom, want_absgrad
         ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
@@ -139,21 +162,24 @@ class _CompositeWithInfo(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
         (depth,) = ctx.saved_tensors
-        grads, v2d, v2d_abs = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad)
+        grads, v2d, v2d_abs, v_vm = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad, ctx.needs_input_grad[9])
         m2 = ctx.means2d_ref()
         if ctx.want_absgrad and m2 is not None:
             m2.absgrad = v2d_abs
         ctx.shared["v_means2d"] = v2d
-        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[4:9]))
+        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[4:9]), v_vm)
 
 
 class Rasterizer:
     def __init__(self, rasterization_mode="classic", packed=True, abs_grad=True, with_eval3d=False, camera_model="pinhole",
-                 sparse_grad=False, distributed=False, grad_strategy=None):
+                 sparse_grad=False, distributed=False, grad_strategy=None, camera_grad: bool = False):
+        """camera_grad: give a camtoworlds that requires grad its gradient (through viewmats = inv(camtoworlds), taken in the graph);
+        off by default: cameras then get None.  Ks never gets a gradient (as in gsplat)."""
         if rasterization_mode != "classic" or camera_model != "pinhole" or with_eval3d or distributed:
             raise NotImplementedError("only the reference's configuration is built: classic / pinhole / no eval3d / single process")
         self.rasterization_mode, self.packed, self.abs_grad, self.camera_model = rasterization_mode, packed, abs_grad, camera_model
         self.sparse_grad, self.grad_strategy, self.distributed, self.with_eval3d = sparse_grad, grad_strategy, distributed, with_eval3d
+        self.camera_grad = bool(camera_grad)
         self._ws = None          # reusable workspace (torch uint8 tensor) and the pair capacity it was sized for
         self._cap = 0
         self.last_n_isects = 0
@@ -181,19 +207,27 @@ class Rasterizer:
             return self._with_info(splat_in, cin, is_sh, camtoworlds, Ks, int(width), int(height), self.abs_grad if absgrad is None else absgrad)
         if absgrad:
             raise ValueError("absgrad is reported through info: pass return_info=True")
-        if torch.is_grad_enabled() and any(t.requires_grad for t in splat_in):
-            return _RasterizeSplats.apply(self, is_sh, int(width), int(height), camtoworlds, Ks, *splat_in)
+        viewmats = self._graph_viewmats(camtoworlds)
+        if torch.is_grad_enabled() and (viewmats is not None or any(t.requires_grad for t in splat_in)):
+            return _RasterizeSplats.apply(self, is_sh, int(width), int(height), camtoworlds, Ks, *splat_in, viewmats)
         rgb, depth, alpha, _ = self._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False)
         return rgb, depth, alpha
 
+    def _graph_viewmats(self, camtoworlds):
+        """with camera_grad, autograd recording and a camtoworlds that requires grad: inv(camtoworlds) as part of the graph; else None"""
+        if self.camera_grad and torch.is_grad_enabled() and camtoworlds.requires_grad:
+            return torch.linalg.inv(camtoworlds.to(torch.float32))
+        return None
+
     def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad):
         V, N = int(camtoworlds.shape[0]), int(splat_in[0].shape[0])
-        if torch.is_grad_enabled() and any(t.requires_grad for t in splat_in):
+        viewmats = self._graph_viewmats(camtoworlds)
+        if torch.is_grad_enabled() and (viewmats is not None or any(t.requires_grad for t in splat_in)):
             shared = {}
-            m2 = _ProjectMeans2d.apply(self, shared, is_sh, width, height, camtoworlds, Ks, *splat_in)
+            m2 = _ProjectMeans2d.apply(self, shared, is_sh, width, height, camtoworlds, Ks, *splat_in, viewmats)
             shared["means2d_ref"] = weakref.ref(m2)
             radii = shared.pop("radii")
-            rgb, depth, alpha = _CompositeWithInfo.apply(shared, (is_sh, width, height), bool(want_absgrad), m2, *splat_in)
+            rgb, depth, alpha = _CompositeWithInfo.apply(shared, (is_sh, width, height), bool(want_absgrad), m2, *splat_in, viewmats)
         else:
             radii = torch.empty((V, N, 2), device=splat_in[0].device, dtype=torch.int32)
             rgb, depth, alpha, state = self._forward(*splat_in[:4], cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False, radii=radii)
@@ -213,15 +247,16 @@ class Rasterizer:
             raise RuntimeError(f"wm_rasterize_means2d failed with status {st}")
         return m2
 
-    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, radii=None):
+    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, radii=None, viewmats=None):
         """One wm_rasterize_splats call.  own_workspace: a workspace of this call's own (kept by the autograd node until its
-        backward has run) instead of the rasteriser's reusable one.  radii: optional [C,N,2] int32 output.
+        backward has run) instead of the rasteriser's reusable one.  radii: optional [C,N,2] int32 output.  viewmats: the inverse of
+        camtoworlds where the caller has taken it already (camera_grad); its values are used, detached.
         -> rgb, depth, alpha, state for the backward."""
         L = _lib.lib()
         dev = means.device
         N, V = int(means.shape[0]), int(camtoworlds.shape[0])
         means, quats, scales, opacities, cin = _f32(means), _f32(quats), _f32(scales), _f32(opacities).reshape(-1), _f32(cin)
-        viewmats = _f32(torch.linalg.inv(camtoworlds.detach().to(torch.float32)))  # :48
+        viewmats = _f32(torch.linalg.inv(camtoworlds.detach().to(torch.float32)) if viewmats is None else viewmats)  # :48
         Ks = _f32(Ks)
         rgb = torch.empty((V, height, width, 3), device=dev, dtype=torch.float32)
         depth = torch.empty((V, height, width, 1), device=dev, dtype=torch.float32)

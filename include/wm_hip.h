@@ -371,7 +371,8 @@ wm_status wm_rasterize_splats(const float* means, const float* quats, const floa
  * _QuatScaleToCovarPreci.backward), which the reference's "Post 3DGS Optimization" (README; gsplat's simple_trainer) runs on.
  * Gradients of out_rgb / out_depth / out_alpha of ONE wm_rasterize_splats call with respect to means [N,3], quats [N,4] (through
  * the normalisation), scales [N,3], opacities [N] and colors [N,3] (the degree-0 SH coefficients when colors_are_sh0: zero where
- * 0.2820948 sh + 0.5 <= 0).  No gradient for viewmats or Ks, no packed / sparse layout; the 2-D mean gradient and absgrad: the _ex entry below.
+ * 0.2820948 sh + 0.5 <= 0).  No packed / sparse layout; the 2-D mean gradient and absgrad: the _ex entry below; the gradient for
+ * viewmats: the _cam entry below; none for Ks.
  * CONTRACT: pass the same inputs, sizes, workspace, workspace_bytes and max_isects as the forward call and the *n_isects it
  * reported; the workspace must be UNTOUCHED between that forward and this call (no other wm_rasterize_splats on it): the
  * backward reads the projection records, the sorted pair list and the tile offsets the forward left there.  out_depth is the
@@ -407,6 +408,28 @@ wm_status wm_rasterize_splats_backward_ex(const float* means, const float* quats
                                           float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
                                           float* v_means2d, float* v_means2d_abs, int want_absgrad,
                                           void* grad_workspace, size_t grad_workspace_bytes, void* stream);
+/* The same backward with the gradient of the cameras — replaces the viewmats gradient of gsplat's _FullyFusedProjection.backward
+ * (gsplat/cuda/_wrapper.py; restated in _torch_impl.py:250-283 _world_to_cam), which the reference's post-3DGS trainer feeds to its
+ * CameraOptModule under --pose_opt (simple_trainer_worldmirror.py:511-523, 734-735, 948-950).
+ * Arguments as wm_rasterize_splats_backward_ex (v_means2d / v_means2d_abs optional in the same way) plus
+ *   v_viewmats [C,4,4], required: gradient with respect to the WORLD-TO-CAMERA matrices, [c,:3,:3] = v_R, [c,:3,3] = v_t, where per
+ *              visible (camera, Gaussian) pair v_t += v_mean_camera and v_R += outer(v_mean_camera, mean) + (v_S + v_S^T) R cov.
+ *              Overwritten; exact zeros in every bottom row and for a camera that sees nothing.  Ks gets no gradient, as in gsplat.
+ * The five splat gradients (and v_means2d, v_means2d_abs) equal those of the entries above bit for bit.
+ * Summation order: the per-pair terms are fp32; from there on fp64: each 64-Gaussian wave sums its lanes by a fixed butterfly, then per
+ * (camera, component) the waves' partials are added in a fixed order (256 strided running sums, then a fixed pairwise tree) and the
+ * result is rounded to fp32 once.  No atomics, bitwise reproducible; nothing depends on what grad_workspace held before.
+ * grad_workspace: wm_rasterize_backward_workspace_bytes_cam bytes = the _ex size + 96 bytes per camera per 64 Gaussians (rounded up
+ * to 256); a smaller workspace returns WM_ERR_INVALID before anything is launched. */
+size_t wm_rasterize_backward_workspace_bytes_cam(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad);
+wm_status wm_rasterize_splats_backward_cam(const float* means, const float* quats, const float* scales, const float* opacities,
+                                           const float* colors, int colors_are_sh0, int n_gaussians, const float* viewmats, const float* Ks,
+                                           int n_cameras, int width, int height, const void* workspace, size_t workspace_bytes,
+                                           size_t max_isects, size_t n_isects, const float* out_rgb, const float* out_depth,
+                                           const float* out_alpha, const float* v_rgb, const float* v_depth, const float* v_alpha,
+                                           float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
+                                           float* v_means2d, float* v_means2d_abs, int want_absgrad, float* v_viewmats,
+                                           void* grad_workspace, size_t grad_workspace_bytes, void* stream);
 /* The pixel-space means [C,N,2] of ONE wm_rasterize_splats call, read out of the workspace it left (same sizes and max_isects,
  * workspace untouched since); radii: that call's radii_out.  Zero where a radius is 0 (culled).  Asynchronous on stream. */
 wm_status wm_rasterize_means2d(const void* workspace, size_t workspace_bytes, int n_gaussians, int n_cameras, int width, int height,
