@@ -59,6 +59,7 @@ EXPORTS = [
     "wm_photometric_loss_workspace_bytes", "wm_photometric_loss_forward_workspace_bytes", "wm_photometric_loss", "wm_photometric_loss_backward",
     "wm_rasterize_backward_workspace_bytes_ex", "wm_rasterize_splats_backward_ex", "wm_rasterize_means2d",
     "wm_rasterize_backward_workspace_bytes_cam", "wm_rasterize_splats_backward_cam",
+    "wm_rasterize_splats_sh", "wm_rasterize_backward_workspace_bytes_sh", "wm_rasterize_splats_backward_sh",
     "wm_densify_accumulate", "wm_densify_plan_workspace_bytes", "wm_densify_plan", "wm_densify_gather",
     "wm_mcmc_inject_noise", "wm_mcmc_partition_workspace_bytes", "wm_mcmc_partition", "wm_mcmc_relocation", "wm_mcmc_scatter", "wm_mcmc_zero_rows",
 ]
@@ -170,6 +171,14 @@ def lib() -> C.CDLL:
     L.wm_rasterize_splats_backward_cam.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, C.c_size_t, vp]
     L.wm_rasterize_splats_backward_cam.restype = i32
+    L.wm_rasterize_splats_sh.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t,
+                                         C.POINTER(C.c_ulonglong), vp]
+    L.wm_rasterize_splats_sh.restype = i32
+    L.wm_rasterize_backward_workspace_bytes_sh.argtypes = [i32, i32, i32, i32, C.c_size_t, i32, i32, i32]
+    L.wm_rasterize_backward_workspace_bytes_sh.restype = C.c_size_t
+    L.wm_rasterize_splats_backward_sh.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
+                                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_size_t, vp]
+    L.wm_rasterize_splats_backward_sh.restype = i32
     L.wm_rasterize_means2d.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, C.c_size_t, vp, vp, vp]
     L.wm_rasterize_means2d.restype = i32
     L.wm_densify_accumulate.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]

@@ -3,6 +3,7 @@
 // pinhole, render_mode "RGB+ED", sh_degree 0 | None).  Stages (gsplat/rendering.py:853-992):
 //   project    quat/scale -> covariance, world -> camera, perspective EWA projection, + 0.3 blur, conic, 3.33-sigma
 //              radii, near/far + screen culling, tile rectangle        (_torch_impl.py:45-61,78-133,250-375)
+//   colour     SH degree 1-3 only: view-dependent colour into the records of the visible pairs (raster_sh.hip; rendering.py:509-525)
 //   scan       exclusive sum of tiles-per-Gaussian                     (hipCUB)
 //   emit       one (key, value) pair per touched tile: key = ((camera << tile_bits | tile) << 32) | depth bits
 //   sort       64-bit radix sort of the pairs                          (hipCUB; _torch_impl.py:378-474)
@@ -304,9 +305,16 @@ hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned lo
   while ((1 << tile_bits) <= tiles) ++tile_bits;  // = bit_length(tiles), as the reference
   int cam_bits = 0;
   while ((1ull << cam_bits) < C) ++cam_bits;
-  hipLaunchKernelGGL(raster_color_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.colors, a.N, a.is_sh, w.rgb);
+  if (a.sh_degree > 0) {   // per-(camera, Gaussian) colours: the projection writes zeros, raster_sh.hip the colours of the visible pairs
+    if (!sh_args_valid(a)) return hipErrorInvalidValue;
+    const hipError_t e0 = hipMemsetAsync(w.rgb, 0, N * sizeof(float4), s);
+    if (e0 != hipSuccess) return e0;
+  } else {
+    hipLaunchKernelGGL(raster_color_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.colors, a.N, a.is_sh, w.rgb);
+  }
   hipLaunchKernelGGL(raster_project_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)C), dim3(256), 0, s, a.means, a.quats, a.scales, a.viewmats,
                      a.Ks, a.N, a.C, a.width, a.height, 0.01f, 1e10f, a.opacities, w.rgb, w.g2d, w.counts, a.radii_out);
+  if (a.sh_degree > 0) launch_sh_colors(a, w.g2d, s);
   hipError_t e = hipMemsetAsync(w.counts + CN, 0, 8, s);
   if (e != hipSuccess) return e;
   size_t tb = w.cub_bytes;

@@ -23,6 +23,8 @@
 //              (v_R 9, v_t 3) are summed over the wave's 64 lanes in fp64 and stored by one lane as the wave's partial.
 //   camreduce  with CAM: per (camera, component) the waves' partials are added in a fixed order, in fp64 -> v_viewmats [C,4,4]
 //   means2d    the pixel-space means the forward's projection left in its records, [C,N,2], zero where culled
+//   SH 1-3     the kernels above run as for given colours (their [N,3] colour gradient goes to a scratch); raster_sh.hip then makes the
+//              coefficient gradient [N,K,3], the direction's share of v_means and v_campos out of the same pair records
 // Sums run in a fixed order everywhere, so gradients are bitwise reproducible run to run.
 #include "wm_common.h"
 #include "wm_kernels.h"
@@ -39,23 +41,6 @@ __global__ __launch_bounds__(256) void raster_locate_sorted_kernel(const unsigne
                                                                   unsigned int* __restrict__ flag) {
   const unsigned int i = blockIdx.x * 256 + threadIdx.x;
   if (i + 1 < n && keys0[i] > keys0[i + 1]) *flag = 1u;
-}
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_of_f64(double x) {   // as dpp_of, on both halves
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROW_MASK, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-// sum over the 64 lanes in the order of wave_sum_hi; the total is valid in lanes 48-63
-__device__ __forceinline__ double wave_sum_hi_f64(double v) {
-  v += dpp_of_f64<0xB1, 0xf>(v);
-  v += dpp_of_f64<0x4E, 0xf>(v);
-  v += dpp_of_f64<0x141, 0xf>(v);
-  v += dpp_of_f64<0x140, 0xf>(v);
-  v += dpp_of_f64<0x142, 0xa>(v);
-  v += dpp_of_f64<0x143, 0xc>(v);
-  return v;
 }
 
 // _torch_impl.py:11-29,45-61 (quaternion, scale -> covariance), :250-283 (world -> camera), :78-133 (perspective), :329-355 (conic)
@@ -313,11 +298,15 @@ void launch_bwd_kernels(const WmRasterBwdArgs& b, const RasterWs& w, unsigned in
 
 }  // namespace
 
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad, int cam) {
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad, int cam, int sh, int campos) {
   (void)width; (void)height;
   const size_t base = align256(256) + align256(n_isects * (absgrad ? PAIR_REC_ABS : PAIR_REC) * sizeof(float));   // buffer flag | pair records
-  if (!cam || N <= 0 || C <= 0) return base;
-  return base + align256((size_t)C * 12 * (((size_t)N + 63) / 64) * sizeof(double));   // | per-wave viewmats partials [C][12][waves]
+  size_t total = base;
+  if (N <= 0 || C <= 0) return total;
+  if (cam) total += align256((size_t)C * 12 * (((size_t)N + 63) / 64) * sizeof(double));   // | per-wave viewmats partials [C][12][waves]
+  if (sh) total += align256((size_t)N * 3 * sizeof(float));                                 // | SH: the geometric pass's colour gradient (unused)
+  if (sh && campos) total += sh_campos_part_bytes(N, C);                                    // | SH: per-wave campos partials [C][3][waves]
+  return total;
 }
 
 hipError_t wm_launch_rasterize_means2d(const void* workspace, size_t workspace_bytes, int N, int C, int width, int height, size_t max_isects,
@@ -340,12 +329,27 @@ hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s) {
   if (b.absgrad && (!b.v_means2d || !b.v_means2d_abs)) return hipErrorInvalidValue;
   RasterWs w = carve((char*)a.workspace, N, C, tiles, a.max_isects);
   if (w.total > a.workspace_bytes) return hipErrorInvalidValue;
-  const int cam = b.v_viewmats ? 1 : 0;
-  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam) > b.grad_workspace_bytes) return hipErrorInvalidValue;
+  const int cam = b.v_viewmats ? 1 : 0, sh = a.sh_degree > 0 ? 1 : 0;
+  if (sh ? !sh_args_valid(a) : b.v_campos != nullptr) return hipErrorInvalidValue;
+  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam, sh, b.v_campos ? 1 : 0) > b.grad_workspace_bytes)
+    return hipErrorInvalidValue;
   const int rec = b.absgrad ? PAIR_REC_ABS : PAIR_REC;
   unsigned int* flag = (unsigned int*)b.grad_workspace;
   float* pair_grad = (float*)((char*)b.grad_workspace + align256(256));
   double* cam_part = (double*)((char*)pair_grad + align256(b.n_isects * rec * sizeof(float)));   // every slot the reducer reads is written
+  if (sh) {
+    // SH degree 1-3: the geometric part through the kernels below as for given colours, their [N,3] colour gradient into a scratch of the
+    // workspace; then raster_sh.hip turns the pairs' colour terms into v_colors [N,K,3], its share of v_means and v_campos
+    char* sh_ws = (char*)b.grad_workspace + wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam);
+    WmRasterBwdArgs geo = b;
+    geo.fwd.sh_degree = 0; geo.fwd.is_sh = 0; geo.v_campos = nullptr;
+    geo.v_colors = (float*)sh_ws;
+    geo.grad_workspace_bytes = (size_t)(sh_ws - (char*)b.grad_workspace);
+    const hipError_t e = wm_launch_rasterize_bwd(geo, s);
+    if (e != hipSuccess) return e;
+    launch_sh_bwd(b, w, pair_grad, rec, (double*)(sh_ws + align256(N * 3 * sizeof(float))), s);
+    return hipGetLastError();
+  }
   hipError_t e = hipMemsetAsync(b.grad_workspace, 0, align256(256) + b.n_isects * rec * sizeof(float), s);
   if (e != hipSuccess) return e;
   if (cam) {

@@ -26,6 +26,22 @@ __device__ __forceinline__ float wave_sum_hi(float v) {
   v += dpp_of<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
   return v;
 }
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_of_f64(double x) {   // as dpp_of, on both halves
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, ROW_MASK, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, ROW_MASK, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+// sum over the 64 lanes in the order of wave_sum_hi; the total is valid in lanes 48-63
+__device__ __forceinline__ double wave_sum_hi_f64(double v) {
+  v += dpp_of_f64<0xB1, 0xf>(v);
+  v += dpp_of_f64<0x4E, 0xf>(v);
+  v += dpp_of_f64<0x141, 0xf>(v);
+  v += dpp_of_f64<0x140, 0xf>(v);
+  v += dpp_of_f64<0x142, 0xa>(v);
+  v += dpp_of_f64<0x143, 0xc>(v);
+  return v;
+}
 
 // Blending rules: raster.hip raster_composite_kernel (RasterizeToPixels3DGSFwd.cu:118-184); backward terms:
 // RasterizeToPixels3DGSBwd.cu (per pixel, last blended Gaussian to first).

@@ -2,6 +2,7 @@
 // projection writes, and the layout of the caller's workspace.  The backward reads what the forward left there.
 #pragma once
 #include "wm_common.h"
+#include "wm_kernels.h"
 
 namespace wm_raster {
 
@@ -14,7 +15,7 @@ struct __attribute__((aligned(16))) G2D {  // per (camera, Gaussian): 48 B = thr
   float ca, cb;         // conic
   float cc, opacity;
   float depth;
-  float r, g, b;        // colour (view-independent: degree-0 SH or given colours)
+  float r, g, b;        // colour: degree-0 SH or given colours (the same for every camera), or SH degree 1-3 along the pair's direction (raster_sh.hip)
   int rect;             // x0 | y0 << 8 | x1 << 16 | y1 << 24 in tiles (tile grids up to 255 x 255); the compositing pass reads words 0-9 only
   int pad;
 };
@@ -29,5 +30,14 @@ struct RasterWs {
 
 // the forward's carving of the caller's workspace (raster.hip; base may be null: sizes only)
 RasterWs carve(char* base, size_t N, size_t C, int tiles, size_t max_isects);
+
+// view-dependent colour, SH degree 1-3 (raster_sh.hip).  sh_args_valid: 1 <= sh_degree <= 3, (sh_degree + 1)^2 <= n_coeffs, campos given
+bool sh_args_valid(const WmRasterArgs& a);
+// after the projection: max(SH colour + 0.5, 0) into the r, g, b of every record with a tile rectangle
+void launch_sh_colors(const WmRasterArgs& a, G2D* g2d, hipStream_t s);
+// after the projection backward: v_colors [N,K,3] written, the direction's term added to v_means, v_campos [C,3] where asked for
+// (campos_part: sh_campos_part_bytes of workspace); pair_grad: the compositing backward's tile records of rec floats
+size_t sh_campos_part_bytes(size_t N, size_t C);
+void launch_sh_bwd(const WmRasterBwdArgs& b, const RasterWs& w, const float* pair_grad, int rec, double* campos_part, hipStream_t s);
 
 }  // namespace wm_raster

@@ -257,6 +257,9 @@ struct WmRasterArgs {
   const float* means; const float* quats; const float* scales; const float* opacities;  // [N,3] [N,4 wxyz] [N,3] [N]
   const float* colors; int is_sh;       // [N,3]: degree-0 SH coefficients (is_sh = 1) or final colours
   int N;
+  // view-dependent colour (raster_sh.hip): sh_degree 1-3 makes colors the SH coefficients [N,n_coeffs,3], (sh_degree + 1)^2 <= n_coeffs,
+  // evaluated along means - campos [C,3] (the cameras' world positions); is_sh is then not read.  sh_degree = 0: as above
+  int sh_degree, n_coeffs; const float* campos;
   const float* viewmats; const float* Ks; int C;  // world-to-camera [C,4,4], intrinsics [C,3,3]
   int width, height;
   float* out_rgb; float* out_depth; float* out_alpha;  // [C,H,W,3] [C,H,W] [C,H,W]
@@ -277,8 +280,11 @@ struct WmRasterBwdArgs {
   float* v_means2d; float* v_means2d_abs; int absgrad;
   // optional: gradient of viewmats [C,4,4] (rows 0-2: v_R | v_t, row 3 zero); needs the larger workspace (cam = 1)
   float* v_viewmats;
+  // optional, with fwd.sh_degree > 0 only (then v_colors is [N,n_coeffs,3]): gradient of campos [C,3], the colour's camera term
+  float* v_campos;
 };
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad = 0, int cam = 0);
+// sh = 1: a backward of an SH degree 1-3 forward; campos = 1: with v_campos
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad = 0, int cam = 0, int sh = 0, int campos = 0);
 hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s);
 // the pixel-space means of the forward whose workspace this is, [C,N,2], zero where radii [C,N,2] has a 0
 hipError_t wm_launch_rasterize_means2d(const void* workspace, size_t workspace_bytes, int N, int C, int width, int height, size_t max_isects,

@@ -2092,6 +2092,65 @@ extern "C" wm_status wm_rasterize_splats_backward_cam(const float* means, const 
   if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
   return e == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
+extern "C" wm_status wm_rasterize_splats_sh(const float* means, const float* quats, const float* scales, const float* opacities,
+                                            const float* sh_coeffs, int n_coeffs, int sh_degree, const float* campos, int n_gaussians,
+                                            const float* viewmats, const float* Ks, int n_cameras, int width, int height, float* out_rgb,
+                                            float* out_depth, float* out_alpha, int* radii_out, void* workspace, size_t workspace_bytes,
+                                            size_t max_isects, unsigned long long* n_isects, void* stream) {
+  if (!means || !quats || !scales || !opacities || !sh_coeffs || !campos || !viewmats || !Ks || !out_rgb || !out_depth || !out_alpha || !workspace)
+    return WM_ERR_INVALID;
+  if (sh_degree < 1 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > n_coeffs) return WM_ERR_INVALID;
+  WmRasterArgs a;
+  memset(&a, 0, sizeof(a));
+  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = sh_coeffs;
+  a.sh_degree = sh_degree; a.n_coeffs = n_coeffs; a.campos = campos;
+  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
+  a.out_rgb = out_rgb; a.out_depth = out_depth; a.out_alpha = out_alpha; a.radii_out = radii_out;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
+  unsigned long long n = 0;
+  const hipError_t e = wm_launch_rasterize(a, (hipStream_t)stream, &n);
+  if (n_isects) *n_isects = n;
+  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
+  if (e != hipSuccess) return WM_ERR_HIP;
+  return n > max_isects ? WM_ERR_STATE : WM_OK;
+}
+extern "C" size_t wm_rasterize_backward_workspace_bytes_sh(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad,
+                                                           int want_viewmats, int want_campos) {
+  return wm_raster_bwd_workspace_bytes(n_gaussians, n_cameras, width, height, n_isects, want_absgrad ? 1 : 0, want_viewmats ? 1 : 0, 1,
+                                       want_campos ? 1 : 0);
+}
+extern "C" wm_status wm_rasterize_splats_backward_sh(const float* means, const float* quats, const float* scales, const float* opacities,
+                                                     const float* sh_coeffs, int n_coeffs, int sh_degree, const float* campos, int n_gaussians,
+                                                     const float* viewmats, const float* Ks, int n_cameras, int width, int height,
+                                                     const void* workspace, size_t workspace_bytes, size_t max_isects, size_t n_isects,
+                                                     const float* out_rgb, const float* out_depth, const float* out_alpha, const float* v_rgb,
+                                                     const float* v_depth, const float* v_alpha, float* v_means, float* v_quats, float* v_scales,
+                                                     float* v_opacities, float* v_sh_coeffs, float* v_means2d, float* v_means2d_abs,
+                                                     int want_absgrad, float* v_viewmats, float* v_campos, void* grad_workspace,
+                                                     size_t grad_workspace_bytes, void* stream) {
+  (void)out_rgb; (void)out_alpha;
+  if (!means || !quats || !scales || !opacities || !sh_coeffs || !campos || !viewmats || !Ks || !workspace || !out_depth || !v_rgb || !v_depth ||
+      !v_alpha || !v_means || !v_quats || !v_scales || !v_opacities || !v_sh_coeffs || !grad_workspace)
+    return WM_ERR_INVALID;
+  if (sh_degree < 1 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > n_coeffs) return WM_ERR_INVALID;
+  if (want_absgrad && (!v_means2d || !v_means2d_abs)) return WM_ERR_INVALID;
+  if (n_isects > max_isects) return WM_ERR_STATE;
+  WmRasterBwdArgs b;
+  memset(&b, 0, sizeof(b));
+  WmRasterArgs& a = b.fwd;
+  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = sh_coeffs;
+  a.sh_degree = sh_degree; a.n_coeffs = n_coeffs; a.campos = campos;
+  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
+  a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
+  b.n_isects = n_isects; b.out_depth = out_depth; b.v_rgb = v_rgb; b.v_depth = v_depth; b.v_alpha = v_alpha;
+  b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_opacities = v_opacities; b.v_colors = v_sh_coeffs;
+  b.v_means2d = v_means2d; b.v_means2d_abs = want_absgrad ? v_means2d_abs : nullptr; b.absgrad = want_absgrad ? 1 : 0;
+  b.v_viewmats = v_viewmats; b.v_campos = v_campos;
+  b.grad_workspace = grad_workspace; b.grad_workspace_bytes = grad_workspace_bytes;
+  const hipError_t e = wm_launch_rasterize_bwd(b, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
+  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+}
 extern "C" wm_status wm_rasterize_means2d(const void* workspace, size_t workspace_bytes, int n_gaussians, int n_cameras, int width, int height,
                                           size_t max_isects, const int* radii, float* means2d, void* stream) {
   if (!workspace || !radii || !means2d) return WM_ERR_INVALID;

@@ -15,6 +15,13 @@ pose.CameraOptModule on): the inverse ``viewmats = inv(camtoworlds)`` is then ta
 backward carries it on to ``camtoworlds`` and whatever produced it.  It works on both routes and when no splat tensor requires grad
 (pose-only refinement); forward outputs are the same bits either way.  ``Ks`` gets ``None`` in every case, as in gsplat.
 
+View-dependent colour: ``colors [N,K,3]`` with ``sh_degree`` 1-3, ``(sh_degree + 1)^2 <= K`` (gsplat/rendering.py:509-525; the reference
+trainer raises ``sh_degree_to_use`` while it trains, simple_trainer_worldmirror.py:613, :738-746), goes through ``wm_rasterize_splats_sh``
+and ``wm_rasterize_splats_backward_sh`` on every route.  The colour of a (camera, Gaussian) pair is evaluated along ``means - campos``,
+``campos = camtoworlds[:, :3, 3]`` (gsplat's ``inverse(viewmats)[:, :3, 3]``); ``colors.grad`` has the full ``[N,K,3]`` shape with exact zeros
+in the bands at or above ``(sh_degree + 1)^2``, ``means.grad`` includes the direction's term, and with ``camera_grad`` ``campos`` is a
+second graph tensor beside ``viewmats``, so that ``camtoworlds.grad`` is the sum of both.  ``sh_degree`` 0 and ``None`` go as before.
+
 ``rasterize_splats(..., return_info=True)`` also returns what gsplat.rasterization's ``info`` gives a densification strategy
 (strategy.DefaultStrategy): the projected ``means2d`` as part of the graph, so that ``retain_grad()`` works and ``.grad`` (and,
 with absgrad, the plain attribute ``.absgrad``) is there after ``loss.backward()``, and the per-(camera, Gaussian) ``radii``.
@@ -38,11 +45,11 @@ class _RasterizeSplats(torch.autograd.Function):
     .backward).  The node owns the forward's workspace: a later rasterize_splats call cannot disturb it before .backward()."""
 
     @staticmethod
-    def forward(ctx, rz, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats):
-        # viewmats: None, or with camera_grad inv(camtoworlds) as a graph tensor: the input that receives the camera gradient
-        cin = colors[:, 0, :] if is_sh else colors
-        rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=True,
-                                               viewmats=viewmats)
+    def forward(ctx, rz, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats, campos, sh_degree):
+        # viewmats: None, or with camera_grad inv(camtoworlds) as a graph tensor: the input that receives the camera gradient;
+        # campos: None, or with camera_grad and sh_degree > 0 the camera positions as a graph tensor: receives the colour's camera term
+        rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, _cin(colors, is_sh, sh_degree), is_sh, camtoworlds, Ks, width, height,
+                                               own_workspace=True, viewmats=viewmats, sh_degree=sh_degree, campos=campos)
         ctx.state, ctx.geom = state, (is_sh, width, height)
         ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
         ctx.save_for_backward(depth)     # the one forward output the backward reads
@@ -52,17 +59,25 @@ class _RasterizeSplats(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
         (depth,) = ctx.saved_tensors
-        grads, _, _, v_vm = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False, ctx.needs_input_grad[11])
-        # camtoworlds, Ks: no gradient of their own (camtoworlds gets its through viewmats)
-        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[6:11]), v_vm)
+        grads, _, _, v_vm, v_cp = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False, ctx.needs_input_grad[11],
+                                            ctx.needs_input_grad[12])
+        # camtoworlds, Ks: no gradient of their own (camtoworlds gets its through viewmats and campos)
+        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0] and not ctx.state[10], ctx.needs_input_grad[6:11]),
+                v_vm, v_cp, None)
 
 
-def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_cam=False):
-    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs, v_viewmats (None unless
-    asked for).  Without want_means2d this is wm_rasterize_splats_backward; the _ex entry gives the same five gradients bit for bit, and
-    so does the _cam entry that want_cam selects (v_viewmats [C,4,4]: gradient of the world-to-camera matrices)."""
+def _cin(colors, is_sh, sh_degree):
+    """what the kernels read: all of the SH coefficients [N,K,3] for sh_degree 1-3, band 0 for degree 0, the colours [N,3] otherwise"""
+    return colors[:, 0, :] if is_sh and not sh_degree else colors
+
+
+def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_cam=False, want_campos=False):
+    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs, v_viewmats, v_campos (None
+    unless asked for).  Without want_means2d this is wm_rasterize_splats_backward; the _ex entry gives the same five gradients bit for bit,
+    and so does the _cam entry that want_cam selects (v_viewmats [C,4,4]: gradient of the world-to-camera matrices).  A forward with SH
+    degree 1-3 goes through the _sh entry on every route (g_colors [N,K,3]; v_campos [C,3]: gradient of the camera positions)."""
     L = _lib.lib()
-    means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n = state
+    means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n, sh_degree, campos = state
     is_sh, width, height = geom
     dev = means.device
     N, V = int(means.shape[0]), int(viewmats.shape[0])
@@ -71,8 +86,21 @@ def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_c
     g_opac, g_col = torch.empty_like(opacities), torch.empty_like(cin)
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    v2d = v2d_abs = v_vm = None
-    if want_cam:
+    v2d = v2d_abs = v_vm = v_cp = None
+    if sh_degree:
+        if want_means2d:
+            v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
+            v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
+        want_absgrad = bool(want_means2d and want_absgrad)
+        v_vm = torch.empty((V, 4, 4), device=dev, dtype=torch.float32) if want_cam else None
+        v_cp = torch.empty((V, 3), device=dev, dtype=torch.float32) if want_campos else None
+        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_sh(N, V, width, height, n, int(want_absgrad), int(bool(want_cam)), int(bool(want_campos))),
+                          device=dev, dtype=torch.uint8)
+        st = L.wm_rasterize_splats_backward_sh(p(means), p(quats), p(scales), p(opacities), p(cin), int(cin.shape[1]), sh_degree, p(campos), N,
+                                               p(viewmats), p(Ks), V, width, height, p(ws), ws.numel(), cap, n, None, p(depth), None,
+                                               p(cot[0]), p(cot[1]), p(cot[2]), p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col),
+                                               p(v2d), p(v2d_abs), int(want_absgrad), p(v_vm), p(v_cp), p(gws), gws.numel(), stream)
+    elif want_cam:
         if want_means2d:
             v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
             v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
@@ -98,7 +126,7 @@ def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_c
                                                p(gws), gws.numel(), stream)
     if st != 0:
         raise RuntimeError(f"wm_rasterize_splats_backward failed with status {st}")
-    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs, v_vm
+    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs, v_vm, v_cp
 
 
 def _shape_grads(grads, meta, is_sh, needed):
@@ -107,7 +135,7 @@ def _shape_grads(grads, meta, is_sh, needed):
         if not needed[i]:
             out.append(None)
             continue
-        if i == 4 and is_sh:     # SH coefficients [N, K, 3]: only degree 0 is rendered
+        if i == 4 and is_sh:     # SH coefficients [N, K, 3] of which only degree 0 is rendered (is_sh here: degree 0)
             full = torch.zeros(shape, device=g.device, dtype=torch.float32)
             full[:, 0, :] = g
             g = full
@@ -121,11 +149,10 @@ class _ProjectMeans2d(torch.autograd.Function):
     parameter gradients all come from the one fused backward of _CompositeWithInfo, so nothing is counted twice."""
 
     @staticmethod
-    def forward(ctx, rz, shared, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats):
-        cin = colors[:, 0, :] if is_sh else colors
+    def forward(ctx, rz, shared, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats, campos, sh_degree):
         radii = torch.empty((int(camtoworlds.shape[0]), int(means.shape[0]), 2), device=means.device, dtype=torch.int32)
-        rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=True,
-                                               radii=radii, viewmats=viewmats)
+        rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, _cin(colors, is_sh, sh_degree), is_sh, camtoworlds, Ks, width, height,
+                                               own_workspace=True, radii=radii, viewmats=viewmats, sh_degree=sh_degree, campos=campos)
         shared.update(out=(rgb, depth, alpha), state=state, radii=radii)
         ctx.shared = shared
         m2 = rz._means2d(state, radii, width, height)
@@ -140,17 +167,18 @@ class _ProjectMeans2d(torch.autograd.Function):
         if sent is None or not (v_means2d.data_ptr() == sent.data_ptr() or torch.equal(v_means2d, sent)):
             raise NotImplementedError("info['means2d'] carries gradient only from the rendered images to itself (.grad / .absgrad for a "
                                       "densification strategy): a loss computed from means2d directly is not propagated to the splats")
-        return (None,) * 13
+        return (None,) * 15
 
 
 class _CompositeWithInfo(torch.autograd.Function):
     """Second half: hands out the images of the forward _ProjectMeans2d ran, with means2d as an input.  Its backward is the one
     fused backward call: the five parameter gradients, and v_means2d as the gradient of the means2d input (-> means2d.grad
     under retain_grad()); with absgrad, means2d.absgrad is set as a plain attribute, as gsplat's _RasterizeToPixels.backward does.
-    viewmats (None, or with camera_grad the graph's inv(camtoworlds)) receives the camera gradient of the same call."""
+    viewmats (None, or with camera_grad the graph's inv(camtoworlds)) receives the camera gradient of the same call, campos (None, or with
+    camera_grad and SH degree 1-3 the graph's camera positions) the colour's camera term."""
 
     @staticmethod
-    def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors, viewmats):
+    def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors, viewmats, campos):
         rgb, depth, alpha = shared.pop("out")
         ctx.state, ctx.geom, ctx.want_absgrad = shared.pop("state"), geom, want_absgrad
         ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
@@ -162,12 +190,13 @@ class _CompositeWithInfo(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
         (depth,) = ctx.saved_tensors
-        grads, v2d, v2d_abs, v_vm = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad, ctx.needs_input_grad[9])
+        grads, v2d, v2d_abs, v_vm, v_cp = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad,
+                                                    ctx.needs_input_grad[9], ctx.needs_input_grad[10])
         m2 = ctx.means2d_ref()
         if ctx.want_absgrad and m2 is not None:
             m2.absgrad = v2d_abs
         ctx.shared["v_means2d"] = v2d
-        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0], ctx.needs_input_grad[4:9]), v_vm)
+        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0] and not ctx.state[10], ctx.needs_input_grad[4:9]), v_vm, v_cp)
 
 
 class Rasterizer:
@@ -194,23 +223,30 @@ class Rasterizer:
             raise TypeError(f"unsupported gsplat.rasterization arguments: {sorted(kwargs)}")
         if means.device.type != "cuda":
             raise RuntimeError("the rasteriser runs in libwm_hip.so on the GPU: move the splats to a HIP device")
+        L = 0
         if colors.dim() == 3:            # SH coefficients [N, K, 3]
-            if sh_degree is None or int(sh_degree) != 0:
-                raise NotImplementedError("SH degree 0 only (the reference renders with sh_degree = min(self.sh_degree, 0))")
-            cin, is_sh = colors[:, 0, :], 1
+            if sh_degree is None or not 0 <= int(sh_degree) <= 3:
+                raise NotImplementedError(f"SH degrees 0 to 3 are built, not sh_degree = {sh_degree}")
+            L, K = int(sh_degree), int(colors.shape[1])
+            if (L + 1) ** 2 > K:
+                raise ValueError(f"sh_degree = {L} reads {(L + 1) ** 2} bands, colors has K = {K}")
+            cin, is_sh = _cin(colors, 1, L), 1
         else:                            # post-activation colours [N, 3]
             if sh_degree is not None:
                 raise ValueError("colors [N, 3] go with sh_degree = None")
             cin, is_sh = colors, 0
         splat_in = (means, quats, scales, opacities, colors)
         if return_info:
-            return self._with_info(splat_in, cin, is_sh, camtoworlds, Ks, int(width), int(height), self.abs_grad if absgrad is None else absgrad)
+            return self._with_info(splat_in, cin, is_sh, camtoworlds, Ks, int(width), int(height), self.abs_grad if absgrad is None else absgrad, L)
         if absgrad:
             raise ValueError("absgrad is reported through info: pass return_info=True")
-        viewmats = self._graph_viewmats(camtoworlds)
+        viewmats, campos = self._graph_viewmats(camtoworlds), None
+        if viewmats is not None and L:
+            campos = camtoworlds.to(torch.float32)[:, :3, 3]
         if torch.is_grad_enabled() and (viewmats is not None or any(t.requires_grad for t in splat_in)):
-            return _RasterizeSplats.apply(self, is_sh, int(width), int(height), camtoworlds, Ks, *splat_in, viewmats)
-        rgb, depth, alpha, _ = self._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False)
+            return _RasterizeSplats.apply(self, is_sh, int(width), int(height), camtoworlds, Ks, *splat_in, viewmats, campos, L)
+        rgb, depth, alpha, _ = self._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False,
+                                             sh_degree=L)
         return rgb, depth, alpha
 
     def _graph_viewmats(self, camtoworlds):
@@ -219,18 +255,21 @@ class Rasterizer:
             return torch.linalg.inv(camtoworlds.to(torch.float32))
         return None
 
-    def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad):
+    def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad, sh_degree=0):
         V, N = int(camtoworlds.shape[0]), int(splat_in[0].shape[0])
-        viewmats = self._graph_viewmats(camtoworlds)
+        viewmats, campos = self._graph_viewmats(camtoworlds), None
+        if viewmats is not None and sh_degree:
+            campos = camtoworlds.to(torch.float32)[:, :3, 3]
         if torch.is_grad_enabled() and (viewmats is not None or any(t.requires_grad for t in splat_in)):
             shared = {}
-            m2 = _ProjectMeans2d.apply(self, shared, is_sh, width, height, camtoworlds, Ks, *splat_in, viewmats)
+            m2 = _ProjectMeans2d.apply(self, shared, is_sh, width, height, camtoworlds, Ks, *splat_in, viewmats, campos, sh_degree)
             shared["means2d_ref"] = weakref.ref(m2)
             radii = shared.pop("radii")
-            rgb, depth, alpha = _CompositeWithInfo.apply(shared, (is_sh, width, height), bool(want_absgrad), m2, *splat_in, viewmats)
+            rgb, depth, alpha = _CompositeWithInfo.apply(shared, (is_sh, width, height), bool(want_absgrad), m2, *splat_in, viewmats, campos)
         else:
             radii = torch.empty((V, N, 2), device=splat_in[0].device, dtype=torch.int32)
-            rgb, depth, alpha, state = self._forward(*splat_in[:4], cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False, radii=radii)
+            rgb, depth, alpha, state = self._forward(*splat_in[:4], cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False, radii=radii,
+                                                     sh_degree=sh_degree)
             m2 = self._means2d(state, radii, width, height)
         info = {"means2d": m2, "radii": radii, "width": width, "height": height, "n_cameras": V, "gaussian_ids": None}
         return rgb, depth, alpha, info
@@ -247,10 +286,12 @@ class Rasterizer:
             raise RuntimeError(f"wm_rasterize_means2d failed with status {st}")
         return m2
 
-    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, radii=None, viewmats=None):
-        """One wm_rasterize_splats call.  own_workspace: a workspace of this call's own (kept by the autograd node until its
-        backward has run) instead of the rasteriser's reusable one.  radii: optional [C,N,2] int32 output.  viewmats: the inverse of
-        camtoworlds where the caller has taken it already (camera_grad); its values are used, detached.
+    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, radii=None, viewmats=None,
+                 sh_degree=0, campos=None):
+        """One wm_rasterize_splats call (sh_degree 1-3: wm_rasterize_splats_sh, cin the coefficients [N,K,3]).  own_workspace: a workspace
+        of this call's own (kept by the autograd node until its backward has run) instead of the rasteriser's reusable one.  radii:
+        optional [C,N,2] int32 output.  viewmats, campos: the inverse of camtoworlds and its translation column where the caller has taken
+        them already (camera_grad); their values are used, detached.
         -> rgb, depth, alpha, state for the backward."""
         L = _lib.lib()
         dev = means.device
@@ -258,6 +299,8 @@ class Rasterizer:
         means, quats, scales, opacities, cin = _f32(means), _f32(quats), _f32(scales), _f32(opacities).reshape(-1), _f32(cin)
         viewmats = _f32(torch.linalg.inv(camtoworlds.detach().to(torch.float32)) if viewmats is None else viewmats)  # :48
         Ks = _f32(Ks)
+        if sh_degree:
+            campos = _f32(camtoworlds[:, :3, 3] if campos is None else campos)
         rgb = torch.empty((V, height, width, 3), device=dev, dtype=torch.float32)
         depth = torch.empty((V, height, width, 1), device=dev, dtype=torch.float32)
         alpha = torch.empty((V, height, width, 1), device=dev, dtype=torch.float32)
@@ -273,8 +316,12 @@ class Rasterizer:
             if not own_workspace:
                 self._ws = ws
             self._cap = cap
-            st = L.wm_rasterize_splats(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
-                                       p(rgb), p(depth), p(alpha), None if radii is None else p(radii), p(ws), ws.numel(), cap, C.byref(n), stream)
+            tail = (p(viewmats), p(Ks), V, width, height, p(rgb), p(depth), p(alpha), None if radii is None else p(radii), p(ws), ws.numel(), cap,
+                    C.byref(n), stream)
+            if sh_degree:
+                st = L.wm_rasterize_splats_sh(p(means), p(quats), p(scales), p(opacities), p(cin), int(cin.shape[1]), sh_degree, p(campos), N, *tail)
+            else:
+                st = L.wm_rasterize_splats(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, *tail)
             if st == 0:
                 break
             if st == 3 and n.value > cap:   # WM_ERR_STATE: more (Gaussian, tile) pairs than the workspace holds
@@ -284,7 +331,7 @@ class Rasterizer:
         else:
             raise RuntimeError("wm_rasterize_splats: workspace re-size did not converge")
         self.last_n_isects = int(n.value)
-        return rgb, depth, alpha, (means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, int(n.value))
+        return rgb, depth, alpha, (means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, int(n.value), int(sh_degree), campos)
 
     # rasterization.py:68-93 (NB: the reference passes what it calls `viewmats` on as `camtoworlds`)
     def rasterize_batches(self, means, quats, scales, opacities, colors, viewmats, Ks, width, height, **kwargs):

@@ -430,6 +430,45 @@ wm_status wm_rasterize_splats_backward_cam(const float* means, const float* quat
                                            float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
                                            float* v_means2d, float* v_means2d_abs, int want_absgrad, float* v_viewmats,
                                            void* grad_workspace, size_t grad_workspace_bytes, void* stream);
+/* View-dependent colour: the forward with real spherical harmonics of degree 1-3 — replaces gsplat.rasterization called with
+ * colors [N,K,3] and sh_degree > 0 (gsplat/rendering.py:509-525 -> gsplat/cuda/_wrapper.py spherical_harmonics, restated in
+ * _torch_impl.py:720-822), which the reference's post-3DGS trainer selects as sh_degree_to_use rises (simple_trainer_worldmirror.py:613,
+ * :738-746).  Arguments as wm_rasterize_splats, with in place of colors / colors_are_sh0:
+ *   sh_coeffs [N,n_coeffs,3], sh_degree L in 1..3 with (L + 1)^2 <= n_coeffs (bands at or above (L + 1)^2 are not read),
+ *   campos [C,3]: the cameras' world positions (gsplat: inverse(viewmats)[:, :3, 3]).
+ * Per (camera, Gaussian) pair that the projection did not cull: colour = max(sum_k B_k(normalize(means - campos)) sh_coeffs[k] + 0.5, 0),
+ * normalize(d) = d / max(|d|, 1e-12).  Projection, binning, sort and compositing are those of wm_rasterize_splats; the workspace is
+ * wm_rasterize_workspace_bytes.  WM_ERR_INVALID for L < 1, L > 3 or (L + 1)^2 > n_coeffs; WM_ERR_STATE as wm_rasterize_splats. */
+wm_status wm_rasterize_splats_sh(const float* means, const float* quats, const float* scales, const float* opacities,
+                                 const float* sh_coeffs, int n_coeffs, int sh_degree, const float* campos, int n_gaussians,
+                                 const float* viewmats, const float* Ks, int n_cameras, int width, int height, float* out_rgb,
+                                 float* out_depth, float* out_alpha, int* radii_out, void* workspace, size_t workspace_bytes,
+                                 size_t max_isects, unsigned long long* n_isects, void* stream);
+/* Backward of ONE wm_rasterize_splats_sh call — replaces the backward of gsplat's _SphericalHarmonics (gsplat/cuda/_wrapper.py; gradient
+ * to the coefficients and, through dirs = means - campos, to the means and the cameras) together with what wm_rasterize_splats_backward_cam
+ * replaces.  Same CONTRACT on the forward's workspace as wm_rasterize_splats_backward.  Outputs, a superset of the _cam entry's:
+ *   v_means, v_quats, v_scales, v_opacities   as the entries above; v_means includes the colour's term through the direction
+ *   v_sh_coeffs [N,n_coeffs,3]                sum over cameras of B_k v_colour, v_colour zero where the clamped channel is 0; bands at or
+ *                                             above (L + 1)^2 are written as exact zeros
+ *   v_means2d, v_means2d_abs, want_absgrad    optional, as the _ex entry
+ *   v_viewmats [C,4,4]                        optional (may be null), as the _cam entry: the PROJECTION's term only, bottom row exact zeros
+ *   v_campos [C,3]                            optional (may be null): the colour's camera term, minus the sum over Gaussians of the
+ *                                             direction's gradient; exact zeros for a camera that sees nothing
+ * v_campos is summed as v_viewmats is: per-pair terms fp32, from there on fp64, a fixed butterfly over each wave's 64 lanes, the waves'
+ * partials added in a fixed order, rounded to fp32 once.  No atomics, bitwise reproducible; nothing depends on what grad_workspace held.
+ * grad_workspace: wm_rasterize_backward_workspace_bytes_sh bytes (the _ex / _cam size + 12 bytes per Gaussian, + 24 bytes per camera per
+ * 64 Gaussians with want_campos, each rounded up to 256); a smaller one returns WM_ERR_INVALID before anything is launched. */
+size_t wm_rasterize_backward_workspace_bytes_sh(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad,
+                                                int want_viewmats, int want_campos);
+wm_status wm_rasterize_splats_backward_sh(const float* means, const float* quats, const float* scales, const float* opacities,
+                                          const float* sh_coeffs, int n_coeffs, int sh_degree, const float* campos, int n_gaussians,
+                                          const float* viewmats, const float* Ks, int n_cameras, int width, int height,
+                                          const void* workspace, size_t workspace_bytes, size_t max_isects, size_t n_isects,
+                                          const float* out_rgb, const float* out_depth, const float* out_alpha, const float* v_rgb,
+                                          const float* v_depth, const float* v_alpha, float* v_means, float* v_quats, float* v_scales,
+                                          float* v_opacities, float* v_sh_coeffs, float* v_means2d, float* v_means2d_abs,
+                                          int want_absgrad, float* v_viewmats, float* v_campos, void* grad_workspace,
+                                          size_t grad_workspace_bytes, void* stream);
 /* The pixel-space means [C,N,2] of ONE wm_rasterize_splats call, read out of the workspace it left (same sizes and max_isects,
  * workspace untouched since); radii: that call's radii_out.  Zero where a radius is 0 (culled).  Asynchronous on stream. */
 wm_status wm_rasterize_means2d(const void* workspace, size_t workspace_bytes, int n_gaussians, int n_cameras, int width, int height,
