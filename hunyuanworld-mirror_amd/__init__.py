@@ -4,7 +4,7 @@ from .worldmirror import WorldMirror, extract_priors  # noqa: F401
 from .geometry import (create_confidence_mask, depth_edge, depth_to_world_coords_points, filter_points_mask,  # noqa: F401
                        normals_edge)
 from .ingest import load_and_preprocess_images, preprocess_rgb  # noqa: F401
-from .rasterization import Rasterizer  # noqa: F401
+from .rasterization import Rasterizer, rasterization  # noqa: F401
 from .losses import fused_ssim, photometric_loss  # noqa: F401
 from .strategy import DefaultStrategy  # noqa: F401
 from .strategy_mcmc import MCMCStrategy  # noqa: F401

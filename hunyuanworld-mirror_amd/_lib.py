@@ -45,6 +45,12 @@ class wm_outputs(C.Structure):
         "splat_opacities", "splat_sh", "splat_weights")] + [("taps", _FP * 4)]
 
 
+class wm_raster_options(C.Structure):
+    """include/wm_hip.h wm_raster_options: gsplat.rasterization's options as the _opt rasteriser entries take them"""
+    _fields_ = [("antialiased", C.c_int), ("depth_mode", C.c_int), ("eps2d", C.c_float), ("near_plane", C.c_float), ("far_plane", C.c_float),
+                ("radius_clip", C.c_float), ("backgrounds", C.c_void_p)]
+
+
 EXPORTS = [
     "wm_create", "wm_destroy", "wm_last_error", "wm_set_weight", "wm_finalize_weights", "wm_host_resample_pos",
     "wm_workspace_bytes", "wm_reserve", "wm_set_workspace", "wm_missing_name", "wm_share_weights", "wm_forward", "wm_forward_sharded", "wm_rccl_unique_id", "wm_comm_init_rccl",
@@ -60,6 +66,7 @@ EXPORTS = [
     "wm_rasterize_backward_workspace_bytes_ex", "wm_rasterize_splats_backward_ex", "wm_rasterize_means2d",
     "wm_rasterize_backward_workspace_bytes_cam", "wm_rasterize_splats_backward_cam",
     "wm_rasterize_splats_sh", "wm_rasterize_backward_workspace_bytes_sh", "wm_rasterize_splats_backward_sh",
+    "wm_rasterize_splats_opt", "wm_rasterize_backward_workspace_bytes_opt", "wm_rasterize_splats_backward_opt",
     "wm_densify_accumulate", "wm_densify_plan_workspace_bytes", "wm_densify_plan", "wm_densify_gather",
     "wm_mcmc_inject_noise", "wm_mcmc_partition_workspace_bytes", "wm_mcmc_partition", "wm_mcmc_relocation", "wm_mcmc_scatter", "wm_mcmc_zero_rows",
 ]
@@ -179,6 +186,15 @@ def lib() -> C.CDLL:
     L.wm_rasterize_splats_backward_sh.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_size_t, vp]
     L.wm_rasterize_splats_backward_sh.restype = i32
+    optp = C.POINTER(wm_raster_options)
+    L.wm_rasterize_splats_opt.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, optp, vp, vp, vp, vp, vp, C.c_size_t,
+                                          C.c_size_t, C.POINTER(C.c_ulonglong), vp]
+    L.wm_rasterize_splats_opt.restype = i32
+    L.wm_rasterize_backward_workspace_bytes_opt.argtypes = [i32, i32, i32, i32, C.c_size_t, i32, i32, i32, i32, i32]
+    L.wm_rasterize_backward_workspace_bytes_opt.restype = C.c_size_t
+    L.wm_rasterize_splats_backward_opt.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, optp, vp, C.c_size_t, C.c_size_t,
+                                                   C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.wm_rasterize_splats_backward_opt.restype = i32
     L.wm_rasterize_means2d.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, C.c_size_t, vp, vp, vp]
     L.wm_rasterize_means2d.restype = i32
     L.wm_densify_accumulate.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]

@@ -1,8 +1,9 @@
 // 3D-Gaussian-splat rasteriser forward — the call the reference makes through
 // Rasterizer.rasterize_splats (src/models/models/rasterization.py:29-66): gsplat.rasterization(packed, "classic",
 // pinhole, render_mode "RGB+ED", sh_degree 0 | None).  Stages (gsplat/rendering.py:853-992):
-//   project    quat/scale -> covariance, world -> camera, perspective EWA projection, + 0.3 blur, conic, 3.33-sigma
-//              radii, near/far + screen culling, tile rectangle        (_torch_impl.py:45-61,78-133,250-375)
+//   project    quat/scale -> covariance, world -> camera, perspective EWA projection, + eps2d blur, conic, 3.33-sigma
+//              radii, near/far + screen culling, tile rectangle        (_torch_impl.py:45-61,78-133,250-375); antialiased:
+//              the record's opacity is opacity * compensation; radius_clip: gsplat's small-splat cull
 //   colour     SH degree 1-3 only: view-dependent colour into the records of the visible pairs (raster_sh.hip; rendering.py:509-525)
 //   scan       exclusive sum of tiles-per-Gaussian                     (hipCUB)
 //   emit       one (key, value) pair per touched tile: key = ((camera << tile_bits | tile) << 32) | depth bits
@@ -29,7 +30,8 @@ namespace {
 __global__ __launch_bounds__(256) void raster_project_kernel(const float* __restrict__ means, const float* __restrict__ quats,
                                                              const float* __restrict__ scales, const float* __restrict__ viewmats,
                                                              const float* __restrict__ Ks, int N, int C, int width, int height,
-                                                             float near_plane, float far_plane, const float* __restrict__ opac,
+                                                             float near_plane, float far_plane, float eps2d, float radius_clip,
+                                                             int antialiased, const float* __restrict__ opac,
                                                              const float4* __restrict__ rgb, G2D* __restrict__ g2d,
                                                              unsigned long long* __restrict__ counts, int* __restrict__ radii_out) {
   const int g = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
@@ -81,9 +83,12 @@ __global__ __launch_bounds__(256) void raster_project_kernel(const float* __rest
   const float b0 = J4 * cc[3] + J5 * cc[6], b1 = J4 * cc[4] + J5 * cc[7], b2 = J4 * cc[5] + J5 * cc[8];
   float c00 = a0 * J0 + a2 * J2, c01 = a1 * J4 + a2 * J5, c10 = b0 * J0 + b2 * J2, c11 = b1 * J4 + b2 * J5;
   const float mx = (K[0] * tx + K[1] * ty + K[2] * tz) / tz, my = (K[3] * tx + K[4] * ty + K[5] * tz) / tz;
-  c00 += 0.3f; c11 += 0.3f;  // eps2d
+  const float det_orig = c00 * c11 - c01 * c10;   // before the blur: the numerator of the antialiased compensation
+  c00 += eps2d; c11 += eps2d;
   float det = c00 * c11 - c01 * c10;
   det = fmaxf(det, 1e-10f);
+  // antialiased (_torch_impl.py:329-344): comp = sqrt(max(det(cov2d) / det(cov2d + eps2d I), 0)), det the clamped one
+  const float comp = antialiased ? sqrtf(fmaxf(det_orig / det, 0.f)) : 1.0f;
   G2D o;
   o.mx = mx; o.my = my;
   o.ca = c11 / det; o.cb = -(c01 + c10) / 2.0f / det; o.cc = c00 / det;
@@ -91,6 +96,9 @@ __global__ __launch_bounds__(256) void raster_project_kernel(const float* __rest
   float rx = ceilf(3.33f * sqrtf(c00)), ry = ceilf(3.33f * sqrtf(c11));
   const bool valid = det > 0.f && tz > near_plane && tz < far_plane;
   if (!valid) { rx = 0.f; ry = 0.f; }
+  // radius_clip (gsplat's ProjectionEWA3DGSFused.cu; the torch projection has no such rule): a pair whose two radii are both at most
+  // radius_clip pixels is culled.  Radii are at least 1 where they are not 0, so radius_clip = 0 culls nothing more.
+  if (radius_clip > 0.f && rx <= radius_clip && ry <= radius_clip) { rx = 0.f; ry = 0.f; }
   const bool inside = mx + rx > 0.f && mx - rx < (float)width && my + ry > 0.f && my - ry < (float)height;
   if (!inside) { rx = 0.f; ry = 0.f; }
   if (!(rx == rx) || !(ry == ry) || isinf(rx) || isinf(ry)) { rx = 0.f; ry = 0.f; }
@@ -107,8 +115,8 @@ __global__ __launch_bounds__(256) void raster_project_kernel(const float* __rest
   }
   o.rect = x0 | (y0 << 8) | (x1 << 16) | (y1 << 24);
   const float4 col = rgb[g];
-  o.opacity = opac[g]; o.r = col.x; o.g = col.y; o.b = col.z;
-  o.pad = 0;
+  o.opacity = antialiased ? opac[g] * comp : opac[g]; o.r = col.x; o.g = col.y; o.b = col.z;
+  o.pad = antialiased ? __float_as_int(comp) : 0;   // the backward reads the compensation back instead of recomputing it
   const size_t idx = (size_t)c * N + g;
   g2d[idx] = o;
   counts[idx] = cnt;
@@ -163,12 +171,15 @@ __global__ __launch_bounds__(256) void raster_offsets_kernel(const unsigned long
 // quadrant (finer skip / stop granularity, four times the scalar traffic).  Blending rules of the reference's forward
 // (csrc/RasterizeToPixels3DGSFwd.cu:118-184): a Gaussian is skipped for a pixel when its exponent is negative or its alpha below
 // 1/255; alpha is capped at 0.999; a pixel whose transmittance would fall to 1e-4 stops BEFORE blending that Gaussian; expected
-// depth = sum(depth * weight) / alpha (rendering.py:984-992).
+// depth = sum(depth * weight) / alpha (rendering.py:984-992).  Epilogue options (wave-uniform, nothing of them inside the list walk):
+// depth_mode 1 writes the accumulated depth sum(depth * weight) as it is; backgrounds [C,3] adds bg[cam] (1 - alpha) to the colour
+// channels only (rendering.py:926-939).
 template <int PX, int PY>
 __global__ __launch_bounds__(256 / (PX * PY)) void raster_composite_kernel(const G2D* __restrict__ g2d, const unsigned int* __restrict__ vals,
                                                                          const unsigned int* __restrict__ offs, int tw, int th, int width,
                                                                          int height, float* __restrict__ out_rgb, float* __restrict__ out_depth,
-                                                                         float* __restrict__ out_alpha) {
+                                                                         float* __restrict__ out_alpha, const float* __restrict__ backgrounds,
+                                                                         int depth_mode) {
   constexpr int NP = PX * PY;               // pixels per lane
   const int tile = blockIdx.x, cam = blockIdx.y;
   const int ty = tile / tw, tx = tile - ty * tw;
@@ -189,6 +200,8 @@ __global__ __launch_bounds__(256 / (PX * PY)) void raster_composite_kernel(const
   unsigned int k = offs[cam * tw * th + tile];
   const unsigned int end = offs[cam * tw * th + tile + 1];
   if (__builtin_amdgcn_ballot_w64(any_open) == 0ull) return;   // a region outside the image (wave-uniform)
+  float bgr = 0.f, bgg = 0.f, bgb = 0.f;
+  if (backgrounds) { bgr = backgrounds[3 * cam]; bgg = backgrounds[3 * cam + 1]; bgb = backgrounds[3 * cam + 2]; }
   if (k < end) {
     // Two-deep scalar pipeline over two register sets: while step k is blended, the record of step k + 1 is in flight together with
     // the list entry its set will need next (two steps ahead).  The requests are asm statements because the compiler sinks a plain
@@ -255,8 +268,9 @@ __global__ __launch_bounds__(256 / (PX * PY)) void raster_composite_kernel(const
     if (i < height && j < width) {
       const size_t pix = ((size_t)cam * height + i) * width + j;
       const float al = 1.0f - T[q];
+      if (backgrounds) { const float rest = 1.0f - al; r[q] = fmaf(bgr, rest, r[q]); g[q] = fmaf(bgg, rest, g[q]); b[q] = fmaf(bgb, rest, b[q]); }
       out_rgb[3 * pix] = r[q]; out_rgb[3 * pix + 1] = g[q]; out_rgb[3 * pix + 2] = b[q];
-      out_depth[pix] = d[q] / fmaxf(al, 1e-10f);
+      out_depth[pix] = depth_mode ? d[q] : d[q] / fmaxf(al, 1e-10f);
       out_alpha[pix] = al;
     }
   }
@@ -297,6 +311,7 @@ size_t wm_raster_workspace_bytes(int N, int C, int width, int height, size_t max
 hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned long long* n_isects_out) {
   const int tw = (a.width + TILE - 1) / TILE, th = (a.height + TILE - 1) / TILE, tiles = tw * th;
   if (a.N <= 0 || a.C <= 0 || tw > 255 || th > 255) return hipErrorInvalidValue;
+  if (!wm_raster_options_valid(a)) return hipErrorInvalidValue;
   const size_t N = a.N, C = a.C, CN = N * C;
   if (CN >= (1ull << 31)) return hipErrorInvalidValue;
   RasterWs w = carve((char*)a.workspace, N, C, tiles, a.max_isects);
@@ -313,7 +328,7 @@ hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned lo
     hipLaunchKernelGGL(raster_color_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.colors, a.N, a.is_sh, w.rgb);
   }
   hipLaunchKernelGGL(raster_project_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)C), dim3(256), 0, s, a.means, a.quats, a.scales, a.viewmats,
-                     a.Ks, a.N, a.C, a.width, a.height, 0.01f, 1e10f, a.opacities, w.rgb, w.g2d, w.counts, a.radii_out);
+                     a.Ks, a.N, a.C, a.width, a.height, a.near_plane, a.far_plane, a.eps2d, a.radius_clip, a.antialiased, a.opacities, w.rgb, w.g2d, w.counts, a.radii_out);
   if (a.sh_degree > 0) launch_sh_colors(a, w.g2d, s);
   hipError_t e = hipMemsetAsync(w.counts + CN, 0, 8, s);
   if (e != hipSuccess) return e;
@@ -347,12 +362,12 @@ hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned lo
   const int ppl = forced_ppl ? forced_ppl : ((long)tiles * C >= 8192 ? 4 : 2);
   if (ppl == 1)
     hipLaunchKernelGGL((raster_composite_kernel<1, 1>), dim3((unsigned)tiles, (unsigned)C), dim3(256), 0, s, w.g2d, sorted_vals, w.tile_offs, tw, th, a.width,
-                       a.height, a.out_rgb, a.out_depth, a.out_alpha);
+                       a.height, a.out_rgb, a.out_depth, a.out_alpha, a.backgrounds, a.depth_mode);
   else if (ppl == 2)
     hipLaunchKernelGGL((raster_composite_kernel<2, 1>), dim3((unsigned)tiles, (unsigned)C), dim3(128), 0, s, w.g2d, sorted_vals, w.tile_offs, tw, th, a.width,
-                       a.height, a.out_rgb, a.out_depth, a.out_alpha);
+                       a.height, a.out_rgb, a.out_depth, a.out_alpha, a.backgrounds, a.depth_mode);
   else
     hipLaunchKernelGGL((raster_composite_kernel<2, 2>), dim3((unsigned)tiles, (unsigned)C), dim3(64), 0, s, w.g2d, sorted_vals, w.tile_offs, tw, th, a.width,
-                       a.height, a.out_rgb, a.out_depth, a.out_alpha);
+                       a.height, a.out_rgb, a.out_depth, a.out_alpha, a.backgrounds, a.depth_mode);
   return hipGetLastError();
 }

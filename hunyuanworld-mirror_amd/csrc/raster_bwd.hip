@@ -25,6 +25,14 @@
 //   means2d    the pixel-space means the forward's projection left in its records, [C,N,2], zero where culled
 //   SH 1-3     the kernels above run as for given colours (their [N,3] colour gradient goes to a scratch); raster_sh.hip then makes the
 //              coefficient gradient [N,K,3], the direction's share of v_means and v_campos out of the same pair records
+//   options    eps2d is the forward's.  Antialiased: the record's opacity is opacity * comp, comp = sqrt(max(det(M) / det(M + eps2d I), 0)),
+//              M = the 2-D covariance before the blur, so v_opacities = sum over cameras of comp * v_opacity' and v_comp = opacity * v_opacity'
+//              enters v_cov2d through d comp^2 / d M = ((1 - comp^2) adj(M + eps2d I)^T - eps2d I) / det(M + eps2d I) (gsplat's add_blur_vjp,
+//              include/Utils.cuh) times 0.5 / comp.  CHOICE: the exact 0.5 / comp, which is what autograd gives the torch projection — gsplat's
+//              CUDA divides by comp + 1e-6 — and exactly 0 where comp == 0 or where the determinant clamp (det < 1e-10) is active; torch's own
+//              autograd gives NaN at det(M) <= 0, this kernel does not.  Backgrounds and the accumulated-depth mode change the compositing
+//              backward's prologue only (raster_bwd_composite.h); v_backgrounds [C,3] is a reduction of its own over v_rgb and the forward's
+//              out_alpha, which is READ here, not recomputed: fp32 terms, fp64 partials per 4096-pixel chunk, chunks added in a fixed order.
 // Sums run in a fixed order everywhere, so gradients are bitwise reproducible run to run.
 #include "wm_common.h"
 #include "wm_kernels.h"
@@ -58,7 +66,8 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
                                                                  float* __restrict__ v_means, float* __restrict__ v_quats, float* __restrict__ v_scales,
                                                                  float* __restrict__ v_opac, float* __restrict__ v_colors,
                                                                  float* __restrict__ v_means2d, float* __restrict__ v_means2d_abs,
-                                                                 double* __restrict__ cam_part) {
+                                                                 double* __restrict__ cam_part, const float* __restrict__ opac, float eps2d,
+                                                                 int antialiased) {
   int g = blockIdx.x * 256 + threadIdx.x;
   bool live = true;
   if constexpr (CAM) {
@@ -117,7 +126,11 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
         if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = p[10]; v_means2d_abs[2 * idx + 1] = p[11]; }
       }
       const float v_mx = p[0], v_my = p[1], v_ca = p[2], v_cb = p[3], v_cc = p[4];
-      a_op += p[5]; a_col[0] += p[6]; a_col[1] += p[7]; a_col[2] += p[8];
+      // antialiased: the pair's opacity was opac[g] * comp (comp read back from the record the forward's projection wrote):
+      // v_opacities += comp * v_opacity', v_comp = opac[g] * v_opacity' goes on into the 2-D covariance below
+      const float comp = antialiased ? __int_as_float(g2d[idx].pad) : 1.0f;
+      a_op += antialiased ? comp * p[5] : p[5];
+      a_col[0] += p[6]; a_col[1] += p[7]; a_col[2] += p[8];
       // forward, as raster_project_kernel
       const float* V = viewmats + 16 * c;
       const float Rv[9] = {V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
@@ -145,7 +158,7 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
       const float J0 = fx * rz, J2 = -fx * u * rz, J4 = fy * rz, J5 = -fy * w * rz;   // J = [[J0 0 J2] [0 J4 J5]]
       const float a0 = J0 * S[0] + J2 * S[6], a1 = J0 * S[1] + J2 * S[7], a2 = J0 * S[2] + J2 * S[8];   // A = J S (2 x 3)
       const float b0 = J4 * S[3] + J5 * S[6], b1 = J4 * S[4] + J5 * S[7], b2 = J4 * S[5] + J5 * S[8];
-      const float c00 = a0 * J0 + a2 * J2 + 0.3f, c01 = a1 * J4 + a2 * J5, c10 = b0 * J0 + b2 * J2, c11 = b1 * J4 + b2 * J5 + 0.3f;
+      const float c00 = a0 * J0 + a2 * J2 + eps2d, c01 = a1 * J4 + a2 * J5, c10 = b0 * J0 + b2 * J2, c11 = b1 * J4 + b2 * J5 + eps2d;
       const float det_raw = c00 * c11 - c01 * c10;
       const float det = fmaxf(det_raw, 1e-10f), rdet = 1.0f / det;
       const float ka = c11 * rdet, kb = -(c01 + c10) * 0.5f * rdet, kc = c00 * rdet;
@@ -154,6 +167,11 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
       if (det_raw >= 1e-10f) {
         const float v_det = -(v_ca * ka + v_cb * kb + v_cc * kc) * rdet;
         g00 += v_det * c11; g11 += v_det * c00; g01 -= v_det * c10; g10 -= v_det * c01;
+        if (antialiased && comp > 0.f) {   // comp^2 = det(M) / det(M + eps2d I), M = cov2d before the blur (derivation: header)
+          const float vsc = opac[g] * p[5] * 0.5f / comp, rest = 1.0f - comp * comp;
+          g00 += vsc * (rest * c11 - eps2d) * rdet; g11 += vsc * (rest * c00 - eps2d) * rdet;
+          g01 -= vsc * rest * c10 * rdet; g10 -= vsc * rest * c01 * rdet;
+        }
       }
       // cov2d = J S J^T:  v_S = J^T G J,  v_J = G J S^T + G^T J S
       const float Jm[6] = {J0, 0.f, J2, 0.f, J4, J5};
@@ -264,6 +282,51 @@ __global__ __launch_bounds__(256) void raster_cam_reduce_kernel(const double* __
   if (comp == 0 && t < 4) v_viewmats[16 * c + 12 + t] = 0.f;
 }
 
+// v_backgrounds [C,3] = sum over the camera's pixels of v_rgb (1 - alpha), alpha READ from the forward's out_alpha (not recomputed).
+// Stage 1: a block takes BG_CHUNK consecutive pixels of one camera, thread t those at t, t + 256, ... in order; every term is formed in
+// fp32, added in fp64, the 256 thread sums go pairwise through a fixed tree -> bg_part [C][3][chunks].  Stage 2 (raster_bg_reduce_kernel)
+// adds the chunks' partials in the order of raster_cam_reduce_kernel and rounds to fp32 once.
+constexpr int BG_CHUNK = 4096;
+__global__ __launch_bounds__(256) void raster_bg_partial_kernel(const float* __restrict__ v_rgb, const float* __restrict__ out_alpha, size_t pixels,
+                                                                size_t chunks, double* __restrict__ bg_part) {
+  __shared__ double sh[3][256];
+  const size_t chunk = blockIdx.x, c = blockIdx.y;
+  const int t = threadIdx.x;
+  const size_t lo = chunk * BG_CHUNK, hi = lo + BG_CHUNK < pixels ? lo + BG_CHUNK : pixels;
+  double acc[3] = {0.0, 0.0, 0.0};
+  for (size_t i = lo + t; i < hi; i += 256) {
+    const size_t pix = c * pixels + i;
+    const float rest = 1.0f - out_alpha[pix];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) acc[j] += (double)(v_rgb[3 * pix + j] * rest);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) sh[j][t] = acc[j];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) sh[j][t] += sh[j][t + o];
+    }
+    __syncthreads();
+  }
+  if (t < 3) bg_part[(c * 3 + t) * chunks + chunk] = sh[t][0];
+}
+__global__ __launch_bounds__(256) void raster_bg_reduce_kernel(const double* __restrict__ bg_part, size_t chunks, float* __restrict__ v_backgrounds) {
+  __shared__ double sh[256];
+  const int comp = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
+  const double* part = bg_part + ((size_t)c * 3 + comp) * chunks;
+  double acc = 0.0;
+  for (size_t w = t; w < chunks; w += 256) acc += part[w];
+  sh[t] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) sh[t] += sh[t + o];
+    __syncthreads();
+  }
+  if (t == 0) v_backgrounds[3 * c + comp] = (float)sh[0];
+}
+
 // the forward's pixel-space means out of its projection records; zero where the camera culled the Gaussian (a radius of 0)
 __global__ __launch_bounds__(256) void raster_means2d_kernel(const G2D* __restrict__ g2d, const int* __restrict__ radii, size_t CN,
                                                              float* __restrict__ means2d) {
@@ -284,28 +347,29 @@ void launch_bwd_kernels(const WmRasterBwdArgs& b, const RasterWs& w, unsigned in
     const dim3 grid((unsigned)(tw * th), (unsigned)C);
     if constexpr (REC == PAIR_REC_ABS)
       wm_launch_composite_bwd_abs(grid, s, w.g2d, w.vals[0], w.vals[1], flag, w.tile_offs, w.offsets, tw, th, a.width, a.height, b.out_depth, b.v_rgb,
-                                  b.v_depth, b.v_alpha, pair_grad);
+                                  b.v_depth, b.v_alpha, pair_grad, a.backgrounds, a.depth_mode);
     else
       hipLaunchKernelGGL(raster_composite_bwd_kernel<PAIR_REC>, grid, dim3(64), 0, s, w.g2d, w.vals[0], w.vals[1], flag, w.tile_offs, w.offsets, tw,
-                         th, a.width, a.height, b.out_depth, b.v_rgb, b.v_depth, b.v_alpha, pair_grad);
+                         th, a.width, a.height, b.out_depth, b.v_rgb, b.v_depth, b.v_alpha, pair_grad, a.backgrounds, a.depth_mode);
   }
   hipLaunchKernelGGL((raster_project_bwd_kernel<REC, M2D, CAM>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.means, a.quats, a.scales, a.colors,
                      a.is_sh, a.viewmats, a.Ks, a.N, a.C, a.width, a.height, w.g2d, w.offsets, pair_grad, b.v_means, b.v_quats, b.v_scales,
-                     b.v_opacities, b.v_colors, b.v_means2d, b.v_means2d_abs, cam_part);
+                     b.v_opacities, b.v_colors, b.v_means2d, b.v_means2d_abs, cam_part, a.opacities, a.eps2d, a.antialiased);
   if constexpr (CAM)
     hipLaunchKernelGGL(raster_cam_reduce_kernel, dim3(12, (unsigned)C), dim3(256), 0, s, cam_part, (N + 63) / 64, b.v_viewmats);
 }
 
 }  // namespace
 
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad, int cam, int sh, int campos) {
-  (void)width; (void)height;
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad, int cam, int sh, int campos, int bg) {
   const size_t base = align256(256) + align256(n_isects * (absgrad ? PAIR_REC_ABS : PAIR_REC) * sizeof(float));   // buffer flag | pair records
   size_t total = base;
   if (N <= 0 || C <= 0) return total;
   if (cam) total += align256((size_t)C * 12 * (((size_t)N + 63) / 64) * sizeof(double));   // | per-wave viewmats partials [C][12][waves]
   if (sh) total += align256((size_t)N * 3 * sizeof(float));                                 // | SH: the geometric pass's colour gradient (unused)
   if (sh && campos) total += sh_campos_part_bytes(N, C);                                    // | SH: per-wave campos partials [C][3][waves]
+  if (bg && width > 0 && height > 0)                                                        // | backgrounds: per-chunk partials [C][3][chunks]
+    total += align256((size_t)C * 3 * (((size_t)width * height + BG_CHUNK - 1) / BG_CHUNK) * sizeof(double));
   return total;
 }
 
@@ -331,8 +395,17 @@ hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s) {
   if (w.total > a.workspace_bytes) return hipErrorInvalidValue;
   const int cam = b.v_viewmats ? 1 : 0, sh = a.sh_degree > 0 ? 1 : 0;
   if (sh ? !sh_args_valid(a) : b.v_campos != nullptr) return hipErrorInvalidValue;
-  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam, sh, b.v_campos ? 1 : 0) > b.grad_workspace_bytes)
+  if (!wm_raster_options_valid(a) || (b.v_backgrounds && (!a.backgrounds || !b.out_alpha))) return hipErrorInvalidValue;
+  if (wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam, sh, b.v_campos ? 1 : 0, b.v_backgrounds ? 1 : 0) >
+      b.grad_workspace_bytes)
     return hipErrorInvalidValue;
+  if (b.v_backgrounds) {   // independent of the splat gradients: its partials lie behind everything else in the workspace
+    double* bg_part = (double*)((char*)b.grad_workspace + wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam, sh,
+                                                                                      b.v_campos ? 1 : 0));
+    const size_t pixels = (size_t)a.width * a.height, chunks = (pixels + BG_CHUNK - 1) / BG_CHUNK;
+    hipLaunchKernelGGL(raster_bg_partial_kernel, dim3((unsigned)chunks, (unsigned)C), dim3(256), 0, s, b.v_rgb, b.out_alpha, pixels, chunks, bg_part);
+    hipLaunchKernelGGL(raster_bg_reduce_kernel, dim3(3, (unsigned)C), dim3(256), 0, s, bg_part, chunks, b.v_backgrounds);
+  }
   const int rec = b.absgrad ? PAIR_REC_ABS : PAIR_REC;
   unsigned int* flag = (unsigned int*)b.grad_workspace;
   float* pair_grad = (float*)((char*)b.grad_workspace + align256(256));
@@ -342,7 +415,7 @@ hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s) {
     // workspace; then raster_sh.hip turns the pairs' colour terms into v_colors [N,K,3], its share of v_means and v_campos
     char* sh_ws = (char*)b.grad_workspace + wm_raster_bwd_workspace_bytes(a.N, a.C, a.width, a.height, b.n_isects, b.absgrad, cam);
     WmRasterBwdArgs geo = b;
-    geo.fwd.sh_degree = 0; geo.fwd.is_sh = 0; geo.v_campos = nullptr;
+    geo.fwd.sh_degree = 0; geo.fwd.is_sh = 0; geo.v_campos = nullptr; geo.v_backgrounds = nullptr;
     geo.v_colors = (float*)sh_ws;
     geo.grad_workspace_bytes = (size_t)(sh_ws - (char*)b.grad_workspace);
     const hipError_t e = wm_launch_rasterize_bwd(geo, s);

@@ -52,7 +52,8 @@ __global__ __launch_bounds__(64) void raster_composite_bwd_kernel(const G2D* __r
                                               const unsigned int* __restrict__ offs, const unsigned long long* __restrict__ pair_offs,
                                               int tw, int th, int width, int height, const float* __restrict__ out_depth,
                                               const float* __restrict__ v_rgb, const float* __restrict__ v_depth,
-                                              const float* __restrict__ v_alpha, float* __restrict__ pair_grad) {
+                                              const float* __restrict__ v_alpha, float* __restrict__ pair_grad,
+                                              const float* __restrict__ backgrounds, int depth_mode) {
   constexpr int PX = 2, PY = 2, NP = 4;
   const int tile = blockIdx.x, cam = blockIdx.y;
   const int ty = tile / tw, tx = tile - ty * tw;
@@ -96,7 +97,11 @@ __global__ __launch_bounds__(64) void raster_composite_bwd_kernel(const G2D* __r
     if (__builtin_amdgcn_ballot_w64(still) == 0ull) { ++k; break; }
   }
   const unsigned int walked = k;   // entries [begin, walked) were looked at by the forward
-  // ---- cotangents of the four composited channels and of alpha; the expected-depth division D / max(alpha, 1e-10) is undone here
+  // ---- cotangents of the four composited channels and of alpha; the expected-depth division D / max(alpha, 1e-10) is undone here.
+  // Prologue options (wave-uniform, as the forward's epilogue): depth_mode 1 (accumulated depth): the depth cotangent is that of D
+  // itself and alpha's has no depth term; backgrounds [C,3]: rgb = composited + bg (1 - alpha) gives alpha's cotangent - v_rgb . bg[cam].
+  float bgr = 0.f, bgg = 0.f, bgb = 0.f;
+  if (backgrounds) { bgr = backgrounds[3 * cam]; bgg = backgrounds[3 * cam + 1]; bgb = backgrounds[3 * cam + 2]; }
   float vr[NP], vg[NP], vb[NP], vd[NP], tfv[NP], br[NP], bg[NP], bb[NP], bd[NP];
 #pragma unroll
   for (int q = 0; q < NP; ++q) {
@@ -109,8 +114,10 @@ __global__ __launch_bounds__(64) void raster_composite_bwd_kernel(const G2D* __r
       const float inv = 1.0f / fmaxf(al, 1e-10f);
       const float ved = v_depth[pix];
       vr[q] = v_rgb[3 * pix]; vg[q] = v_rgb[3 * pix + 1]; vb[q] = v_rgb[3 * pix + 2];
-      vd[q] = ved * inv;
-      const float val = v_alpha[pix] - (al > 1e-10f ? ved * out_depth[pix] * inv : 0.f);
+      vd[q] = depth_mode ? ved : ved * inv;
+      float val = v_alpha[pix];
+      if (!depth_mode) val -= al > 1e-10f ? ved * out_depth[pix] * inv : 0.f;
+      if (backgrounds) val -= vr[q] * bgr + vg[q] * bgg + vb[q] * bgb;
       tfv[q] = T[q] * val;
     }
   }
@@ -174,4 +181,5 @@ __global__ __launch_bounds__(64) void raster_composite_bwd_kernel(const G2D* __r
 // the 12-float instantiation (raster_bwd_abs.hip): same grid, block and arguments as the 10-float launch in raster_bwd.hip
 void wm_launch_composite_bwd_abs(dim3 grid, hipStream_t s, const wm_raster::G2D* g2d, const unsigned int* vals0, const unsigned int* vals1,
                                  const unsigned int* which, const unsigned int* offs, const unsigned long long* pair_offs, int tw, int th, int width,
-                                 int height, const float* out_depth, const float* v_rgb, const float* v_depth, const float* v_alpha, float* pair_grad);
+                                 int height, const float* out_depth, const float* v_rgb, const float* v_depth, const float* v_alpha, float* pair_grad,
+                                 const float* backgrounds, int depth_mode);

@@ -265,7 +265,20 @@ struct WmRasterArgs {
   float* out_rgb; float* out_depth; float* out_alpha;  // [C,H,W,3] [C,H,W] [C,H,W]
   int* radii_out;                       // optional [C,N,2] (tests)
   void* workspace; size_t workspace_bytes; size_t max_isects;
+  // gsplat.rasterization's options (wm_raster_options of the C ABI); wm_raster_default_options sets what the entries without them render
+  int antialiased;                      // 1: opacity * sqrt(max(det(cov2d) / det(cov2d + eps2d I), 0)) (rasterize_mode "antialiased")
+  int depth_mode;                       // 0: expected depth D / max(alpha, 1e-10); 1: accumulated depth D
+  float eps2d, near_plane, far_plane, radius_clip;
+  const float* backgrounds;             // optional [C,3]: rgb += backgrounds[c] (1 - alpha)
 };
+inline void wm_raster_default_options(WmRasterArgs& a) {
+  a.antialiased = 0; a.depth_mode = 0; a.eps2d = 0.3f; a.near_plane = 0.01f; a.far_plane = 1e10f; a.radius_clip = 0.f; a.backgrounds = nullptr;
+}
+// the one check of the options (negated comparisons, so that a NaN is invalid too); the C ABI entries and both launchers call it
+inline bool wm_raster_options_valid(const WmRasterArgs& a) {
+  return (a.antialiased == 0 || a.antialiased == 1) && (a.depth_mode == 0 || a.depth_mode == 1) && a.eps2d >= 0.f && a.near_plane < a.far_plane &&
+         a.radius_clip >= 0.f;
+}
 size_t wm_raster_workspace_bytes(int N, int C, int width, int height, size_t max_isects);
 hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned long long* n_isects_out);
 // backward (raster_bwd.hip): fwd = the arguments of the forward call whose workspace is still as that call left it (outputs unused)
@@ -282,9 +295,12 @@ struct WmRasterBwdArgs {
   float* v_viewmats;
   // optional, with fwd.sh_degree > 0 only (then v_colors is [N,n_coeffs,3]): gradient of campos [C,3], the colour's camera term
   float* v_campos;
+  // optional, with fwd.backgrounds: gradient of the backgrounds [C,3]; reads out_alpha [C,H,W], the forward's alpha (bg = 1 workspace)
+  float* v_backgrounds; const float* out_alpha;
 };
-// sh = 1: a backward of an SH degree 1-3 forward; campos = 1: with v_campos
-size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad = 0, int cam = 0, int sh = 0, int campos = 0);
+// sh = 1: a backward of an SH degree 1-3 forward; campos = 1: with v_campos; bg = 1: with v_backgrounds
+size_t wm_raster_bwd_workspace_bytes(int N, int C, int width, int height, size_t n_isects, int absgrad = 0, int cam = 0, int sh = 0, int campos = 0,
+                                     int bg = 0);
 hipError_t wm_launch_rasterize_bwd(const WmRasterBwdArgs& b, hipStream_t s);
 // the pixel-space means of the forward whose workspace this is, [C,N,2], zero where radii [C,N,2] has a 0
 hipError_t wm_launch_rasterize_means2d(const void* workspace, size_t workspace_bytes, int N, int C, int width, int height, size_t max_isects,

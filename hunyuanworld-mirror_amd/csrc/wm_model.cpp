@@ -1981,17 +1981,37 @@ extern "C" wm_status wm_prune_gs(const float* means, const float* quats, const f
 extern "C" size_t wm_rasterize_workspace_bytes(int n_gaussians, int n_cameras, int width, int height, size_t max_isects) {
   return wm_raster_workspace_bytes(n_gaussians, n_cameras, width, height, max_isects);
 }
-extern "C" wm_status wm_rasterize_splats(const float* means, const float* quats, const float* scales, const float* opacities,
-                                         const float* colors, int colors_are_sh0, int n_gaussians, const float* viewmats, const float* Ks,
-                                         int n_cameras, int width, int height, float* out_rgb, float* out_depth, float* out_alpha,
-                                         int* radii_out, void* workspace, size_t workspace_bytes, size_t max_isects,
-                                         unsigned long long* n_isects, void* stream) {
+// ---- the rasteriser's entries: wm_rasterize_splats_opt / wm_rasterize_splats_backward_opt do everything; the entries without options are
+// thin wrappers that keep their own argument checks and pass default options (null)
+static bool raster_fill(WmRasterArgs& a, const float* means, const float* quats, const float* scales, const float* opacities, const float* colors,
+                        int colors_are_sh0, int n_coeffs, int sh_degree, const float* campos, int n_gaussians, const float* viewmats,
+                        const float* Ks, int n_cameras, int width, int height, const wm_raster_options* opt) {
+  memset(&a, 0, sizeof(a));
+  wm_raster_default_options(a);
+  if (opt) {
+    a.antialiased = opt->antialiased; a.depth_mode = opt->depth_mode; a.eps2d = opt->eps2d; a.near_plane = opt->near_plane;
+    a.far_plane = opt->far_plane; a.radius_clip = opt->radius_clip; a.backgrounds = opt->backgrounds;
+  }
+  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = colors;
+  if (sh_degree == 0) a.is_sh = colors_are_sh0;
+  else { a.sh_degree = sh_degree; a.n_coeffs = n_coeffs; a.campos = campos; }
+  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
+  // checked here, in front of the first HIP call
+  if (sh_degree < 0 || sh_degree > 3 || (sh_degree > 0 && ((sh_degree + 1) * (sh_degree + 1) > n_coeffs || !campos))) return false;
+  return wm_raster_options_valid(a);
+}
+extern "C" wm_status wm_rasterize_splats_opt(const float* means, const float* quats, const float* scales, const float* opacities,
+                                             const float* colors, int colors_are_sh0, int n_coeffs, int sh_degree, const float* campos,
+                                             int n_gaussians, const float* viewmats, const float* Ks, int n_cameras, int width, int height,
+                                             const wm_raster_options* options, float* out_rgb, float* out_depth, float* out_alpha,
+                                             int* radii_out, void* workspace, size_t workspace_bytes, size_t max_isects,
+                                             unsigned long long* n_isects, void* stream) {
   if (!means || !quats || !scales || !opacities || !colors || !viewmats || !Ks || !out_rgb || !out_depth || !out_alpha || !workspace)
     return WM_ERR_INVALID;
   WmRasterArgs a;
-  memset(&a, 0, sizeof(a));
-  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = colors; a.is_sh = colors_are_sh0;
-  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
+  if (!raster_fill(a, means, quats, scales, opacities, colors, colors_are_sh0, n_coeffs, sh_degree, campos, n_gaussians, viewmats, Ks, n_cameras,
+                   width, height, options))
+    return WM_ERR_INVALID;
   a.out_rgb = out_rgb; a.out_depth = out_depth; a.out_alpha = out_alpha; a.radii_out = radii_out;
   a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
   unsigned long long n = 0;
@@ -2000,6 +2020,53 @@ extern "C" wm_status wm_rasterize_splats(const float* means, const float* quats,
   if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
   if (e != hipSuccess) return WM_ERR_HIP;
   return n > max_isects ? WM_ERR_STATE : WM_OK;  // WM_ERR_STATE: the workspace is too small for *n_isects pairs, nothing was rendered
+}
+extern "C" size_t wm_rasterize_backward_workspace_bytes_opt(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad,
+                                                            int want_viewmats, int sh_degree, int want_campos, int want_backgrounds) {
+  return wm_raster_bwd_workspace_bytes(n_gaussians, n_cameras, width, height, n_isects, want_absgrad ? 1 : 0, want_viewmats ? 1 : 0,
+                                       sh_degree > 0 ? 1 : 0, sh_degree > 0 && want_campos ? 1 : 0, want_backgrounds ? 1 : 0);
+}
+extern "C" wm_status wm_rasterize_splats_backward_opt(const float* means, const float* quats, const float* scales, const float* opacities,
+                                                      const float* colors, int colors_are_sh0, int n_coeffs, int sh_degree, const float* campos,
+                                                      int n_gaussians, const float* viewmats, const float* Ks, int n_cameras, int width,
+                                                      int height, const wm_raster_options* options, const void* workspace,
+                                                      size_t workspace_bytes, size_t max_isects, size_t n_isects, const float* out_rgb,
+                                                      const float* out_depth, const float* out_alpha, const float* v_rgb, const float* v_depth,
+                                                      const float* v_alpha, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
+                                                      float* v_colors, float* v_means2d, float* v_means2d_abs, int want_absgrad,
+                                                      float* v_viewmats, float* v_campos, float* v_backgrounds, void* grad_workspace,
+                                                      size_t grad_workspace_bytes, void* stream) {
+  (void)out_rgb;   // the kernels rebuild the transmittance themselves; the expected depth is read back, and out_alpha for v_backgrounds only
+  if (!means || !quats || !scales || !opacities || !colors || !viewmats || !Ks || !workspace || !out_depth || !v_rgb || !v_depth || !v_alpha ||
+      !v_means || !v_quats || !v_scales || !v_opacities || !v_colors || !grad_workspace)
+    return WM_ERR_INVALID;
+  if (want_absgrad && (!v_means2d || !v_means2d_abs)) return WM_ERR_INVALID;
+  if (v_backgrounds && (!options || !options->backgrounds || !out_alpha)) return WM_ERR_INVALID;
+  if (v_campos && sh_degree <= 0) return WM_ERR_INVALID;
+  WmRasterBwdArgs b;
+  memset(&b, 0, sizeof(b));
+  if (!raster_fill(b.fwd, means, quats, scales, opacities, colors, colors_are_sh0, n_coeffs, sh_degree, campos, n_gaussians, viewmats, Ks,
+                   n_cameras, width, height, options))
+    return WM_ERR_INVALID;
+  if (n_isects > max_isects) return WM_ERR_STATE;   // that forward rendered nothing: there is no state to differentiate
+  WmRasterArgs& a = b.fwd;
+  a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
+  b.n_isects = n_isects; b.out_depth = out_depth; b.out_alpha = out_alpha; b.v_rgb = v_rgb; b.v_depth = v_depth; b.v_alpha = v_alpha;
+  b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_opacities = v_opacities; b.v_colors = v_colors;
+  b.v_means2d = v_means2d; b.v_means2d_abs = want_absgrad ? v_means2d_abs : nullptr; b.absgrad = want_absgrad ? 1 : 0;
+  b.v_viewmats = v_viewmats; b.v_campos = v_campos; b.v_backgrounds = v_backgrounds;
+  b.grad_workspace = grad_workspace; b.grad_workspace_bytes = grad_workspace_bytes;
+  const hipError_t e = wm_launch_rasterize_bwd(b, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
+  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+}
+extern "C" wm_status wm_rasterize_splats(const float* means, const float* quats, const float* scales, const float* opacities,
+                                         const float* colors, int colors_are_sh0, int n_gaussians, const float* viewmats, const float* Ks,
+                                         int n_cameras, int width, int height, float* out_rgb, float* out_depth, float* out_alpha,
+                                         int* radii_out, void* workspace, size_t workspace_bytes, size_t max_isects,
+                                         unsigned long long* n_isects, void* stream) {
+  return wm_rasterize_splats_opt(means, quats, scales, opacities, colors, colors_are_sh0, 0, 0, nullptr, n_gaussians, viewmats, Ks, n_cameras, width,
+                                 height, nullptr, out_rgb, out_depth, out_alpha, radii_out, workspace, workspace_bytes, max_isects, n_isects, stream);
 }
 extern "C" size_t wm_rasterize_backward_workspace_bytes(int n_gaussians, int n_cameras, int width, int height, size_t n_isects) {
   return wm_raster_bwd_workspace_bytes(n_gaussians, n_cameras, width, height, n_isects);
@@ -2011,23 +2078,10 @@ extern "C" wm_status wm_rasterize_splats_backward(const float* means, const floa
                                                   const float* out_alpha, const float* v_rgb, const float* v_depth, const float* v_alpha,
                                                   float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
                                                   void* grad_workspace, size_t grad_workspace_bytes, void* stream) {
-  (void)out_rgb; (void)out_alpha;   // the kernels rebuild the transmittance themselves; only the expected depth is read back
-  if (!means || !quats || !scales || !opacities || !colors || !viewmats || !Ks || !workspace || !out_depth || !v_rgb || !v_depth || !v_alpha ||
-      !v_means || !v_quats || !v_scales || !v_opacities || !v_colors || !grad_workspace)
-    return WM_ERR_INVALID;
-  if (n_isects > max_isects) return WM_ERR_STATE;   // that forward rendered nothing: there is no state to differentiate
-  WmRasterBwdArgs b;
-  memset(&b, 0, sizeof(b));
-  WmRasterArgs& a = b.fwd;
-  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = colors; a.is_sh = colors_are_sh0;
-  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
-  a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
-  b.n_isects = n_isects; b.out_depth = out_depth; b.v_rgb = v_rgb; b.v_depth = v_depth; b.v_alpha = v_alpha;
-  b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_opacities = v_opacities; b.v_colors = v_colors;
-  b.grad_workspace = grad_workspace; b.grad_workspace_bytes = grad_workspace_bytes;
-  const hipError_t e = wm_launch_rasterize_bwd(b, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
-  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+  return wm_rasterize_splats_backward_opt(means, quats, scales, opacities, colors, colors_are_sh0, 0, 0, nullptr, n_gaussians, viewmats, Ks, n_cameras,
+                                          width, height, nullptr, workspace, workspace_bytes, max_isects, n_isects, out_rgb, out_depth, out_alpha, v_rgb,
+                                          v_depth, v_alpha, v_means, v_quats, v_scales, v_opacities, v_colors, nullptr, nullptr, 0, nullptr, nullptr,
+                                          nullptr, grad_workspace, grad_workspace_bytes, stream);
 }
 extern "C" size_t wm_rasterize_backward_workspace_bytes_ex(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad) {
   return wm_raster_bwd_workspace_bytes(n_gaussians, n_cameras, width, height, n_isects, want_absgrad ? 1 : 0);
@@ -2040,25 +2094,10 @@ extern "C" wm_status wm_rasterize_splats_backward_ex(const float* means, const f
                                                      const float* v_alpha, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
                                                      float* v_colors, float* v_means2d, float* v_means2d_abs, int want_absgrad,
                                                      void* grad_workspace, size_t grad_workspace_bytes, void* stream) {
-  (void)out_rgb; (void)out_alpha;
-  if (!means || !quats || !scales || !opacities || !colors || !viewmats || !Ks || !workspace || !out_depth || !v_rgb || !v_depth || !v_alpha ||
-      !v_means || !v_quats || !v_scales || !v_opacities || !v_colors || !grad_workspace)
-    return WM_ERR_INVALID;
-  if (want_absgrad && (!v_means2d || !v_means2d_abs)) return WM_ERR_INVALID;
-  if (n_isects > max_isects) return WM_ERR_STATE;
-  WmRasterBwdArgs b;
-  memset(&b, 0, sizeof(b));
-  WmRasterArgs& a = b.fwd;
-  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = colors; a.is_sh = colors_are_sh0;
-  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
-  a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
-  b.n_isects = n_isects; b.out_depth = out_depth; b.v_rgb = v_rgb; b.v_depth = v_depth; b.v_alpha = v_alpha;
-  b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_opacities = v_opacities; b.v_colors = v_colors;
-  b.v_means2d = v_means2d; b.v_means2d_abs = want_absgrad ? v_means2d_abs : nullptr; b.absgrad = want_absgrad ? 1 : 0;
-  b.grad_workspace = grad_workspace; b.grad_workspace_bytes = grad_workspace_bytes;
-  const hipError_t e = wm_launch_rasterize_bwd(b, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
-  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+  return wm_rasterize_splats_backward_opt(means, quats, scales, opacities, colors, colors_are_sh0, 0, 0, nullptr, n_gaussians, viewmats, Ks, n_cameras,
+                                          width, height, nullptr, workspace, workspace_bytes, max_isects, n_isects, out_rgb, out_depth, out_alpha, v_rgb,
+                                          v_depth, v_alpha, v_means, v_quats, v_scales, v_opacities, v_colors, v_means2d, v_means2d_abs, want_absgrad,
+                                          nullptr, nullptr, nullptr, grad_workspace, grad_workspace_bytes, stream);
 }
 extern "C" size_t wm_rasterize_backward_workspace_bytes_cam(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad) {
   return wm_raster_bwd_workspace_bytes(n_gaussians, n_cameras, width, height, n_isects, want_absgrad ? 1 : 0, 1);
@@ -2071,48 +2110,20 @@ extern "C" wm_status wm_rasterize_splats_backward_cam(const float* means, const 
                                                       const float* v_alpha, float* v_means, float* v_quats, float* v_scales, float* v_opacities,
                                                       float* v_colors, float* v_means2d, float* v_means2d_abs, int want_absgrad,
                                                       float* v_viewmats, void* grad_workspace, size_t grad_workspace_bytes, void* stream) {
-  (void)out_rgb; (void)out_alpha;
-  if (!means || !quats || !scales || !opacities || !colors || !viewmats || !Ks || !workspace || !out_depth || !v_rgb || !v_depth || !v_alpha ||
-      !v_means || !v_quats || !v_scales || !v_opacities || !v_colors || !v_viewmats || !grad_workspace)
-    return WM_ERR_INVALID;
-  if (want_absgrad && (!v_means2d || !v_means2d_abs)) return WM_ERR_INVALID;
-  if (n_isects > max_isects) return WM_ERR_STATE;
-  WmRasterBwdArgs b;
-  memset(&b, 0, sizeof(b));
-  WmRasterArgs& a = b.fwd;
-  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = colors; a.is_sh = colors_are_sh0;
-  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
-  a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
-  b.n_isects = n_isects; b.out_depth = out_depth; b.v_rgb = v_rgb; b.v_depth = v_depth; b.v_alpha = v_alpha;
-  b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_opacities = v_opacities; b.v_colors = v_colors;
-  b.v_means2d = v_means2d; b.v_means2d_abs = want_absgrad ? v_means2d_abs : nullptr; b.absgrad = want_absgrad ? 1 : 0;
-  b.v_viewmats = v_viewmats;
-  b.grad_workspace = grad_workspace; b.grad_workspace_bytes = grad_workspace_bytes;
-  const hipError_t e = wm_launch_rasterize_bwd(b, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
-  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+  if (!v_viewmats) return WM_ERR_INVALID;
+  return wm_rasterize_splats_backward_opt(means, quats, scales, opacities, colors, colors_are_sh0, 0, 0, nullptr, n_gaussians, viewmats, Ks, n_cameras,
+                                          width, height, nullptr, workspace, workspace_bytes, max_isects, n_isects, out_rgb, out_depth, out_alpha, v_rgb,
+                                          v_depth, v_alpha, v_means, v_quats, v_scales, v_opacities, v_colors, v_means2d, v_means2d_abs, want_absgrad,
+                                          v_viewmats, nullptr, nullptr, grad_workspace, grad_workspace_bytes, stream);
 }
 extern "C" wm_status wm_rasterize_splats_sh(const float* means, const float* quats, const float* scales, const float* opacities,
                                             const float* sh_coeffs, int n_coeffs, int sh_degree, const float* campos, int n_gaussians,
                                             const float* viewmats, const float* Ks, int n_cameras, int width, int height, float* out_rgb,
                                             float* out_depth, float* out_alpha, int* radii_out, void* workspace, size_t workspace_bytes,
                                             size_t max_isects, unsigned long long* n_isects, void* stream) {
-  if (!means || !quats || !scales || !opacities || !sh_coeffs || !campos || !viewmats || !Ks || !out_rgb || !out_depth || !out_alpha || !workspace)
-    return WM_ERR_INVALID;
-  if (sh_degree < 1 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > n_coeffs) return WM_ERR_INVALID;
-  WmRasterArgs a;
-  memset(&a, 0, sizeof(a));
-  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = sh_coeffs;
-  a.sh_degree = sh_degree; a.n_coeffs = n_coeffs; a.campos = campos;
-  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
-  a.out_rgb = out_rgb; a.out_depth = out_depth; a.out_alpha = out_alpha; a.radii_out = radii_out;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
-  unsigned long long n = 0;
-  const hipError_t e = wm_launch_rasterize(a, (hipStream_t)stream, &n);
-  if (n_isects) *n_isects = n;
-  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
-  if (e != hipSuccess) return WM_ERR_HIP;
-  return n > max_isects ? WM_ERR_STATE : WM_OK;
+  if (sh_degree < 1) return WM_ERR_INVALID;
+  return wm_rasterize_splats_opt(means, quats, scales, opacities, sh_coeffs, 0, n_coeffs, sh_degree, campos, n_gaussians, viewmats, Ks, n_cameras, width,
+                                 height, nullptr, out_rgb, out_depth, out_alpha, radii_out, workspace, workspace_bytes, max_isects, n_isects, stream);
 }
 extern "C" size_t wm_rasterize_backward_workspace_bytes_sh(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad,
                                                            int want_viewmats, int want_campos) {
@@ -2128,28 +2139,11 @@ extern "C" wm_status wm_rasterize_splats_backward_sh(const float* means, const f
                                                      float* v_opacities, float* v_sh_coeffs, float* v_means2d, float* v_means2d_abs,
                                                      int want_absgrad, float* v_viewmats, float* v_campos, void* grad_workspace,
                                                      size_t grad_workspace_bytes, void* stream) {
-  (void)out_rgb; (void)out_alpha;
-  if (!means || !quats || !scales || !opacities || !sh_coeffs || !campos || !viewmats || !Ks || !workspace || !out_depth || !v_rgb || !v_depth ||
-      !v_alpha || !v_means || !v_quats || !v_scales || !v_opacities || !v_sh_coeffs || !grad_workspace)
-    return WM_ERR_INVALID;
-  if (sh_degree < 1 || sh_degree > 3 || (sh_degree + 1) * (sh_degree + 1) > n_coeffs) return WM_ERR_INVALID;
-  if (want_absgrad && (!v_means2d || !v_means2d_abs)) return WM_ERR_INVALID;
-  if (n_isects > max_isects) return WM_ERR_STATE;
-  WmRasterBwdArgs b;
-  memset(&b, 0, sizeof(b));
-  WmRasterArgs& a = b.fwd;
-  a.means = means; a.quats = quats; a.scales = scales; a.opacities = opacities; a.colors = sh_coeffs;
-  a.sh_degree = sh_degree; a.n_coeffs = n_coeffs; a.campos = campos;
-  a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
-  a.workspace = const_cast<void*>(workspace); a.workspace_bytes = workspace_bytes; a.max_isects = max_isects;
-  b.n_isects = n_isects; b.out_depth = out_depth; b.v_rgb = v_rgb; b.v_depth = v_depth; b.v_alpha = v_alpha;
-  b.v_means = v_means; b.v_quats = v_quats; b.v_scales = v_scales; b.v_opacities = v_opacities; b.v_colors = v_sh_coeffs;
-  b.v_means2d = v_means2d; b.v_means2d_abs = want_absgrad ? v_means2d_abs : nullptr; b.absgrad = want_absgrad ? 1 : 0;
-  b.v_viewmats = v_viewmats; b.v_campos = v_campos;
-  b.grad_workspace = grad_workspace; b.grad_workspace_bytes = grad_workspace_bytes;
-  const hipError_t e = wm_launch_rasterize_bwd(b, (hipStream_t)stream);
-  if (e == hipErrorInvalidValue) return WM_ERR_INVALID;
-  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+  if (sh_degree < 1) return WM_ERR_INVALID;
+  return wm_rasterize_splats_backward_opt(means, quats, scales, opacities, sh_coeffs, 0, n_coeffs, sh_degree, campos, n_gaussians, viewmats, Ks,
+                                          n_cameras, width, height, nullptr, workspace, workspace_bytes, max_isects, n_isects, out_rgb, out_depth,
+                                          out_alpha, v_rgb, v_depth, v_alpha, v_means, v_quats, v_scales, v_opacities, v_sh_coeffs, v_means2d,
+                                          v_means2d_abs, want_absgrad, v_viewmats, v_campos, nullptr, grad_workspace, grad_workspace_bytes, stream);
 }
 extern "C" wm_status wm_rasterize_means2d(const void* workspace, size_t workspace_bytes, int n_gaussians, int n_cameras, int width, int height,
                                           size_t max_isects, const int* radii, float* means2d, void* stream) {

@@ -26,9 +26,20 @@ second graph tensor beside ``viewmats``, so that ``camtoworlds.grad`` is the sum
 (strategy.DefaultStrategy): the projected ``means2d`` as part of the graph, so that ``retain_grad()`` works and ``.grad`` (and,
 with absgrad, the plain attribute ``.absgrad``) is there after ``loss.backward()``, and the per-(camera, Gaussian) ``radii``.
 ``means2d`` receives gradient from the rendered images only; unlike gsplat's, it does not pass gradient on to the splats, so a loss
-computed from ``means2d`` itself raises ``NotImplementedError`` in ``backward()`` rather than being dropped."""
+computed from ``means2d`` itself raises ``NotImplementedError`` in ``backward()`` rather than being dropped.
+
+gsplat's own call: the module-level ``rasterization(...)`` has gsplat.rasterization's signature and ``(render_colors, render_alphas, info)``
+return (gsplat/rendering.py), as the reference's post-3DGS trainer calls it (simple_trainer_worldmirror.py:619-642, :741-752): world-to-camera
+``viewmats`` (differentiable where they require grad), ``render_mode`` "RGB" | "D" | "ED" | "RGB+D" | "RGB+ED", ``rasterize_mode`` "classic" |
+"antialiased", ``near_plane``, ``far_plane``, ``eps2d``, ``radius_clip`` and differentiable ``backgrounds [C,3]``.  These options travel as one
+``wm_raster_options`` struct to ``wm_rasterize_splats_opt`` / ``wm_rasterize_splats_backward_opt``.  ``Rasterizer`` takes
+``rasterization_mode="antialiased"`` and the same keywords except ``render_mode`` (its triple stays rgb, expected depth, alpha, as in the
+reference class); a classic ``Rasterizer`` called with none of them goes through the entries without options, as before — with gsplat's default
+values both routes give the same bits.  What the kernels do not do (packed, sparse_grad, distributed, tile_size != 16, non-pinhole cameras,
+with_ut, with_eval3d, colour channels other than 3, unknown keywords) raises ``NotImplementedError`` naming the argument."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import weakref
 import torch
@@ -45,25 +56,33 @@ class _RasterizeSplats(torch.autograd.Function):
     .backward).  The node owns the forward's workspace: a later rasterize_splats call cannot disturb it before .backward()."""
 
     @staticmethod
-    def forward(ctx, rz, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats, campos, sh_degree):
+    def forward(ctx, rz, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats, campos, sh_degree, opts,
+                backgrounds):
         # viewmats: None, or with camera_grad inv(camtoworlds) as a graph tensor: the input that receives the camera gradient;
         # campos: None, or with camera_grad and sh_degree > 0 the camera positions as a graph tensor: receives the colour's camera term
+        # opts: None (today's entries) or the _Opts of the _opt entries; backgrounds: None or [C,3], receives its gradient
         rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, _cin(colors, is_sh, sh_degree), is_sh, camtoworlds, Ks, width, height,
-                                               own_workspace=True, viewmats=viewmats, sh_degree=sh_degree, campos=campos)
+                                               own_workspace=True, viewmats=viewmats, sh_degree=sh_degree, campos=campos, opts=opts,
+                                               backgrounds=backgrounds)
         ctx.state, ctx.geom = state, (is_sh, width, height)
         ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
-        ctx.save_for_backward(depth)     # the one forward output the backward reads
+        ctx.bg_meta = None if backgrounds is None else (backgrounds.shape, backgrounds.dtype)
+        if backgrounds is None:
+            ctx.save_for_backward(depth)     # the one forward output the backward reads
+        else:
+            ctx.save_for_backward(depth, alpha)     # v_backgrounds reads the forward's alpha
         return rgb, depth, alpha
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
-        (depth,) = ctx.saved_tensors
-        grads, _, _, v_vm, v_cp = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False, ctx.needs_input_grad[11],
-                                            ctx.needs_input_grad[12])
+        depth, alpha = (*ctx.saved_tensors, None)[:2]
+        want_bg = ctx.bg_meta is not None and ctx.needs_input_grad[15]
+        grads, _, _, v_vm, v_cp, v_bg = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False, ctx.needs_input_grad[11],
+                                                  ctx.needs_input_grad[12], want_bg, alpha)
         # camtoworlds, Ks: no gradient of their own (camtoworlds gets its through viewmats and campos)
         return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0] and not ctx.state[10], ctx.needs_input_grad[6:11]),
-                v_vm, v_cp, None)
+                v_vm, v_cp, None, None, _shape_bg(v_bg, ctx.bg_meta))
 
 
 def _cin(colors, is_sh, sh_degree):
@@ -71,13 +90,18 @@ def _cin(colors, is_sh, sh_degree):
     return colors[:, 0, :] if is_sh and not sh_degree else colors
 
 
-def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_cam=False, want_campos=False):
-    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs, v_viewmats, v_campos (None
-    unless asked for).  Without want_means2d this is wm_rasterize_splats_backward; the _ex entry gives the same five gradients bit for bit,
-    and so does the _cam entry that want_cam selects (v_viewmats [C,4,4]: gradient of the world-to-camera matrices).  A forward with SH
-    degree 1-3 goes through the _sh entry on every route (g_colors [N,K,3]; v_campos [C,3]: gradient of the camera positions)."""
+def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_cam=False, want_campos=False, want_bg=False, alpha=None):
+    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs, v_viewmats, v_campos,
+    v_backgrounds (each None unless asked for).  Which entry runs:
+      forward with options (state[12] is an _Opts)  wm_rasterize_splats_backward_opt, whatever else is asked for; v_backgrounds [C,3] reads
+                                                    the forward's alpha
+      forward without options, SH degree 1-3        the _sh entry (g_colors [N,K,3]; v_campos [C,3]: gradient of the camera positions)
+      ... want_cam                                  the _cam entry (v_viewmats [C,4,4]: gradient of the world-to-camera matrices)
+      ... want_means2d                              the _ex entry
+      ... none of these                             wm_rasterize_splats_backward
+    The five splat gradients are the same bits on every one of them."""
     L = _lib.lib()
-    means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n, sh_degree, campos = state
+    means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n, sh_degree, campos, opts, bg = state
     is_sh, width, height = geom
     dev = means.device
     N, V = int(means.shape[0]), int(viewmats.shape[0])
@@ -86,8 +110,24 @@ def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_c
     g_opac, g_col = torch.empty_like(opacities), torch.empty_like(cin)
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    v2d = v2d_abs = v_vm = v_cp = None
-    if sh_degree:
+    v2d = v2d_abs = v_vm = v_cp = v_bg = None
+    if opts is not None:
+        if want_means2d:
+            v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
+            v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
+        want_absgrad = bool(want_means2d and want_absgrad)
+        v_vm = torch.empty((V, 4, 4), device=dev, dtype=torch.float32) if want_cam else None
+        v_cp = torch.empty((V, 3), device=dev, dtype=torch.float32) if want_campos and sh_degree else None
+        v_bg = torch.empty((V, 3), device=dev, dtype=torch.float32) if want_bg and bg is not None else None
+        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_opt(N, V, width, height, n, int(want_absgrad), int(v_vm is not None), sh_degree,
+                                                                      int(v_cp is not None), int(v_bg is not None)), device=dev, dtype=torch.uint8)
+        st = L.wm_rasterize_splats_backward_opt(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, int(cin.shape[1]) if sh_degree else 0,
+                                                sh_degree, p(campos) if sh_degree else None, N, p(viewmats), p(Ks), V, width, height,
+                                                C.byref(opts.struct(bg)), p(ws), ws.numel(), cap, n, None, p(depth),
+                                                None if v_bg is None else p(_f32(alpha)), p(cot[0]), p(cot[1]), p(cot[2]), p(g_means), p(g_quats),
+                                                p(g_scales), p(g_opac), p(g_col), p(v2d), p(v2d_abs), int(want_absgrad), p(v_vm), p(v_cp), p(v_bg),
+                                                p(gws), gws.numel(), stream)
+    elif sh_degree:
         if want_means2d:
             v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
             v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
@@ -126,7 +166,11 @@ def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_c
                                                p(gws), gws.numel(), stream)
     if st != 0:
         raise RuntimeError(f"wm_rasterize_splats_backward failed with status {st}")
-    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs, v_vm, v_cp
+    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs, v_vm, v_cp, v_bg
+
+
+def _shape_bg(v_bg, meta):
+    return None if v_bg is None else v_bg.reshape(meta[0]).to(meta[1])
 
 
 def _shape_grads(grads, meta, is_sh, needed):
@@ -149,10 +193,13 @@ class _ProjectMeans2d(torch.autograd.Function):
     parameter gradients all come from the one fused backward of _CompositeWithInfo, so nothing is counted twice."""
 
     @staticmethod
-    def forward(ctx, rz, shared, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats, campos, sh_degree):
-        radii = torch.empty((int(camtoworlds.shape[0]), int(means.shape[0]), 2), device=means.device, dtype=torch.int32)
+    def forward(ctx, rz, shared, is_sh, width, height, camtoworlds, Ks, means, quats, scales, opacities, colors, viewmats, campos, sh_degree,
+                opts, backgrounds):
+        radii = torch.empty((int((viewmats if camtoworlds is None else camtoworlds).shape[0]), int(means.shape[0]), 2), device=means.device,
+                            dtype=torch.int32)
         rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, _cin(colors, is_sh, sh_degree), is_sh, camtoworlds, Ks, width, height,
-                                               own_workspace=True, radii=radii, viewmats=viewmats, sh_degree=sh_degree, campos=campos)
+                                               own_workspace=True, radii=radii, viewmats=viewmats, sh_degree=sh_degree, campos=campos, opts=opts,
+                                               backgrounds=backgrounds)
         shared.update(out=(rgb, depth, alpha), state=state, radii=radii)
         ctx.shared = shared
         m2 = rz._means2d(state, radii, width, height)
@@ -167,7 +214,7 @@ class _ProjectMeans2d(torch.autograd.Function):
         if sent is None or not (v_means2d.data_ptr() == sent.data_ptr() or torch.equal(v_means2d, sent)):
             raise NotImplementedError("info['means2d'] carries gradient only from the rendered images to itself (.grad / .absgrad for a "
                                       "densification strategy): a loss computed from means2d directly is not propagated to the splats")
-        return (None,) * 15
+        return (None,) * 17
 
 
 class _CompositeWithInfo(torch.autograd.Function):
@@ -178,25 +225,43 @@ class _CompositeWithInfo(torch.autograd.Function):
     camera_grad and SH degree 1-3 the graph's camera positions) the colour's camera term."""
 
     @staticmethod
-    def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors, viewmats, campos):
+    def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors, viewmats, campos, backgrounds):
         rgb, depth, alpha = shared.pop("out")
         ctx.state, ctx.geom, ctx.want_absgrad = shared.pop("state"), geom, want_absgrad
         ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
+        ctx.bg_meta = None if backgrounds is None else (backgrounds.shape, backgrounds.dtype)
         ctx.means2d_ref, ctx.shared = shared["means2d_ref"], shared
-        ctx.save_for_backward(depth)
+        if backgrounds is None:
+            ctx.save_for_backward(depth)
+        else:
+            ctx.save_for_backward(depth, alpha)
         return rgb, depth, alpha
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
-        (depth,) = ctx.saved_tensors
-        grads, v2d, v2d_abs, v_vm, v_cp = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad,
-                                                    ctx.needs_input_grad[9], ctx.needs_input_grad[10])
+        depth, alpha = (*ctx.saved_tensors, None)[:2]
+        want_bg = ctx.bg_meta is not None and ctx.needs_input_grad[11]
+        grads, v2d, v2d_abs, v_vm, v_cp, v_bg = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad,
+                                                          ctx.needs_input_grad[9], ctx.needs_input_grad[10], want_bg, alpha)
         m2 = ctx.means2d_ref()
         if ctx.want_absgrad and m2 is not None:
             m2.absgrad = v2d_abs
         ctx.shared["v_means2d"] = v2d
-        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0] and not ctx.state[10], ctx.needs_input_grad[4:9]), v_vm, v_cp)
+        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0] and not ctx.state[10], ctx.needs_input_grad[4:9]), v_vm, v_cp,
+                _shape_bg(v_bg, ctx.bg_meta))
+
+
+class _Opts(collections.namedtuple("_Opts", "antialiased depth_mode eps2d near_plane far_plane radius_clip")):
+    """gsplat.rasterization's options as the _opt entries take them (include/wm_hip.h wm_raster_options); backgrounds travel beside it"""
+    __slots__ = ()
+
+    def struct(self, backgrounds=None):
+        return _lib.wm_raster_options(int(self.antialiased), int(self.depth_mode), float(self.eps2d), float(self.near_plane), float(self.far_plane),
+                                      float(self.radius_clip), None if backgrounds is None else backgrounds.data_ptr())
+
+
+_OPTION_DEFAULTS = dict(near_plane=0.01, far_plane=1e10, eps2d=0.3, radius_clip=0.0)
 
 
 class Rasterizer:
@@ -204,8 +269,8 @@ class Rasterizer:
                  sparse_grad=False, distributed=False, grad_strategy=None, camera_grad: bool = False):
         """camera_grad: give a camtoworlds that requires grad its gradient (through viewmats = inv(camtoworlds), taken in the graph);
         off by default: cameras then get None.  Ks never gets a gradient (as in gsplat)."""
-        if rasterization_mode != "classic" or camera_model != "pinhole" or with_eval3d or distributed:
-            raise NotImplementedError("only the reference's configuration is built: classic / pinhole / no eval3d / single process")
+        if rasterization_mode not in ("classic", "antialiased") or camera_model != "pinhole" or with_eval3d or distributed:
+            raise NotImplementedError("only the reference's configuration is built: classic or antialiased / pinhole / no eval3d / single process")
         self.rasterization_mode, self.packed, self.abs_grad, self.camera_model = rasterization_mode, packed, abs_grad, camera_model
         self.sparse_grad, self.grad_strategy, self.distributed, self.with_eval3d = sparse_grad, grad_strategy, distributed, with_eval3d
         self.camera_grad = bool(camera_grad)
@@ -215,12 +280,21 @@ class Rasterizer:
 
     # rasterization.py:29-66
     def rasterize_splats(self, means, quats, scales, opacities, colors, camtoworlds, Ks, width: int, height: int,
-                         sh_degree=None, return_info: bool = False, absgrad: bool | None = None, **kwargs):
+                         sh_degree=None, return_info: bool = False, absgrad: bool | None = None, near_plane=None, far_plane=None, eps2d=None,
+                         radius_clip=None, backgrounds=None, **kwargs):
         """-> (rgb, depth, alpha), or with return_info=True (rgb, depth, alpha, info): info["means2d"] [C,N,2] fp32 (zero where
         culled, part of the graph), info["radii"] [C,N,2] int32, "width", "height", "n_cameras", "gaussian_ids" = None (the layout
-        is always the unpacked [C,N,...] one).  absgrad (None: self.abs_grad) is read on the return_info route only."""
+        is always the unpacked [C,N,...] one).  absgrad (None: self.abs_grad) is read on the return_info route only.
+        near_plane / far_plane / eps2d / radius_clip (gsplat's defaults 0.01 / 1e10 / 0.3 / 0) and backgrounds [C,3] (differentiable) are
+        gsplat.rasterization's; depth stays the expected depth (the reference class hard-wires render_mode "RGB+ED", so render_mode here is a
+        TypeError as it is there).  A classic rasteriser called with none of them takes the entries without options."""
         if kwargs:
             raise TypeError(f"unsupported gsplat.rasterization arguments: {sorted(kwargs)}")
+        given = dict(near_plane=near_plane, far_plane=far_plane, eps2d=eps2d, radius_clip=radius_clip)
+        opts = None
+        if self.rasterization_mode == "antialiased" or backgrounds is not None or any(v is not None for v in given.values()):
+            opts = _Opts(int(self.rasterization_mode == "antialiased"), 0,
+                         **{k: _OPTION_DEFAULTS[k] if v is None else float(v) for k, v in given.items()})
         if means.device.type != "cuda":
             raise RuntimeError("the rasteriser runs in libwm_hip.so on the GPU: move the splats to a HIP device")
         L = 0
@@ -237,16 +311,22 @@ class Rasterizer:
             cin, is_sh = colors, 0
         splat_in = (means, quats, scales, opacities, colors)
         if return_info:
-            return self._with_info(splat_in, cin, is_sh, camtoworlds, Ks, int(width), int(height), self.abs_grad if absgrad is None else absgrad, L)
+            return self._with_info(splat_in, cin, is_sh, camtoworlds, Ks, int(width), int(height), self.abs_grad if absgrad is None else absgrad, L,
+                                   opts=opts, backgrounds=backgrounds)
         if absgrad:
             raise ValueError("absgrad is reported through info: pass return_info=True")
         viewmats, campos = self._graph_viewmats(camtoworlds), None
         if viewmats is not None and L:
             campos = camtoworlds.to(torch.float32)[:, :3, 3]
-        if torch.is_grad_enabled() and (viewmats is not None or any(t.requires_grad for t in splat_in)):
-            return _RasterizeSplats.apply(self, is_sh, int(width), int(height), camtoworlds, Ks, *splat_in, viewmats, campos, L)
-        rgb, depth, alpha, _ = self._forward(means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False,
-                                             sh_degree=L)
+        return self._render(splat_in, cin, is_sh, camtoworlds, Ks, int(width), int(height), L, viewmats, campos, opts, backgrounds)
+
+    def _render(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, L, viewmats, campos, opts, backgrounds):
+        """the route without info.  viewmats / campos: None, or graph tensors (with camtoworlds = None: the cameras themselves)"""
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (*splat_in, viewmats, campos, backgrounds)):
+            return _RasterizeSplats.apply(self, is_sh, width, height, camtoworlds, Ks, *splat_in, viewmats, campos, L, opts, backgrounds)
+        rgb, depth, alpha, _ = self._forward(*splat_in[:4], cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False,
+                                             viewmats=None if camtoworlds is not None else viewmats, sh_degree=L,
+                                             campos=None if camtoworlds is not None else campos, opts=opts, backgrounds=backgrounds)
         return rgb, depth, alpha
 
     def _graph_viewmats(self, camtoworlds):
@@ -255,21 +335,28 @@ class Rasterizer:
             return torch.linalg.inv(camtoworlds.to(torch.float32))
         return None
 
-    def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad, sh_degree=0):
-        V, N = int(camtoworlds.shape[0]), int(splat_in[0].shape[0])
-        viewmats, campos = self._graph_viewmats(camtoworlds), None
-        if viewmats is not None and sh_degree:
-            campos = camtoworlds.to(torch.float32)[:, :3, 3]
-        if torch.is_grad_enabled() and (viewmats is not None or any(t.requires_grad for t in splat_in)):
+    def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad, sh_degree=0, opts=None, backgrounds=None, cameras=None):
+        """cameras: None (camtoworlds given), or (viewmats, campos) with camtoworlds = None: the world-to-camera matrices themselves and, for SH
+        degree 1-3, the camera positions, graph tensors where they require grad (the module-level rasterization())"""
+        if cameras is None:
+            viewmats, campos = self._graph_viewmats(camtoworlds), None
+            if viewmats is not None and sh_degree:
+                campos = camtoworlds.to(torch.float32)[:, :3, 3]
+        else:
+            viewmats, campos = cameras
+        V, N = int((viewmats if camtoworlds is None else camtoworlds).shape[0]), int(splat_in[0].shape[0])
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (*splat_in, viewmats, campos, backgrounds)):
             shared = {}
-            m2 = _ProjectMeans2d.apply(self, shared, is_sh, width, height, camtoworlds, Ks, *splat_in, viewmats, campos, sh_degree)
+            m2 = _ProjectMeans2d.apply(self, shared, is_sh, width, height, camtoworlds, Ks, *splat_in, viewmats, campos, sh_degree, opts, backgrounds)
             shared["means2d_ref"] = weakref.ref(m2)
             radii = shared.pop("radii")
-            rgb, depth, alpha = _CompositeWithInfo.apply(shared, (is_sh, width, height), bool(want_absgrad), m2, *splat_in, viewmats, campos)
+            rgb, depth, alpha = _CompositeWithInfo.apply(shared, (is_sh, width, height), bool(want_absgrad), m2, *splat_in, viewmats, campos,
+                                                         backgrounds)
         else:
             radii = torch.empty((V, N, 2), device=splat_in[0].device, dtype=torch.int32)
             rgb, depth, alpha, state = self._forward(*splat_in[:4], cin, is_sh, camtoworlds, Ks, width, height, own_workspace=False, radii=radii,
-                                                     sh_degree=sh_degree)
+                                                     viewmats=None if camtoworlds is not None else viewmats, sh_degree=sh_degree,
+                                                     campos=None if camtoworlds is not None else campos, opts=opts, backgrounds=backgrounds)
             m2 = self._means2d(state, radii, width, height)
         info = {"means2d": m2, "radii": radii, "width": width, "height": height, "n_cameras": V, "gaussian_ids": None}
         return rgb, depth, alpha, info
@@ -287,16 +374,22 @@ class Rasterizer:
         return m2
 
     def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, radii=None, viewmats=None,
-                 sh_degree=0, campos=None):
-        """One wm_rasterize_splats call (sh_degree 1-3: wm_rasterize_splats_sh, cin the coefficients [N,K,3]).  own_workspace: a workspace
+                 sh_degree=0, campos=None, opts=None, backgrounds=None):
+        """One wm_rasterize_splats call (sh_degree 1-3: wm_rasterize_splats_sh, cin the coefficients [N,K,3]; with opts, an _Opts, and
+        backgrounds [C,3] or None: wm_rasterize_splats_opt in either colour form; camtoworlds may then be None when viewmats, and for SH
+        degree 1-3 campos, are given).  own_workspace: a workspace
         of this call's own (kept by the autograd node until its backward has run) instead of the rasteriser's reusable one.  radii:
         optional [C,N,2] int32 output.  viewmats, campos: the inverse of camtoworlds and its translation column where the caller has taken
         them already (camera_grad); their values are used, detached.
         -> rgb, depth, alpha, state for the backward."""
         L = _lib.lib()
         dev = means.device
-        N, V = int(means.shape[0]), int(camtoworlds.shape[0])
+        N, V = int(means.shape[0]), int((viewmats if camtoworlds is None else camtoworlds).shape[0])
         means, quats, scales, opacities, cin = _f32(means), _f32(quats), _f32(scales), _f32(opacities).reshape(-1), _f32(cin)
+        if backgrounds is not None:
+            if tuple(backgrounds.shape) != (V, 3):
+                raise ValueError(f"backgrounds must be [C, 3] = [{V}, 3], not {tuple(backgrounds.shape)}")
+            backgrounds = _f32(backgrounds)
         viewmats = _f32(torch.linalg.inv(camtoworlds.detach().to(torch.float32)) if viewmats is None else viewmats)  # :48
         Ks = _f32(Ks)
         if sh_degree:
@@ -318,7 +411,11 @@ class Rasterizer:
             self._cap = cap
             tail = (p(viewmats), p(Ks), V, width, height, p(rgb), p(depth), p(alpha), None if radii is None else p(radii), p(ws), ws.numel(), cap,
                     C.byref(n), stream)
-            if sh_degree:
+            if opts is not None:
+                st = L.wm_rasterize_splats_opt(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, int(cin.shape[1]) if sh_degree else 0,
+                                               sh_degree, p(campos) if sh_degree else None, N, tail[0], tail[1], V, width, height,
+                                               C.byref(opts.struct(backgrounds)), *tail[5:])
+            elif sh_degree:
                 st = L.wm_rasterize_splats_sh(p(means), p(quats), p(scales), p(opacities), p(cin), int(cin.shape[1]), sh_degree, p(campos), N, *tail)
             else:
                 st = L.wm_rasterize_splats(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, *tail)
@@ -331,7 +428,7 @@ class Rasterizer:
         else:
             raise RuntimeError("wm_rasterize_splats: workspace re-size did not converge")
         self.last_n_isects = int(n.value)
-        return rgb, depth, alpha, (means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, int(n.value), int(sh_degree), campos)
+        return rgb, depth, alpha, (means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, int(n.value), int(sh_degree), campos, opts, backgrounds)
 
     # rasterization.py:68-93 (NB: the reference passes what it calls `viewmats` on as `camtoworlds`)
     def rasterize_batches(self, means, quats, scales, opacities, colors, viewmats, Ks, width, height, **kwargs):
@@ -342,3 +439,55 @@ class Rasterizer:
             c, d, a = self.rasterize_splats(means[i], quats[i], scales[i], opacities[i], colors[i], viewmats[i], Ks[i], width, height, **kwargs)
             rc.append(c); rd.append(d); ra.append(a)
         return torch.stack(rc, 0), torch.stack(rd, 0), torch.stack(ra, 0)
+
+
+_RENDER_MODES = {"RGB": (True, None), "D": (False, 1), "ED": (False, 0), "RGB+D": (True, 1), "RGB+ED": (True, 0)}   # colour?, depth_mode
+_shared = None
+
+
+def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, height, near_plane=0.01, far_plane=1e10, radius_clip=0.0,
+                  eps2d=0.3, sh_degree=None, packed=False, tile_size=16, backgrounds=None, render_mode="RGB", sparse_grad=False, absgrad=False,
+                  rasterize_mode="classic", channel_chunk=32, distributed=False, camera_model="pinhole", segmented=False, covars=None,
+                  with_ut=False, with_eval3d=False, **unsupported):
+    """gsplat.rasterization (gsplat/rendering.py) as the reference's post-3DGS trainer calls it (simple_trainer_worldmirror.py:619-642):
+    -> (render_colors [C,H,W,3 | 1 | 4], render_alphas [C,H,W,1], info).  viewmats [C,4,4] are WORLD-TO-CAMERA, as in gsplat; a viewmats
+    that requires grad receives the camera gradient directly and, with sh_degree > 0, also through campos = inv(viewmats)[:, :3, 3], taken
+    in the graph.  colors: [N,3] with sh_degree None, or SH coefficients [N,K,3] with sh_degree 0-3.  render_mode: "RGB", "D" (accumulated
+    depth), "ED" (expected depth), "RGB+D", "RGB+ED"; backgrounds [C,3] (differentiable) reach the colour channels only.  info is that of
+    Rasterizer.rasterize_splats(return_info=True): means2d (with .grad, and .absgrad with absgrad=True, after backward), radii, width,
+    height, n_cameras, gaussian_ids = None.  Whatever the kernels do not do raises NotImplementedError naming the argument."""
+    global _shared
+    for name, bad in (("packed", packed), ("sparse_grad", sparse_grad), ("distributed", distributed), ("with_ut", with_ut),
+                      ("with_eval3d", with_eval3d), ("segmented", segmented), ("covars", covars is not None),
+                      ("tile_size", tile_size != 16), ("camera_model", camera_model != "pinhole"),
+                      ("rasterize_mode", rasterize_mode not in ("classic", "antialiased")), ("render_mode", render_mode not in _RENDER_MODES)):
+        if bad:
+            raise NotImplementedError(f"rasterization(): {name} = {locals()[name]!r} is not built")
+    if unsupported:
+        raise NotImplementedError(f"rasterization(): arguments not built: {sorted(unsupported)}")
+    if colors.shape[-1] != 3 or colors.dim() != (2 if sh_degree is None else 3):
+        raise NotImplementedError(f"rasterization(): colors of shape {tuple(colors.shape)} with sh_degree = {sh_degree}: 3 colour channels, "
+                                  "[N,3] or SH coefficients [N,K,3], are built")
+    L, is_sh = 0, 0
+    if sh_degree is not None:
+        L, is_sh = int(sh_degree), 1
+        if not 0 <= L <= 3:
+            raise NotImplementedError(f"rasterization(): sh_degree = {sh_degree} (0 to 3 are built)")
+        if (L + 1) ** 2 > int(colors.shape[1]):
+            raise ValueError(f"sh_degree = {L} reads {(L + 1) ** 2} bands, colors has K = {int(colors.shape[1])}")
+    if means.device.type != "cuda":
+        raise RuntimeError("the rasteriser runs in libwm_hip.so on the GPU: move the splats to a HIP device")
+    want_rgb, depth_mode = _RENDER_MODES[render_mode]
+    opts = _Opts(int(rasterize_mode == "antialiased"), int(depth_mode or 0), float(eps2d), float(near_plane), float(far_plane), float(radius_clip))
+    if _shared is None:
+        _shared = Rasterizer()
+    vm = viewmats.to(torch.float32)
+    campos = None
+    if L:
+        with torch.set_grad_enabled(torch.is_grad_enabled() and vm.requires_grad):
+            campos = torch.linalg.inv(vm)[:, :3, 3]
+    rgb, depth, alpha, info = _shared._with_info((means, quats, scales, opacities, colors), _cin(colors, is_sh, L), is_sh, None, Ks, int(width),
+                                                 int(height), bool(absgrad), L, opts=opts, backgrounds=backgrounds, cameras=(vm, campos))
+    if depth_mode is None:
+        return rgb, alpha, info
+    return (torch.cat([rgb, depth], -1) if want_rgb else depth), alpha, info

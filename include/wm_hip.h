@@ -469,6 +469,58 @@ wm_status wm_rasterize_splats_backward_sh(const float* means, const float* quats
                                           float* v_opacities, float* v_sh_coeffs, float* v_means2d, float* v_means2d_abs,
                                           int want_absgrad, float* v_viewmats, float* v_campos, void* grad_workspace,
                                           size_t grad_workspace_bytes, void* stream);
+/* gsplat.rasterization's own options — replaces the keyword arguments the reference's post-3DGS trainer passes to gsplat.rasterization
+ * (simple_trainer_worldmirror.py:619-642, :741-752; gsplat/rendering.py): rasterize_mode, near_plane / far_plane, eps2d, radius_clip,
+ * backgrounds and the depth half of render_mode.  A null options pointer means the defaults noted beside the fields, which are what the
+ * entries above render. */
+typedef struct wm_raster_options {
+  int   antialiased;    /* 0 classic, 1: opacity * sqrt(max(det(cov2d) / det(cov2d + eps2d I), 0)) (_torch_impl.py:329-344) */
+  int   depth_mode;     /* 0 expected (ED): sum w z / max(alpha, 1e-10); 1 accumulated (D): sum w z (rendering.py:984-992) */
+  float eps2d;          /* 0.3: the blur added to the 2-D covariance's diagonal (not the 0.3 of _persp_proj's clamp limits) */
+  float near_plane;     /* 0.01 */
+  float far_plane;      /* 1e10 */
+  float radius_clip;    /* 0: a (camera, Gaussian) pair whose two radii are both <= radius_clip pixels is culled (gsplat's
+                           ProjectionEWA3DGSFused.cu; 0 culls nothing) */
+  const float* backgrounds;  /* device [C,3] or null: out_rgb += backgrounds[c] (1 - alpha); the depth channel gets none (rendering.py:926-939) */
+} wm_raster_options;
+/* The forward with options: a superset of wm_rasterize_splats and wm_rasterize_splats_sh.  Colours in either form: sh_degree = 0 with
+ * colors [N,3] and colors_are_sh0 as wm_rasterize_splats (n_coeffs, campos not read), or sh_degree 1-3 with colors = sh_coeffs
+ * [N,n_coeffs,3] and campos [C,3] as wm_rasterize_splats_sh (colors_are_sh0 not read).  Outputs, workspace (wm_rasterize_workspace_bytes),
+ * max_isects / *n_isects and WM_ERR_STATE exactly as wm_rasterize_splats; wm_rasterize_means2d works on the workspace this call leaves.
+ * out_depth holds the depth channel of the chosen depth_mode.  WM_ERR_INVALID, before anything is launched, for eps2d < 0,
+ * near_plane >= far_plane, radius_clip < 0, depth_mode or antialiased outside {0, 1}, sh_degree outside 0..3, (sh_degree + 1)^2 > n_coeffs
+ * or a null campos with sh_degree > 0.  With null (default) options the outputs are those of the entries above, bit for bit. */
+wm_status wm_rasterize_splats_opt(const float* means, const float* quats, const float* scales, const float* opacities,
+                                  const float* colors, int colors_are_sh0, int n_coeffs, int sh_degree, const float* campos,
+                                  int n_gaussians, const float* viewmats, const float* Ks, int n_cameras, int width, int height,
+                                  const wm_raster_options* options, float* out_rgb, float* out_depth, float* out_alpha,
+                                  int* radii_out, void* workspace, size_t workspace_bytes, size_t max_isects,
+                                  unsigned long long* n_isects, void* stream);
+/* Backward of ONE wm_rasterize_splats_opt call (same options, same CONTRACT on the forward's workspace as wm_rasterize_splats_backward) —
+ * replaces what gsplat's autograd gives for the options: the compensation's gradient (gsplat/cuda/include/Utils.cuh add_blur_vjp), the
+ * background term of rendering.py:926-939 and the depth mode's.  Outputs: all of the _sh entry's (v_colors [N,3], or [N,n_coeffs,3] with
+ * sh_degree > 0; v_means2d, v_means2d_abs, v_viewmats, v_campos optional; v_campos needs sh_degree > 0) plus
+ *   v_backgrounds [C,3] optional (needs options->backgrounds and out_alpha, the forward's alpha, which is READ): sum over the camera's
+ *                 pixels of v_rgb (1 - alpha).  Terms fp32; from there on fp64: per 4096-pixel chunk 256 strided running sums and a fixed
+ *                 pairwise tree, then the chunks' partials in a fixed order (256 strided running sums, a fixed tree), rounded to fp32 once.
+ * Antialiased: v_opacities = sum over cameras of comp * v_opacity'; v_comp = opacity * v_opacity' enters the 2-D covariance's gradient with
+ * the EXACT derivative 0.5 / comp (autograd's on the torch projection; gsplat's CUDA divides by comp + 1e-6), exactly 0 where comp == 0 or
+ * the determinant clamp is active (never NaN).  Accumulated depth: v_depth is the cotangent of sum w z itself.  Everything else: summation
+ * order, no atomics, bitwise reproducible, as the entries above; with null options the same bits as those entries.
+ * grad_workspace: wm_rasterize_backward_workspace_bytes_opt bytes = the _sh / _cam / _ex size for the same requests (sh_degree > 0 adds the
+ * _sh parts) + with want_backgrounds 24 bytes per camera per 4096 pixels (rounded up to 256); a smaller one returns WM_ERR_INVALID before
+ * anything is launched, as do invalid options. */
+size_t wm_rasterize_backward_workspace_bytes_opt(int n_gaussians, int n_cameras, int width, int height, size_t n_isects, int want_absgrad,
+                                                 int want_viewmats, int sh_degree, int want_campos, int want_backgrounds);
+wm_status wm_rasterize_splats_backward_opt(const float* means, const float* quats, const float* scales, const float* opacities,
+                                           const float* colors, int colors_are_sh0, int n_coeffs, int sh_degree, const float* campos,
+                                           int n_gaussians, const float* viewmats, const float* Ks, int n_cameras, int width, int height,
+                                           const wm_raster_options* options, const void* workspace, size_t workspace_bytes,
+                                           size_t max_isects, size_t n_isects, const float* out_rgb, const float* out_depth,
+                                           const float* out_alpha, const float* v_rgb, const float* v_depth, const float* v_alpha,
+                                           float* v_means, float* v_quats, float* v_scales, float* v_opacities, float* v_colors,
+                                           float* v_means2d, float* v_means2d_abs, int want_absgrad, float* v_viewmats, float* v_campos,
+                                           float* v_backgrounds, void* grad_workspace, size_t grad_workspace_bytes, void* stream);
 /* The pixel-space means [C,N,2] of ONE wm_rasterize_splats call, read out of the workspace it left (same sizes and max_isects,
  * workspace untouched since); radii: that call's radii_out.  Zero where a radius is 0 (culled).  Asynchronous on stream. */
 wm_status wm_rasterize_means2d(const void* workspace, size_t workspace_bytes, int n_gaussians, int n_cameras, int width, int height,
