@@ -61,7 +61,7 @@ EXPORTS = [
     "wm_depth_edge", "wm_normals_edge", "wm_point_filter_mask_workspace_bytes", "wm_point_filter_mask",
     "wm_op_im2col", "wm_op_im2col7", "wm_op_dino_tokens", "wm_op_vgt_special", "wm_op_gemm_rowmap", "wm_op_gemm_convt", "wm_op_layernorm_rows",
     "wm_op_bilinear_add", "wm_op_bilinear16", "wm_op_copy2d", "wm_op_small_attention", "wm_op_adaln", "wm_op_cam_update", "wm_op_cam_matrices",
-    "wm_op_linear_f32_ex", "wm_op_dpt_tail", "wm_op_up_conv_n32_tail",
+    "wm_op_linear_f32_ex", "wm_op_dpt_tail", "wm_op_up_conv_n32_tail", "wm_op_dpt_tap_front",
     "wm_photometric_loss_workspace_bytes", "wm_photometric_loss_forward_workspace_bytes", "wm_photometric_loss", "wm_photometric_loss_backward",
     "wm_rasterize_backward_workspace_bytes_ex", "wm_rasterize_splats_backward_ex", "wm_rasterize_means2d",
     "wm_rasterize_backward_workspace_bytes_cam", "wm_rasterize_splats_backward_cam",
@@ -251,6 +251,8 @@ def lib() -> C.CDLL:
     L.wm_op_gs_splat.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
     L.wm_op_dpt_tail.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, i32, i32, vp]
     L.wm_op_up_conv_n32_tail.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.wm_op_dpt_tap_front.argtypes = [i32, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, i32, i32,
+                                      C.POINTER(vp), C.POINTER(i32), vp]
     L.wm_set_tuning.argtypes = [C.c_char_p, i32]
     L.wm_set_tuning.restype = i32
     _lib = L

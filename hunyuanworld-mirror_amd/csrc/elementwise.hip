@@ -70,8 +70,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const WmLnArgs p) {
 // and bias — requested up front.  The general kernel above tests `c < D` per chunk, so hipcc emits, per chunk, {load w, load b,
 // s_waitcnt vmcnt(0), compute, store}: four serialised L2 round trips per row behind the reductions (round 4: 14.3 -> 12.x us for the
 // 11008 x 1024 rows of a backbone LayerNorm).  Same expressions in the same order as the general kernel: bit-identical results.
-template <int NV, int T, int RPW>
-__global__ __launch_bounds__(256) void layernorm_fast_kernel(const WmLnArgs p) {
+// AFF = false: no weight / bias (the DPT heads' shared tap normalisation, whose affine lives in the projection weights): the same mean / rstd
+// arithmetic, y = (x - mean) * rstd.
+template <int NV, int T, int RPW, bool AFF>
+__device__ __forceinline__ void layernorm_fast_body(const WmLnArgs& p) {
   // RPW rows per wave (A/B: 2 makes the 11 K-row launches of an 8-view forward one round of wave slots instead of 1.34 — measured equal),
   // all of their loads in flight before the first reduction
   const int lane = threadIdx.x & 63;
@@ -92,10 +94,12 @@ __global__ __launch_bounds__(256) void layernorm_fast_kernel(const WmLnArgs p) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[r][i] = *(const float4*)(x[r] + (i * 64 + lane) * 4);
   }
+  if constexpr (AFF) {
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    w[i] = *(const float4*)(p.w + (i * 64 + lane) * 4);
-    b[i] = *(const float4*)(p.b + (i * 64 + lane) * 4);
+    for (int i = 0; i < NV; ++i) {
+      w[i] = *(const float4*)(p.w + (i * 64 + lane) * 4);
+      b[i] = *(const float4*)(p.b + (i * 64 + lane) * 4);
+    }
   }
 #pragma unroll
   for (int r = 0; r < RPW; ++r) {
@@ -114,8 +118,11 @@ __global__ __launch_bounds__(256) void layernorm_fast_kernel(const WmLnArgs p) {
     u16* y = (u16*)p.y + orow[r] * p.ld_out;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      const float y0 = (v[r][i].x - mean) * rstd * w[i].x + b[i].x, y1 = (v[r][i].y - mean) * rstd * w[i].y + b[i].y;
-      const float y2 = (v[r][i].z - mean) * rstd * w[i].z + b[i].z, y3 = (v[r][i].w - mean) * rstd * w[i].w + b[i].w;
+      float y0 = (v[r][i].x - mean) * rstd, y1 = (v[r][i].y - mean) * rstd, y2 = (v[r][i].z - mean) * rstd, y3 = (v[r][i].w - mean) * rstd;
+      if constexpr (AFF) {
+        y0 = y0 * w[i].x + b[i].x; y1 = y1 * w[i].y + b[i].y;
+        y2 = y2 * w[i].z + b[i].z; y3 = y3 * w[i].w + b[i].w;
+      }
       uint2 u;
       u.x = (uint32_t)f2t<T>(y0) | ((uint32_t)f2t<T>(y1) << 16);
       u.y = (uint32_t)f2t<T>(y2) | ((uint32_t)f2t<T>(y3) << 16);
@@ -123,6 +130,10 @@ __global__ __launch_bounds__(256) void layernorm_fast_kernel(const WmLnArgs p) {
     }
   }
 }
+template <int NV, int T, int RPW>
+__global__ __launch_bounds__(256) void layernorm_fast_kernel(const WmLnArgs p) { layernorm_fast_body<NV, T, RPW, true>(p); }
+template <int NV, int T>
+__global__ __launch_bounds__(256) void layernorm_fast_noaffine_kernel(const WmLnArgs p) { layernorm_fast_body<NV, T, 1, false>(p); }
 
 // ------------------------------------------------------------------------------------------ QKV post
 // One wave = one token x 4 heads; 16 lanes per head vector (4 elements per lane).
@@ -568,6 +579,16 @@ hipError_t wm_launch_layernorm(const WmLnArgs& a, hipStream_t s) {
   if (a.D % 4 || a.D > 2048 || a.ld_in % 4 || a.ld_out % 4) return hipErrorInvalidValue;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   const int nv = (a.D + 255) / 256;
+  if (a.D == nv * 256 && (nv == 4 || nv == 8) && !a.w && !a.b && !a.out_f32) {   // no affine: the DPT heads' shared tap normalisation (D = 2048)
+    if (nv == 4) {
+      if (a.dtype == WM_T_BF16) hipLaunchKernelGGL((layernorm_fast_noaffine_kernel<4, WM_T_BF16>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((layernorm_fast_noaffine_kernel<4, WM_T_F16>), grid, block, 0, s, a);
+    } else {
+      if (a.dtype == WM_T_BF16) hipLaunchKernelGGL((layernorm_fast_noaffine_kernel<8, WM_T_BF16>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((layernorm_fast_noaffine_kernel<8, WM_T_F16>), grid, block, 0, s, a);
+    }
+    return hipGetLastError();
+  }
   if (a.D == nv * 256 && (nv == 4 || nv == 8) && a.w && a.b && !a.out_f32) {   // the backbone's LayerNorms (D = 1024) and the DPT heads' (D = 2048)
     // rows per wave: 1; 2 (tuning ln_rpw, D = 1024 only: one round of wave slots instead of 1.34 at 8 views) measured the same 12.5 us
     // (tools/bench_ln.py) and stays an A/B variant

@@ -68,6 +68,15 @@ __device__ __forceinline__ void tile_of(int lid, int ntm, int ntn, int G, int& b
   band = sg * G + (r - nt * here);
 }
 
+// WM_EPI_ROWMAP_ADD with split_n > 0: column `col` of the launch belongs to slice col / split_n; returns the column inside the slice, the slice's
+// width (the pitch of the `add` table) and its output tensor
+__device__ __forceinline__ void rowmap_slice(const WmGemmArgs& p, int& col, int& addn, void*& Cb) {
+  const int hd = col / p.split_n;
+  col -= hd * p.split_n;
+  addn = p.split_n;
+  Cb = hd == 0 ? p.split_C[0] : hd == 1 ? p.split_C[1] : hd == 2 ? p.split_C[2] : p.split_C[3];
+}
+
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int T, int EPI, int WM, int WN, int TM, int TN, int NSTAGE, int ILV, int KT = 64>
@@ -327,11 +336,13 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const WmGemmArgs 
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             if (!ok[g]) continue;
-            const int col = cb + 8 * g;
+            int col = cb + 8 * g, addn = p.N;
+            void* Cb = p.C;
+            if (p.split_n > 0) rowmap_slice(p, col, addn, Cb);   // (kernel-uniform) several consumers' columns side by side
             float4 x = v[g];
             if (p.relu) x = make_float4(fmaxf(x.x, 0.f), fmaxf(x.y, 0.f), fmaxf(x.z, 0.f), fmaxf(x.w, 0.f));
             if (p.add) {
-              const float4 ad = *(const float4*)(p.add + (size_t)q * p.N + col);
+              const float4 ad = *(const float4*)(p.add + (size_t)q * addn + col);
               x.x += ad.x; x.y += ad.y; x.z += ad.z; x.w += ad.w;
             }
             const size_t o = orow * p.ldc + col;
@@ -339,9 +350,9 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(const WmGemmArgs 
               uint2 u;
               u.x = (uint32_t)f2t<T>(x.x) | ((uint32_t)f2t<T>(x.y) << 16);
               u.y = (uint32_t)f2t<T>(x.z) | ((uint32_t)f2t<T>(x.w) << 16);
-              *(uint2*)((u16*)p.C + o) = u;
+              *(uint2*)((u16*)Cb + o) = u;
             } else {
-              float* c = (float*)p.C + o;
+              float* c = (float*)Cb + o;
               if (p.accumulate) {
                 const float4 od = *(const float4*)c;
                 x.x += od.x; x.y += od.y; x.z += od.z; x.w += od.w;
@@ -607,6 +618,46 @@ __device__ __forceinline__ void epilogue16(const WmGemmArgs& p, f32x4 (&acc)[SM]
           for (int j = 0; j < SN; ++j) {
             const int col = colb + j * 16 + 4 * lq;
             if (row < mlim && col < p.N) *(float4*)((float*)p.C + out_row(row) * p.ldc + col - cshift) = y[j];
+          }
+        }
+      }
+      return;
+    }
+    if constexpr (EPI == WM_EPI_ROWMAP_ADD) {
+      // acc + bias, ReLU?, + add[row inside its group][col], into the remapped row (and, with split_n, the column's own slice tensor)
+#pragma unroll
+      for (int i = 0; i < SM; ++i) {
+        if (rowb + i * 16 >= mlim) break;
+        const int row = rowb + i * 16 + l15;
+        if (row >= mlim) continue;
+        const int gI = row / p.rows_per_group, q = row - gI * p.rows_per_group;
+        const size_t orow = (size_t)gI * p.out_group + p.out_off + q;
+#pragma unroll
+        for (int j = 0; j < SN; ++j) {
+          int col = colb + j * 16 + 4 * lq, addn = p.N;
+          if (col >= p.N) continue;
+          void* Cb = p.C;
+          if (p.split_n > 0) rowmap_slice(p, col, addn, Cb);
+          const float4 bs = bs4[j];
+          float4 x = make_float4(acc[i][j][0] + bs.x, acc[i][j][1] + bs.y, acc[i][j][2] + bs.z, acc[i][j][3] + bs.w);
+          if (p.relu) x = make_float4(fmaxf(x.x, 0.f), fmaxf(x.y, 0.f), fmaxf(x.z, 0.f), fmaxf(x.w, 0.f));
+          if (p.add) {
+            const float4 ad = *(const float4*)(p.add + (size_t)q * addn + col);
+            x.x += ad.x; x.y += ad.y; x.z += ad.z; x.w += ad.w;
+          }
+          const size_t o = orow * p.ldc + col;
+          if (p.out16) {
+            uint2 u;
+            u.x = (uint32_t)f2t<T>(x.x) | ((uint32_t)f2t<T>(x.y) << 16);
+            u.y = (uint32_t)f2t<T>(x.z) | ((uint32_t)f2t<T>(x.w) << 16);
+            *(uint2*)((u16*)Cb + o) = u;
+          } else {
+            float* c = (float*)Cb + o;
+            if (p.accumulate) {
+              const float4 od = *(const float4*)c;
+              x.x += od.x; x.y += od.y; x.z += od.z; x.w += od.w;
+            }
+            *(float4*)c = x;
           }
         }
       }
@@ -1562,6 +1613,7 @@ hipError_t launch_T(const WmGemmArgs& a, int cfg, hipStream_t s) {
       case WM_EPI_GELU_T16: return launch_pp_E<T, WM_EPI_GELU_T16>(a, cfg, s);
       case WM_EPI_RESID: return launch_pp_E<T, WM_EPI_RESID>(a, cfg, s);
       case WM_EPI_QKV: return launch_pp_E<T, WM_EPI_QKV>(a, cfg, s);
+      case WM_EPI_ROWMAP_ADD: if (a.split_n > 0) return launch_pp_E<T, WM_EPI_ROWMAP_ADD>(a, cfg, s); break;   // (the plain form keeps gemm_nt_kernel)
       default: break;
     }
   }
@@ -1693,7 +1745,8 @@ static void plan_gemm(const WmGemmArgs& a, int& cfg, int& sched_b, bool& pp2_out
     // ping-pong v2 launches only (launch_T): backbone epilogues on the 256- / 192-row tiles
     const int ncu = wm_ncu();
     const int pp = wm_tune(WM_TUNE_GEMM_PP, 1);
-    const bool pp2 = (cfg == 4 || cfg == 5) && (pp == 1 || pp == 2 || pp == 4 || a.epi == WM_EPI_CONV) && (a.epi == WM_EPI_F32 || a.epi == WM_EPI_T16 || a.epi == WM_EPI_GELU_T16 || a.epi == WM_EPI_RESID || a.epi == WM_EPI_QKV || a.epi == WM_EPI_CONV);
+    const bool pp2 = (cfg == 4 || cfg == 5) && (pp == 1 || pp == 2 || pp == 4 || a.epi == WM_EPI_CONV) && (a.epi == WM_EPI_F32 || a.epi == WM_EPI_T16 || a.epi == WM_EPI_GELU_T16 || a.epi == WM_EPI_RESID || a.epi == WM_EPI_QKV || a.epi == WM_EPI_CONV ||
+                                                                                                          (a.epi == WM_EPI_ROWMAP_ADD && a.split_n > 0));
     const int ts = wm_tune(WM_TUNE_GEMM_SCHED, -1);   // -1 choose, 0 off (full-height tiles), > 0 that many bands
     if (pp2 && ts != 0) {
       // Measured (profiles/r04_gemm_timeline.md, `sched` rows): at M = 11008 the schedule takes 2.4 - 5.1 % off all four backbone
@@ -1723,6 +1776,11 @@ hipError_t wm_launch_gemm(const WmGemmArgs& a, hipStream_t s) {
   if (a.epi == WM_EPI_CONV && a.tc_k > 0 && (a.cv_h <= 0 || a.cv_w <= 0 || a.cv_cin % 64 || a.K != 4 * a.cv_cin || a.M % (a.cv_h * a.cv_w) || !a.cv_zero || a.tc_k > 4 ||
                                              a.N != a.tc_k * a.tc_k * 256 || a.ldc != 256 || a.cv_resid || a.cv_resid2))
     return hipErrorInvalidValue;
+  if (a.split_n != 0) {
+    if (a.epi != WM_EPI_ROWMAP_ADD || a.split_n < 0 || (a.split_n & 3) || a.N % a.split_n || a.N / a.split_n > 4 || a.accumulate) return hipErrorInvalidValue;
+    for (int i = 0; i < a.N / a.split_n; ++i)
+      if (!a.split_C[i]) return hipErrorInvalidValue;
+  }
   int cfg, sched_b;
   bool is_pp2;
   plan_gemm(a, cfg, sched_b, is_pp2);

@@ -42,6 +42,12 @@ struct WmGemmArgs {
                                                        // sched_bands row bands of floor / ceil(units / bands) units each, so that bands x column tiles fills whole
                                                        // rounds of the CUs; 0 = bands of the kernel's full tile height
   int rows_per_group, out_group, out_off, accumulate, out16, relu;  // WM_EPI_ROWMAP_ADD (out16: C is 16-bit, no accumulate; relu before add)
+  // WM_EPI_ROWMAP_ADD over several consumers' columns at once (the DPT heads' shared tap projection, tuning tap_shared): split_n > 0 cuts the
+  // N columns into N / split_n slices of split_n columns (split_n % 4 == 0, at most 4 slices); slice h lands in split_C[h] with row pitch ldc
+  // and columns [0, split_n) (C is unused), `add` is [rows_per_group][split_n] and is indexed by the column inside the slice; bias is [N].
+  // No accumulate.  Such launches may take the ping-pong kernel (the plain WM_EPI_ROWMAP_ADD launches keep gemm_nt_kernel).
+  int split_n;
+  void* split_C[4];
   int ct_k, ct_cout, ct_gh, ct_gw;                     // WM_EPI_CONVT
   WmQkvArgs qkv;                                       // WM_EPI_QKV (qkv.qkv unused; qkv.H*64 = D)
   // WM_EPI_CONV (round 4): a 3x3 / stride 1 / pad 1 convolution of a 16-BIT NHWC tensor A = x[n][y][x][cv_cin] as the ping-pong GEMM itself:
@@ -138,7 +144,7 @@ constexpr int WM_ATTN_HINT_TTL = 15;
 
 // ------------------------------------------------------------------ elementwise (elementwise.hip)
 // LayerNorm over the last dim with row remapping: out row (g*out_group + out_off + q) <- in row
-// (g*in_group + in_off + q), q < rows_per_group, g < groups.  Output 16-bit or f32.
+// (g*in_group + in_off + q), q < rows_per_group, g < groups.  Output 16-bit or f32.  w and b both null: no affine, y = (x - mean) * rstd.
 struct WmLnArgs {
   const float* x; void* y; const float* w; const float* b;
   int D, ld_in, ld_out; float eps;
@@ -396,6 +402,7 @@ hipError_t wm_launch_prune_gs(const float* means, const float* quats, const floa
   X(UP1_COMP, "up1_comp") \
   X(CONV_BM, "conv_bm") \
   X(RASTER_PPL, "raster_ppl") \
+  X(TAP_SHARED, "tap_shared") \
   X(ATTN_DEBUG_SKIP, "attn_debug_skip") \
   X(CONV_DBG, "conv_dbg") \
   X(DBG_SPLAT, "dbg_splat")

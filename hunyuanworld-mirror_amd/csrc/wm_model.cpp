@@ -81,6 +81,27 @@ static void free_up1comp(Up1Comp& u) {
 }
 static hipError_t build_up1comp(int dt, int F_, int Co, const float* woc1, const float* wout, const float* bout, Up1Comp& out, hipStream_t s);
 
+// The DPT heads' tap front shared between heads (tuning tap_shared): LayerNorm(2D) -> projects.i (dense_head.py:53,204-208) with each head's
+// LayerNorm affine folded into its projection, W'_h = W_h diag(gamma_h), b'_h = b_h + W_h beta_h, the heads' rows one under the other: all heads
+// then read the SAME normalised tap and one GEMM per tap serves them all (build_tapfold below)
+struct TapFold {
+  void* w16[4] = {nullptr, nullptr, nullptr, nullptr};      // per tap [nh * oc_i][Kp] 16-bit
+  float* bias[4] = {nullptr, nullptr, nullptr, nullptr};    // per tap [nh * oc_i]
+  std::vector<std::string> heads;                           // the group's head prefixes, in the order of their row blocks
+  bool valid = false;                                       // false: no group, or a folded weight left the operand type's range (direct form)
+};
+static void free_tapfold(TapFold& t) {
+  for (int i = 0; i < 4; ++i) {
+    if (t.w16[i]) (void)hipFree(t.w16[i]);
+    if (t.bias[i]) (void)hipFree(t.bias[i]);
+  }
+  t = TapFold();
+}
+// one tap: W[h] [oc][K], b[h] [oc], gamma[h], beta[h] [K] (host fp32) -> w16 [nh oc][Kp], bias [nh oc] on the device; *in_range = false (and nothing
+// allocated) when a folded weight or bias is not finite, or a weight exceeds the f16 maximum for f16 operands
+static hipError_t build_tapfold(int dt, int nh, int oc, int K, int Kp, const float* const* Wh, const float* const* bh, const float* const* gamma,
+                                const float* const* beta, void** w16_out, float** bias_out, bool* in_range);
+
 struct EvPair { hipEvent_t a, b; };
 
 struct Comm {
@@ -114,12 +135,14 @@ struct wm_handle {
   std::map<std::string, TconvPack> tconv;   // per head and level ("pts_head.0"): rebuilt by wm_reserve after a weight change
   bool tconv_valid = false;
   std::map<std::string, Up1Comp> up1comp;   // per head ("pts_head."), rebuilt with the token-conv packs
+  TapFold tapfold;                          // the heads' shared tap front, rebuilt with them
   std::vector<std::string> missing;  // names wm_finalize_weights filled with their init values
   // shape-dependent device tables (allocated inside the arena by plan())
   std::map<std::string, void*> buf;
   // the DPT heads are mutually independent: each runs on its own stream (forked/joined with events)
   hipStream_t hstream[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t hfork = nullptr, hjoin[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t hfront = nullptr;   // behind the heads' shared tap front on the caller's stream: the forked heads start from it
   // K/V all-gather of the sharded forward runs on its own queue, under the attention over the local keys
   hipStream_t cstream = nullptr;
   hipEvent_t cfork = nullptr, cjoin = nullptr;
@@ -156,6 +179,15 @@ bool ends_with(const std::string& s, const char* suf) {
   return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
 }
 bool starts_with(const std::string& s, const char* p) { return s.compare(0, strlen(p), p) == 0; }
+// the tensors build_tapfold composes (kept in fp32 on the host): a DPT head's norm.{weight,bias} and projects.i.{weight,bias}
+bool is_tapfold_source(const std::string& n) {
+  for (const char* p : {"pts_head.", "depth_head.", "norm_head.", "gs_head."})
+    if (starts_with(n, p)) {
+      const std::string r = n.substr(strlen(p));
+      return r == "norm.weight" || r == "norm.bias" || starts_with(r, "projects.");
+    }
+  return false;
+}
 
 enum WKind { WK_F32, WK_LIN16_BACKBONE, WK_LIN16_HEAD, WK_CONV16_HEAD, WK_CONVT16_HEAD };
 
@@ -360,15 +392,19 @@ std::vector<std::pair<std::string, size_t>> arena_layout(const wm_handle* h, con
   const int nslots = (c.enable_depth ? 1 : 0) + (c.enable_pts ? 1 : 0) + (c.enable_norm ? 1 : 0) + (c.enable_gs ? 1 : 0);
   const size_t big = ch * std::max<size_t>({64 * hw * (size_t)Fm, (size_t)d.H * d.W * (Fm / 2), (size_t)d.H * d.W * 32,
                                             c.enable_gs ? (size_t)d.H * d.W * c.gs_dim : 0}) * 4;
+  // the shared tap front (tuning tap_shared) projects every tap of every view chunk before the heads fork: with two or more heads the four
+  // projection outputs of a head hold all n views (dpt_P16b: the second tap's, which the direct form puts into dpt_P16 after the first's consumer)
+  const size_t pv = nslots >= 2 ? (size_t)d.n : ch;
   for (int sl = 0; sl < std::max(nslots, 1); ++sl) {
     const std::string x = "_h" + std::to_string(sl);
     auto addh = [&](const char* n, size_t b) { add((std::string(n) + x).c_str(), b); };
-    addh("dpt_T16", ch * hw * D2 * 2);
-    addh("dpt_P16", ch * hw * std::max(oc[0], oc[1]) * 2);
+    addh("dpt_T16", ch * hw * D2 * 2);   // (slot 0's is the shared front's normalised tap)
+    addh("dpt_P16", pv * hw * std::max(oc[0], oc[1]) * 2);
+    if (nslots >= 2) addh("dpt_P16b", pv * hw * oc[1] * 2);
     addh("dpt_f0", ch * 16 * hw * oc[0] * 4);
     addh("dpt_f1", ch * 4 * hw * oc[1] * 4);
-    addh("dpt_f2", ch * hw * oc[2] * 4);
-    addh("dpt_f3in", ch * hw * oc[3] * 4);
+    addh("dpt_f2", pv * hw * oc[2] * 4);
+    addh("dpt_f3in", pv * hw * oc[3] * 4);
     addh("dpt_f3", ch * (size_t)d.gh2 * d.gw2 * oc[3] * 4);
     addh("dpt_rn1", ch * 16 * hw * Fm * 4);
     addh("dpt_rn2", ch * 4 * hw * Fm * 4);
@@ -511,6 +547,8 @@ extern "C" void wm_destroy(wm_handle* h) {
   (void)hipSetDevice(h->device);
   for (auto& kv : h->tconv) free_tconv(kv.second);
   for (auto& kv : h->up1comp) free_up1comp(kv.second);
+  free_tapfold(h->tapfold);
+  if (h->hfront) (void)hipEventDestroy(h->hfront);
   for (auto& kv : h->w) {
     if (!kv.second.owned) continue;
     if (kv.second.f32) (void)hipFree(kv.second.f32);
@@ -566,14 +604,15 @@ extern "C" wm_status wm_set_weight(wm_handle* h, const char* name, const float* 
     HIPCHK(h, hipMemcpy(w.f32, host, numel * 4, hipMemcpyHostToDevice));
     if (ends_with(n, "pos_embed") || ends_with(n, "init_token")) w.host.assign(host, host + numel);
     if (n.find(".resize_layers.0.bias") != std::string::npos || n.find(".resize_layers.1.bias") != std::string::npos ||
-        ends_with(n, ".scratch.refinenet1.out_conv.bias"))
+        ends_with(n, ".scratch.refinenet1.out_conv.bias") || is_tapfold_source(n))
       w.host.assign(host, host + numel);
     return WM_OK;
   }
   // the ConvTranspose / layer_rn pairs that wm_reserve composes into one token-resolution GEMM (build_tconv) are kept in fp32 on the host
   if (n.find(".resize_layers.0.weight") != std::string::npos || n.find(".resize_layers.1.weight") != std::string::npos ||
       ends_with(n, ".scratch.layer1_rn.weight") || ends_with(n, ".scratch.layer2_rn.weight") ||
-      ends_with(n, ".scratch.refinenet1.out_conv.weight") || ends_with(n, ".scratch.output_conv1.weight"))   // (+ build_up1comp)
+      ends_with(n, ".scratch.refinenet1.out_conv.weight") || ends_with(n, ".scratch.output_conv1.weight") ||   // (+ build_up1comp)
+      is_tapfold_source(n))                                                                                    // (+ build_tapfold)
     w.host.assign(host, host + numel);
   const int dt = k == WK_LIN16_BACKBONE ? h->cfg.backbone_dtype : h->cfg.head_dtype;
   std::vector<uint16_t> r;
@@ -809,6 +848,39 @@ wm_status plan(wm_handle* h, const Dims& d) {
         if ((Co != 128 && Co != 64 && Co != 32) || w1->host.size() != (size_t)Co * F_ * 9 || wo->host.size() != (size_t)F_ * F_ || bo->host.size() != (size_t)F_) continue;
         HIPCHK(h, build_up1comp(c.head_dtype, F_, Co, w1->host.data(), wo->host.data(), bo->host.data(), h->up1comp[p], nullptr));
       }
+    // the heads' shared tap front: every enabled DPT head reads the same four taps through a LayerNorm(2D) and 1x1 projections of the same widths
+    free_tapfold(h->tapfold);
+    {
+      std::vector<std::string> grp;   // in the order the forward runs them (and numbers their workspace slots)
+      if (c.enable_depth) grp.push_back("depth_head.");
+      if (c.enable_pts) grp.push_back("pts_head.");
+      if (c.enable_norm) grp.push_back("norm_head.");
+      if (c.enable_gs) grp.push_back("gs_head.");
+      const int D2 = 2 * d.D, Kp = ru(D2, 64);
+      bool ok = grp.size() >= 2 && grp.size() <= 4;
+      std::vector<const float*> Wh, bh, gm, bt;
+      TapFold tf;
+      for (int i = 0; i < 4 && ok; ++i) {
+        const int oci = c.dpt_out_channels[i];
+        Wh.clear(); bh.clear(); gm.clear(); bt.clear();
+        for (const std::string& p : grp) {
+          const Weight* w = W(h, p + "projects." + std::to_string(i) + ".weight");
+          const Weight* b = W(h, p + "projects." + std::to_string(i) + ".bias");
+          const Weight* g = W(h, p + "norm.weight");
+          const Weight* e = W(h, p + "norm.bias");
+          // (a head whose tensors are missing or of another size keeps the whole group on the direct form)
+          if (!w || !b || !g || !e || w->host.size() != (size_t)oci * D2 || b->host.size() != (size_t)oci || g->host.size() != (size_t)D2 ||
+              e->host.size() != (size_t)D2 || w->k16 != Kp || (oci & 3)) { ok = false; break; }
+          Wh.push_back(w->host.data()); bh.push_back(b->host.data()); gm.push_back(g->host.data()); bt.push_back(e->host.data());
+        }
+        if (!ok) break;
+        bool in_range = false;
+        HIPCHK(h, build_tapfold(c.head_dtype, (int)grp.size(), oci, D2, Kp, Wh.data(), bh.data(), gm.data(), bt.data(), &tf.w16[i], &tf.bias[i], &in_range));
+        if (!in_range) ok = false;   // gamma now scales a weight: out of the operand type's range -> the direct form for this handle
+      }
+      if (ok) { tf.heads = grp; tf.valid = true; h->tapfold = tf; }
+      else free_tapfold(tf);
+    }
     h->tconv_valid = true;
   }
   // camera init token broadcast [nt][12]
@@ -1285,6 +1357,83 @@ done:
   if (e != hipSuccess) free_up1comp(out);
   return e;
 }
+static hipError_t build_tapfold(int dt, int nh, int oc, int K, int Kp, const float* const* Wh, const float* const* bh, const float* const* gamma,
+                                const float* const* beta, void** w16_out, float** bias_out, bool* in_range) {
+  // fp64 on the host, one rounding to the operand type
+  *w16_out = nullptr; *bias_out = nullptr; *in_range = true;
+  std::vector<uint16_t> w16((size_t)nh * oc * Kp, 0);
+  std::vector<float> bias((size_t)nh * oc);
+  for (int hd = 0; hd < nh; ++hd)
+    for (int r = 0; r < oc; ++r) {
+      const float* wr = Wh[hd] + (size_t)r * K;
+      double acc = (double)bh[hd][r];
+      uint16_t* o = &w16[((size_t)hd * oc + r) * Kp];
+      for (int k = 0; k < K; ++k) {
+        const float wf = (float)((double)wr[k] * (double)gamma[hd][k]);
+        if (!std::isfinite(wf) || (dt == WM_DT_F16 && std::fabs(wf) > 65504.0f) || (dt == WM_DT_BF16 && std::fabs(wf) > 3.3895314e38f)) *in_range = false;
+        o[k] = h_to16(wf, dt);
+        acc += (double)wr[k] * (double)beta[hd][k];
+      }
+      bias[(size_t)hd * oc + r] = (float)acc;
+      if (!std::isfinite(bias[(size_t)hd * oc + r])) *in_range = false;
+    }
+  if (!*in_range) return hipSuccess;
+  hipError_t e = hipMalloc(w16_out, w16.size() * 2);
+  if (e == hipSuccess) e = hipMalloc((void**)bias_out, bias.size() * 4);
+  if (e == hipSuccess) e = hipMemcpy(*w16_out, w16.data(), w16.size() * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(*bias_out, bias.data(), bias.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (*w16_out) (void)hipFree(*w16_out);
+    if (*bias_out) (void)hipFree(*bias_out);
+    *w16_out = nullptr; *bias_out = nullptr;
+  }
+  return e;
+}
+
+// One tap of the shared front for n views: xhat = LayerNorm without affine of the tap's patch rows (hw of P per view, from row psi) as a 16-bit
+// tensor, then ONE projection GEMM over all heads' folded rows; head k's oc columns (+ the tap's position table, dense_head.py:204-208) land in
+// dst[k] [n hw][oc], 16-bit (out16) or fp32
+wm_status tap_front_one(Ctx& c, const float* tap, void* xhat, const void* w16, const float* bias, const float* pos, int nh, int oc, int out16,
+                        void* const* dst, int n, int hw, int P, int psi, int D2) {
+  wm_status st = layernorm(c, tap, D2, xhat, D2, nullptr, nullptr, D2, 1e-5f, n, hw, P, psi, hw, 0, 0, c.hdt);
+  if (st) return st;
+  WmGemmArgs ex;
+  memset(&ex, 0, sizeof(ex));
+  ex.rows_per_group = hw; ex.out_group = hw; ex.out_off = 0; ex.add = pos; ex.out16 = out16;
+  ex.split_n = oc;
+  for (int k = 0; k < nh; ++k) ex.split_C[k] = dst[k];
+  return gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, xhat, D2, w16, ru(D2, 64), nullptr, oc, bias, nullptr, n * hw, nh * oc, D2, &ex);
+}
+
+// where head `slot` finds the projection of tap i for the views from v0 on (the shared front's outputs; all n views of the rank)
+void* tap_front_dst(wm_handle* h, const Dims& d, int slot, int i, int v0) {
+  const int32_t* oc = h->cfg.dpt_out_channels;
+  static const char* const names[4] = {"dpt_P16_h", "dpt_P16b_h", "dpt_f2_h", "dpt_f3in_h"};
+  char* base = (char*)h->buf.at(std::string(names[i]) + std::to_string(slot));
+  return base + (size_t)v0 * d.hw * oc[i] * (i < 2 ? 2 : 4);
+}
+
+// the shared front of all heads of the group, every view chunk, on c.s (before the heads fork)
+wm_status tap_front(Ctx& c) {
+  wm_handle* h = c.h;
+  const Dims& d = c.d;
+  const TapFold& tf = h->tapfold;
+  const int D2 = 2 * d.D, nh = (int)tf.heads.size();
+  void* xhat = h->buf.at("dpt_T16_h0");
+  for (int v0 = 0; v0 < d.n; v0 += d.chunk) {
+    const int n = std::min(d.chunk, d.n - v0);
+    for (int i = 0; i < 4; ++i) {
+      void* dst[4] = {nullptr, nullptr, nullptr, nullptr};
+      for (int k = 0; k < nh; ++k) dst[k] = tap_front_dst(h, d, k, i, v0);
+      const float* tap = B<float>(h, ("tap" + std::to_string(i)).c_str()) + (size_t)v0 * d.P * D2;
+      wm_status st = tap_front_one(c, tap, xhat, tf.w16[i], tf.bias[i], B<float>(h, ("dpt_pos" + std::to_string(i)).c_str()), nh,
+                                   h->cfg.dpt_out_channels[i], i < 2 ? 1 : 0, dst, n, d.hw, d.P, d.psi, D2);
+      if (st) return st;
+    }
+  }
+  return WM_OK;
+}
+
 // rn = tconv(tokens): tokens16 [n][gh][gw][Cin] (16-bit) -> out fp32 [n][k gh][k gw][256]
 static hipError_t launch_tconv(const TconvPack& t, int dt, const void* tokens16, float* out, int n, int gh, int gw, const void* zero16, hipStream_t s) {
   WmGemmArgs g;
@@ -1361,7 +1510,8 @@ wm_status out_conv(Ctx& c, const std::string& name, const float* x2, bool x2_is_
 
 // DPTHead (dense_head.py:107-295) for views [v0, v0+n) of this rank
 wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, bool is_gs, float* out_attr, float* out_conf,
-                   const float* img, const wm_outputs* out, int first_view, int slot) {
+                   const float* img, const wm_outputs* out, int first_view, int slot, bool front_done = false) {
+  // front_done: the shared front (tap_front) has already normalised and projected the four taps of every view for this head's slot
   const std::string sx = "_h" + std::to_string(slot);
   auto HB = [&](const char* n) { return (float*)c.h->buf.at(std::string(n) + sx); };
   wm_handle* h = c.h;
@@ -1374,22 +1524,26 @@ wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, b
   wm_status st;
   for (int v0 = 0; v0 < d.n; v0 += d.chunk) {
     const int n = std::min(d.chunk, d.n - v0);
-    float* feats[4] = {HB("dpt_f0"), HB("dpt_f1"), HB("dpt_f2"), HB("dpt_f3")};
+    float* feats[4] = {HB("dpt_f0"), HB("dpt_f1"), front_done ? (float*)tap_front_dst(h, d, slot, 2, v0) : HB("dpt_f2"), HB("dpt_f3")};
     bool tconv_done[4] = {false, false, false, false};
     for (int i = 0; i < 4; ++i) {
       const float* tap = B<float>(h, ("tap" + std::to_string(i)).c_str()) + (size_t)v0 * d.P * D2;
       void* T16 = HB("dpt_T16");
-      st = layernorm(c, tap, D2, T16, D2, F(h, p + "norm.weight"), F(h, p + "norm.bias"), D2, 1e-5f, n, hw, d.P, d.psi, hw, 0, 0, c.hdt);
-      if (st) return st;
+      if (!front_done) {
+        st = layernorm(c, tap, D2, T16, D2, F(h, p + "norm.weight"), F(h, p + "norm.bias"), D2, 1e-5f, n, hw, d.P, d.psi, hw, 0, 0, c.hdt);
+        if (st) return st;
+      }
       const std::string pj = p + "projects." + std::to_string(i);
       WmGemmArgs ex;
       memset(&ex, 0, sizeof(ex));
       ex.rows_per_group = hw; ex.out_group = hw; ex.out_off = 0; ex.add = B<float>(h, ("dpt_pos" + std::to_string(i)).c_str());
       if (i < 2) {  // feeds a k==stride ConvTranspose (GEMM): 16-bit output
         ex.out16 = 1;
-        void* P16 = HB("dpt_P16");
-        st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, W16(h, pj + ".weight"), D2, P16, oc[i], F(h, pj + ".bias"), nullptr, n * hw, oc[i], D2, &ex);
-        if (st) return st;
+        void* P16 = front_done ? tap_front_dst(h, d, slot, i, v0) : (void*)HB("dpt_P16");
+        if (!front_done) {
+          st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, W16(h, pj + ".weight"), D2, P16, oc[i], F(h, pj + ".bias"), nullptr, n * hw, oc[i], D2, &ex);
+          if (st) return st;
+        }
         auto tc = h->tconv.find(p + std::to_string(i));
         tconv_done[i] = wm_tune(WM_TUNE_TCONV, 1) != 0 && !is_gs && F_ == 256 && tc != h->tconv.end() && tc->second.w16 != nullptr;
         if (tconv_done[i]) {   // ConvTranspose and layer{i+1}_rn as one GEMM at the token resolution, straight into rn[i]
@@ -1405,9 +1559,11 @@ wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, b
         st = gemm(c, c.hdt, WM_EPI_CONVT, P16, oc[i], W16(h, rs + ".weight"), oc[i], feats[i], 0, F(h, rs + ".bias"), nullptr, n * hw, k * k * oc[i], oc[i], &ct);
         if (st) return st;
       } else {
-        float* dst = i == 2 ? feats[2] : HB("dpt_f3in");
-        st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, W16(h, pj + ".weight"), D2, dst, oc[i], F(h, pj + ".bias"), nullptr, n * hw, oc[i], D2, &ex);
-        if (st) return st;
+        float* dst = i == 2 ? feats[2] : front_done ? (float*)tap_front_dst(h, d, slot, 3, v0) : HB("dpt_f3in");
+        if (!front_done) {
+          st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, W16(h, pj + ".weight"), D2, dst, oc[i], F(h, pj + ".bias"), nullptr, n * hw, oc[i], D2, &ex);
+          if (st) return st;
+        }
         if (i == 3) {
           st = conv(c, dst, p + "resize_layers.3", true, nullptr, false, nullptr, feats[3], n, gh, gw, 3, 2, 1, false);
           if (st) return st;
@@ -1701,12 +1857,25 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
     // a hardware queue and ran one after the other — the kernel trace of a timed forward showed one head done after 7.5 ms and the other
     // two, serialised, after 12.3 ms (profiles/r04_head_phase_queues.md).  Side heads are enqueued first, the caller's stream joins them
     // only behind its own head's launches.
+    // The heads' front — LayerNorm of each tap and its 1x1 projection — once for all heads on the caller's stream (tuning tap_shared = 0: every
+    // head normalises and projects for itself).  Taken when the folded weights exist (wm_reserve: two or more heads, in range) and the call
+    // runs exactly the group's heads, whose order numbers the workspace slots.
+    bool front = wm_tune(WM_TUNE_TAP_SHARED, 1) != 0 && h->tapfold.valid && h->tapfold.heads.size() == jobs.size();
+    for (size_t k = 0; front && k < jobs.size(); ++k) front = h->tapfold.heads[k] == jobs[k].p;
+    if (front) {
+      st = tap_front(c);
+      if (st) return st;
+      if (!serial) {
+        if (!h->hfront) LCHK(c, hipEventCreateWithFlags(&h->hfront, hipEventDisableTiming));
+        LCHK(c, hipEventRecord(h->hfront, s));
+      }
+    }
     const size_t main_k = jobs.empty() || wm_tune(WM_TUNE_HEADS_MAIN, 1) == 0 ? (size_t)-1 : jobs.size() - 1;   // (tuning heads_main = 0: every head forks, round 3's form — A/B)
     auto run_head = [&](size_t k, hipStream_t hs) -> wm_status {
       Ctx hc = c;
       hc.s = hs;
       if (jobs[k].gs && cam_async) LCHK(c, hipStreamWaitEvent(hs, h->camjoin, 0));  // the splats are unprojected with the predicted cameras
-      return dpt_head(hc, jobs[k].p, jobs[k].F, jobs[k].od, jobs[k].act, jobs[k].gs, jobs[k].attr, jobs[k].conf, img, out, first_view, (int)k);
+      return dpt_head(hc, jobs[k].p, jobs[k].F, jobs[k].od, jobs[k].act, jobs[k].gs, jobs[k].attr, jobs[k].conf, img, out, first_view, (int)k, front);
     };
     const bool fork_heads = !serial && (jobs.size() > 1 || cam_async);
     for (size_t k = 0; k < jobs.size(); ++k) {
@@ -1716,7 +1885,7 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
         if (!h->hstream[k]) LCHK(c, hipStreamCreateWithFlags(&h->hstream[k], hipStreamNonBlocking));
         if (!h->hjoin[k]) LCHK(c, hipEventCreateWithFlags(&h->hjoin[k], hipEventDisableTiming));
         hs = h->hstream[k];
-        LCHK(c, hipStreamWaitEvent(hs, h->hfork, 0));
+        LCHK(c, hipStreamWaitEvent(hs, front ? h->hfront : h->hfork, 0));
       }
       st = run_head(k, hs);
       if (st) return st;
@@ -2523,6 +2692,60 @@ extern "C" wm_status wm_op_gemm_rowmap(int dtype, const void* A, const void* Wp,
   a.dtype = dtype; a.epi = WM_EPI_ROWMAP_ADD;
   a.rows_per_group = rows_per_group; a.out_group = out_group; a.out_off = out_off; a.accumulate = accumulate; a.out16 = out16; a.relu = relu;
   return op_status(wm_launch_gemm(a, (hipStream_t)stream));
+}
+// The DPT heads' tap front for one tap (dense_head.py:53,204-208), both forms the forward has: shared = 0 every head normalises the tap with its
+// own affine and projects it; shared = 1 one LayerNorm without affine and one GEMM over the heads' folded weights (build_tapfold), unless a folded
+// weight leaves the operand type's range — then the direct form runs (*ran_shared tells).  Host fp32 weights, device tap / pos / outputs.
+extern "C" wm_status wm_op_dpt_tap_front(int dtype, const float* tap, int n, int P, int psi, int hw, int D2, int nheads, int oc,
+                                         const float* const* norm_w, const float* const* norm_b, const float* const* proj_w,
+                                         const float* const* proj_b, const float* pos, int out16, int shared, void* const* out, int* ran_shared,
+                                         void* stream) {
+  if (!tap || !norm_w || !norm_b || !proj_w || !proj_b || !out || n <= 0 || hw <= 0 || psi < 0 || P < psi + hw || D2 <= 0 || D2 % 64 || nheads < 1 ||
+      nheads > 4 || oc <= 0 || (oc & 3) || (dtype != WM_DT_BF16 && dtype != WM_DT_F16))
+    return WM_ERR_INVALID;
+  for (int k = 0; k < nheads; ++k)
+    if (!norm_w[k] || !norm_b[k] || !proj_w[k] || !proj_b[k] || !out[k]) return WM_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  wm_handle tmp;
+  Ctx c{&tmp, Dims(), s, dtype, dtype};
+  if (ran_shared) *ran_shared = 0;
+  std::vector<void*> dev;
+  auto dalloc = [&](size_t bytes) -> void* { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; dev.push_back(q); return q; };
+  auto finish = [&](wm_status st) {
+    (void)hipStreamSynchronize(s);
+    for (void* q : dev) (void)hipFree(q);
+    return st;
+  };
+  void* xhat = dalloc((size_t)n * hw * D2 * 2);
+  if (!xhat) return finish(WM_ERR_HIP);
+  if (shared) {
+    void* w16 = nullptr; float* bias = nullptr; bool in_range = false;
+    if (build_tapfold(dtype, nheads, oc, D2, D2, proj_w, proj_b, norm_w, norm_b, &w16, &bias, &in_range) != hipSuccess) return finish(WM_ERR_HIP);
+    if (in_range) {
+      dev.push_back(w16); dev.push_back(bias);
+      if (ran_shared) *ran_shared = 1;
+      return finish(tap_front_one(c, tap, xhat, w16, bias, pos, nheads, oc, out16, out, n, hw, P, psi, D2));
+    }
+  }
+  for (int k = 0; k < nheads; ++k) {   // the direct form, as dpt_head runs it
+    float* gw = (float*)dalloc((size_t)D2 * 4); float* gb = (float*)dalloc((size_t)D2 * 4); float* pb = (float*)dalloc((size_t)oc * 4);
+    void* w16 = dalloc((size_t)oc * D2 * 2);
+    if (!gw || !gb || !pb || !w16) return finish(WM_ERR_HIP);
+    std::vector<uint16_t> r((size_t)oc * D2);
+    for (size_t i = 0; i < r.size(); ++i) r[i] = h_to16(proj_w[k][i], dtype);
+    if (hipMemcpy(gw, norm_w[k], (size_t)D2 * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(gb, norm_b[k], (size_t)D2 * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pb, proj_b[k], (size_t)oc * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(w16, r.data(), r.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
+      return finish(WM_ERR_HIP);
+    wm_status st = layernorm(c, tap, D2, xhat, D2, gw, gb, D2, 1e-5f, n, hw, P, psi, hw, 0, 0, dtype);
+    if (st) return finish(st);
+    WmGemmArgs ex;
+    memset(&ex, 0, sizeof(ex));
+    ex.rows_per_group = hw; ex.out_group = hw; ex.out_off = 0; ex.add = pos; ex.out16 = out16;
+    st = gemm(c, dtype, WM_EPI_ROWMAP_ADD, xhat, D2, w16, D2, out[k], oc, pb, nullptr, n * hw, oc, D2, &ex);
+    if (st) return finish(st);
+    if (hipStreamSynchronize(s) != hipSuccess) return finish(WM_ERR_HIP);   // xhat is reused by the next head
+  }
+  return finish(WM_OK);
 }
 extern "C" wm_status wm_op_gemm_convt(int dtype, const void* A, const void* Wp, float* C, const float* bias, int M, int N, int K, int ct_k,
                                       int ct_cout, int ct_gh, int ct_gw, void* stream) {

@@ -208,6 +208,16 @@ wm_status wm_op_vgt_special(float* X, const float* cam_tok, const float* reg_tok
  * accumulate); ldc in elements of C.  (patch embed + pos table, depth-prior MLP into the view tokens, the DPT heads' projections) */
 wm_status wm_op_gemm_rowmap(int dtype, const void* A, const void* W, void* C, const float* bias, const float* add, int M, int N, int K,
                             int ldc, int rows_per_group, int out_group, int out_off, int accumulate, int out16, int relu, void* stream);
+/* The front of the DPT heads for one tap (dense_head.py:53,204-208): out[k] [n hw][oc] = Linear_k(LayerNorm_k(tap patch rows)) + pos, for nheads
+ * (1-4) heads reading the same tap f32 [n][P][D2] (patch rows psi .. psi + hw of every view); pos f32 [hw][oc] or NULL; out 16-bit when out16,
+ * else f32.  norm_w / norm_b [D2], proj_w [oc][D2], proj_b [oc]: HOST fp32, one pointer per head; tap, pos, out[k]: device.
+ * shared = 0: every head normalises with its own affine and projects (the forward with tuning tap_shared = 0).  shared = 1: the forward's default
+ * form — one LayerNorm without affine, and ONE GEMM over the heads' weights W_k diag(norm_w_k) with bias proj_b_k + W_k norm_b_k (composed in
+ * fp64, rounded once); when a composed weight is not finite in the operand type (or exceeds 65 504 for f16) the direct form runs instead.
+ * *ran_shared (optional) tells which form ran.  Synchronises the stream (it owns scratch device memory). */
+wm_status wm_op_dpt_tap_front(int dtype, const float* tap, int n, int P, int psi, int hw, int D2, int nheads, int oc,
+                              const float* const* norm_w, const float* const* norm_b, const float* const* proj_w, const float* const* proj_b,
+                              const float* pos, int out16, int shared, void* const* out, int* ran_shared, void* stream);
 /* GEMM with the ConvTranspose2d(kernel = stride = ct_k) pixel-shuffle epilogue (dense_head.py:57-66): A 16-bit [n*ct_gh*ct_gw][K] tokens,
  * W 16-bit [ct_k*ct_k*ct_cout][K] with row (ii*ct_k + jj)*ct_cout + co, bias f32 [ct_cout] -> C f32 NHWC [n][ct_gh*ct_k][ct_gw*ct_k][ct_cout] */
 wm_status wm_op_gemm_convt(int dtype, const void* A, const void* W, float* C, const float* bias, int M, int N, int K, int ct_k, int ct_cout,
@@ -630,6 +640,11 @@ wm_status wm_photometric_loss_backward(const float* img1, const int64_t* strides
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
 int wm_set_tuning(const char* key, int value);
+/* Key "tap_shared" (default 1): the DPT heads' front.  1: the taps are normalised ONCE (LayerNorm without affine) on the caller's stream and one
+ * projection GEMM per tap serves every head, each head's LayerNorm affine folded into its projection weights by wm_reserve (W diag(gamma),
+ * b + W beta, fp64 on the host, one rounding) — taken when two or more DPT heads are enabled, the call asks for all of them, and every folded
+ * weight is finite in the head operand type (|W gamma| <= 65 504 for f16 heads); otherwise, and with 0, every head normalises and projects
+ * the taps itself.  The two forms differ by one operand rounding: round(xhat gamma + beta) x round(W) against round(xhat) x round(W gamma). */
 
 /* host helper: fp32 -> 16-bit (round to nearest even), for building test operands */
 void wm_host_to_16(const float* in, uint16_t* out, size_t n, int dtype);
