@@ -6,6 +6,7 @@ from .geometry import (create_confidence_mask, depth_edge, depth_to_world_coords
 from .ingest import load_and_preprocess_images, preprocess_rgb  # noqa: F401
 from .rasterization import Rasterizer, rasterization  # noqa: F401
 from .losses import fused_ssim, photometric_loss  # noqa: F401
+from .bilagrid import BilateralGrid, slice, total_variation_loss  # noqa: F401
 from .strategy import DefaultStrategy  # noqa: F401
 from .strategy_mcmc import MCMCStrategy  # noqa: F401
 from .pose import CameraOptModule  # noqa: F401

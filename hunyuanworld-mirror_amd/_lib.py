@@ -69,6 +69,8 @@ EXPORTS = [
     "wm_rasterize_splats_opt", "wm_rasterize_backward_workspace_bytes_opt", "wm_rasterize_splats_backward_opt",
     "wm_densify_accumulate", "wm_densify_plan_workspace_bytes", "wm_densify_plan", "wm_densify_gather",
     "wm_mcmc_inject_noise", "wm_mcmc_partition_workspace_bytes", "wm_mcmc_partition", "wm_mcmc_relocation", "wm_mcmc_scatter", "wm_mcmc_zero_rows",
+    "wm_bilagrid_slice", "wm_bilagrid_slice_backward_workspace_bytes", "wm_bilagrid_slice_backward", "wm_bilagrid_tv_workspace_bytes",
+    "wm_bilagrid_tv", "wm_bilagrid_tv_backward",
 ]
 
 _lib = None
@@ -227,6 +229,18 @@ def lib() -> C.CDLL:
     L.wm_photometric_loss.restype = i32
     L.wm_photometric_loss_backward.argtypes = [vp, i64p, vp, i64p, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
     L.wm_photometric_loss_backward.restype = i32
+    L.wm_bilagrid_slice.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp]
+    L.wm_bilagrid_slice.restype = i32
+    L.wm_bilagrid_slice_backward_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
+    L.wm_bilagrid_slice_backward_workspace_bytes.restype = C.c_size_t
+    L.wm_bilagrid_slice_backward.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.wm_bilagrid_slice_backward.restype = i32
+    L.wm_bilagrid_tv_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    L.wm_bilagrid_tv_workspace_bytes.restype = C.c_size_t
+    L.wm_bilagrid_tv.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]
+    L.wm_bilagrid_tv.restype = i32
+    L.wm_bilagrid_tv_backward.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.wm_bilagrid_tv_backward.restype = i32
     L.wm_preprocess_image_size.argtypes = [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.wm_preprocess_image_size.restype = i32
     L.wm_preprocess_image_workspace_bytes.argtypes = [i32, i32, i32, i32]

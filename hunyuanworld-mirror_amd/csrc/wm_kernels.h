@@ -360,6 +360,22 @@ hipError_t wm_launch_photoloss_fwd(const WmPhotoLossArgs& a, int want_backward, 
 // backward: g_ssim / g_l1 device floats; grad_img1 is written with img1's strides
 hipError_t wm_launch_photoloss_bwd(const WmPhotoLossArgs& a, const float* g_ssim, const float* g_l1, float* grad_img1, hipStream_t s);
 
+// ------------------------------------------------------------------ bilateral-grid slice and total variation (bilagrid.hip)
+// grids [G,12,L,Hg,Wg]; grid_idx int32 [B] on the device; xy [B,n,2], rgb [B,n,3] contiguous fp32
+constexpr int WM_BILAGRID_MAX_CELLS = 4096;   // L * Hg * Wg the grid backward keeps in registers (four cells per thread of a 1024-thread block)
+struct WmBilagridArgs {
+  const float* grids; const int* grid_idx; const float* xy; const float* rgb;
+  int G, L, Hg, Wg, B, n;
+};
+size_t wm_bilagrid_bwd_workspace_bytes(int G, int L, int Hg, int Wg, int B, int n);   // 0 for sizes the launchers refuse
+hipError_t wm_launch_bilagrid_slice(const WmBilagridArgs& a, float* out, hipStream_t s);
+// v_grids / v_rgb may be null (that gradient is not computed); ws is touched for v_grids only
+hipError_t wm_launch_bilagrid_slice_bwd(const WmBilagridArgs& a, const float* v_out, float* v_grids, float* v_rgb, void* ws, size_t ws_bytes,
+                                        hipStream_t s);
+size_t wm_bilagrid_tv_ws_bytes(int B, int C, int L, int H, int W);
+hipError_t wm_launch_bilagrid_tv(const float* x, int B, int C, int L, int H, int W, float* out, void* ws, size_t ws_bytes, hipStream_t s);
+hipError_t wm_launch_bilagrid_tv_bwd(const float* x, int B, int C, int L, int H, int W, const float* g, float* v_x, hipStream_t s);
+
 // ------------------------------------------------------------------ voxel merge of splats (splat_prune.hip)
 size_t wm_prune_workspace_bytes(size_t N);
 hipError_t wm_launch_prune_gs(const float* means, const float* quats, const float* scales, const float* opac, const float* sh,

@@ -2413,6 +2413,39 @@ extern "C" wm_status wm_photometric_loss_backward(const float* img1, const int64
   const hipError_t e = wm_launch_photoloss_bwd(a, g_ssim, g_l1, grad_img1, (hipStream_t)stream);
   return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP;
 }
+static wm_status bilagrid_status(hipError_t e) { return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP; }
+static bool bilagrid_args(WmBilagridArgs& a, const float* grids, int G, int L, int Hg, int Wg, const int* grid_idx, const float* xy, const float* rgb,
+                          int B, int n) {
+  if (!grids || !grid_idx || !xy || !rgb) return false;
+  a.grids = grids; a.grid_idx = grid_idx; a.xy = xy; a.rgb = rgb; a.G = G; a.L = L; a.Hg = Hg; a.Wg = Wg; a.B = B; a.n = n;
+  return true;       // the sizes are checked by the launcher, before it launches anything
+}
+extern "C" wm_status wm_bilagrid_slice(const float* grids, int G, int L, int Hg, int Wg, const int* grid_idx, const float* xy, const float* rgb,
+                                       int B, int n, float* out, void* stream) {
+  WmBilagridArgs a;
+  if (!out || !bilagrid_args(a, grids, G, L, Hg, Wg, grid_idx, xy, rgb, B, n)) return WM_ERR_INVALID;
+  return bilagrid_status(wm_launch_bilagrid_slice(a, out, (hipStream_t)stream));
+}
+extern "C" size_t wm_bilagrid_slice_backward_workspace_bytes(int G, int L, int Hg, int Wg, int B, int n) {
+  return wm_bilagrid_bwd_workspace_bytes(G, L, Hg, Wg, B, n);
+}
+extern "C" wm_status wm_bilagrid_slice_backward(const float* grids, int G, int L, int Hg, int Wg, const int* grid_idx, const float* xy,
+                                                const float* rgb, int B, int n, const float* v_out, float* v_grids, float* v_rgb,
+                                                void* workspace, size_t workspace_bytes, void* stream) {
+  WmBilagridArgs a;
+  if (!v_out || !bilagrid_args(a, grids, G, L, Hg, Wg, grid_idx, xy, rgb, B, n)) return WM_ERR_INVALID;
+  return bilagrid_status(wm_launch_bilagrid_slice_bwd(a, v_out, v_grids, v_rgb, workspace, workspace_bytes, (hipStream_t)stream));
+}
+extern "C" size_t wm_bilagrid_tv_workspace_bytes(int B, int C, int L, int H, int W) { return wm_bilagrid_tv_ws_bytes(B, C, L, H, W); }
+extern "C" wm_status wm_bilagrid_tv(const float* x, int B, int C, int L, int H, int W, float* out, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  if (!x || !out) return WM_ERR_INVALID;
+  return bilagrid_status(wm_launch_bilagrid_tv(x, B, C, L, H, W, out, workspace, workspace_bytes, (hipStream_t)stream));
+}
+extern "C" wm_status wm_bilagrid_tv_backward(const float* x, int B, int C, int L, int H, int W, const float* g, float* v_x, void* stream) {
+  if (!x || !g || !v_x) return WM_ERR_INVALID;
+  return bilagrid_status(wm_launch_bilagrid_tv_bwd(x, B, C, L, H, W, g, v_x, (hipStream_t)stream));
+}
 extern "C" wm_status wm_op_layernorm(const float* x, void* y, const float* w, const float* b, int rows, int D, float eps, int out_f32,
                                      int dtype, void* stream) {
   WmLnArgs a;

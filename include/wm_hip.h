@@ -636,6 +636,40 @@ wm_status wm_photometric_loss_backward(const float* img1, const int64_t* strides
                                        int C, int H, int W, int padding_valid, const float* g_ssim, const float* g_l1,
                                        float* grad_img1, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* Bilateral-grid appearance correction of the post-3DGS trainer (gsplat's simple_trainer_worldmirror.py:812-814 under
+ * --use_bilateral_grid, :555-570 for the loss term).  The trainer's --use_fused_bilagrid package is CUDA-only; these entries are
+ * the semantics of its pure-torch twin, examples/lib_bilagrid.py.
+ * slice (lib_bilagrid.py:180-244 with BilateralGrid.forward :310-365 and color_affine_transform :141-154):
+ *   grids fp32 [G,12,L,Hg,Wg], channel 4 r + c = entry (r, c) of a 3 x 4 matrix; grid_idx int32 [B] ON THE DEVICE; xy [B,n,2] in
+ *   [0,1], rgb [B,n,3], out [B,n,3], all contiguous fp32.  Sample j of row b reads grid grid_idx[b] at
+ *   (2 (x - .5), 2 (y - .5), 2 (.299 r + .587 g + .114 b) - 1) as F.grid_sample(mode="bilinear", align_corners=True,
+ *   padding_mode="border") does: u = (c + 1) / 2 * (size - 1) clamped to [0, size - 1], trilinear; the 12 numbers A give
+ *   out = A[:, :3] rgb + A[:, 3].  The [.., 3, 4] matrices ("rgb_affine_mats") are never written anywhere.
+ *   A row whose index is outside [0, G) reads no grid: its out (and its v_rgb) are NaN and it adds nothing to v_grids.
+ * backward: v_out [B,n,3].  v_grids [G,12,L,Hg,Wg]: EVERY element is written (zeros for a grid that no row names; rows naming one
+ *   grid sum); v_rgb [B,n,3] = A[:, :3]^T v_out + the term through the guidance coordinate, which is zero where that coordinate
+ *   sits on or outside the clamp range (torch's rule).  Either of v_grids, v_rgb may be NULL: that gradient is not computed.  xy gets none.
+ *   The workspace (needed for v_grids only) holds one partial grid gradient per block: 48 L Hg Wg bytes times at most 256 blocks
+ *   (B rows x segments per row).  Sums run in a fixed order (sample, row, segment), no atomics: identical bits run to run.
+ * total variation (lib_bilagrid.py:161-177) of x fp32 [B,C,L,H,W], contiguous: the sum over the three trailing axes of
+ *   sum (x shifted by one - x)^2 / max(C L H W with that axis one shorter, 1), divided by B -> *out (device float).
+ *   Backward: v_x (same shape, every element written) = *g (device float) * d tv / d x.  The workspace of the value call holds one
+ *   double per block (at most 8 KiB).
+ * LIMITS: L * Hg * Wg <= 4096 cells and each of L, Hg, Wg <= 1024 (the grid gradient keeps a block's cells in registers; the
+ *   default 16 x 16 x 8 is 2048); B * n < 2^29.  Larger shapes are refused by all three slice entries, there is no slower path.
+ * Every call is asynchronous on stream and never synchronises the host.  WM_ERR_INVALID, before anything is launched: a size <= 0,
+ * a shape beyond the limits, a null pointer where none is allowed, a workspace that is too small. */
+wm_status wm_bilagrid_slice(const float* grids, int G, int L, int Hg, int Wg, const int* grid_idx, const float* xy, const float* rgb,
+                            int B, int n, float* out, void* stream);
+size_t wm_bilagrid_slice_backward_workspace_bytes(int G, int L, int Hg, int Wg, int B, int n);
+wm_status wm_bilagrid_slice_backward(const float* grids, int G, int L, int Hg, int Wg, const int* grid_idx, const float* xy,
+                                     const float* rgb, int B, int n, const float* v_out, float* v_grids, float* v_rgb,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+size_t wm_bilagrid_tv_workspace_bytes(int B, int C, int L, int H, int W);
+wm_status wm_bilagrid_tv(const float* x, int B, int C, int L, int H, int W, float* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+wm_status wm_bilagrid_tv_backward(const float* x, int B, int C, int L, int H, int W, const float* g, float* v_x, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
