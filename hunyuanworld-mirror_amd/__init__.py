@@ -7,6 +7,7 @@ from .ingest import load_and_preprocess_images, preprocess_rgb  # noqa: F401
 from .rasterization import Rasterizer, rasterization  # noqa: F401
 from .losses import fused_ssim, photometric_loss  # noqa: F401
 from .bilagrid import BilateralGrid, slice, total_variation_loss  # noqa: F401
+from .appearance import AppearanceOptModule  # noqa: F401
 from .strategy import DefaultStrategy  # noqa: F401
 from .strategy_mcmc import MCMCStrategy  # noqa: F401
 from .pose import CameraOptModule  # noqa: F401

@@ -71,6 +71,7 @@ EXPORTS = [
     "wm_mcmc_inject_noise", "wm_mcmc_partition_workspace_bytes", "wm_mcmc_partition", "wm_mcmc_relocation", "wm_mcmc_scatter", "wm_mcmc_zero_rows",
     "wm_bilagrid_slice", "wm_bilagrid_slice_backward_workspace_bytes", "wm_bilagrid_slice_backward", "wm_bilagrid_tv_workspace_bytes",
     "wm_bilagrid_tv", "wm_bilagrid_tv_backward",
+    "wm_appearance_forward", "wm_appearance_backward_workspace_bytes", "wm_appearance_backward",
 ]
 
 _lib = None
@@ -241,6 +242,13 @@ def lib() -> C.CDLL:
     L.wm_bilagrid_tv.restype = i32
     L.wm_bilagrid_tv_backward.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.wm_bilagrid_tv_backward.restype = i32
+    L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.wm_appearance_forward.restype = i32
+    L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
+    L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t
+    L.wm_appearance_backward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         C.c_size_t, vp]
+    L.wm_appearance_backward.restype = i32
     L.wm_preprocess_image_size.argtypes = [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
     L.wm_preprocess_image_size.restype = i32
     L.wm_preprocess_image_workspace_bytes.argtypes = [i32, i32, i32, i32]

@@ -4,7 +4,8 @@
 //   project    quat/scale -> covariance, world -> camera, perspective EWA projection, + eps2d blur, conic, 3.33-sigma
 //              radii, near/far + screen culling, tile rectangle        (_torch_impl.py:45-61,78-133,250-375); antialiased:
 //              the record's opacity is opacity * compensation; radius_clip: gsplat's small-splat cull
-//   colour     SH degree 1-3 only: view-dependent colour into the records of the visible pairs (raster_sh.hip; rendering.py:509-525)
+//   colour     SH degree 1-3 only: view-dependent colour into the records of the visible pairs (raster_sh.hip; rendering.py:509-525);
+//              per-camera colours [C,N,3] (gsplat's post-activation colours with a camera axis): the projection copies the pair's own
 //   scan       exclusive sum of tiles-per-Gaussian                     (hipCUB)
 //   emit       one (key, value) pair per touched tile: key = ((camera << tile_bits | tile) << 32) | depth bits
 //   sort       64-bit radix sort of the pairs                          (hipCUB; _torch_impl.py:378-474)
@@ -32,8 +33,9 @@ __global__ __launch_bounds__(256) void raster_project_kernel(const float* __rest
                                                              const float* __restrict__ Ks, int N, int C, int width, int height,
                                                              float near_plane, float far_plane, float eps2d, float radius_clip,
                                                              int antialiased, const float* __restrict__ opac,
-                                                             const float4* __restrict__ rgb, G2D* __restrict__ g2d,
-                                                             unsigned long long* __restrict__ counts, int* __restrict__ radii_out) {
+                                                             const float4* __restrict__ rgb, const float* __restrict__ colors_pc,
+                                                             G2D* __restrict__ g2d, unsigned long long* __restrict__ counts,
+                                                             int* __restrict__ radii_out) {
   const int g = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
   if (g >= N) return;
   // covariance = (R S)(R S)^T, quats wxyz normalised (_torch_impl.py:11-29,45-61)
@@ -114,10 +116,12 @@ __global__ __launch_bounds__(256) void raster_project_kernel(const float* __rest
     cnt = (unsigned long long)((x1 - x0) * (y1 - y0));
   }
   o.rect = x0 | (y0 << 8) | (x1 << 16) | (y1 << 24);
-  const float4 col = rgb[g];
+  const size_t idx = (size_t)c * N + g;
+  float4 col;
+  if (colors_pc) col = make_float4(colors_pc[3 * idx], colors_pc[3 * idx + 1], colors_pc[3 * idx + 2], 0.f);   // per-camera colours [C,N,3], as they are
+  else col = rgb[g];
   o.opacity = antialiased ? opac[g] * comp : opac[g]; o.r = col.x; o.g = col.y; o.b = col.z;
   o.pad = antialiased ? __float_as_int(comp) : 0;   // the backward reads the compensation back instead of recomputing it
-  const size_t idx = (size_t)c * N + g;
   g2d[idx] = o;
   counts[idx] = cnt;
   if (radii_out) { radii_out[2 * idx] = irx; radii_out[2 * idx + 1] = iry; }
@@ -324,11 +328,12 @@ hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned lo
     if (!sh_args_valid(a)) return hipErrorInvalidValue;
     const hipError_t e0 = hipMemsetAsync(w.rgb, 0, N * sizeof(float4), s);
     if (e0 != hipSuccess) return e0;
-  } else {
+  } else if (a.is_sh != WM_COLORS_PER_CAMERA) {   // per-camera colours [C,N,3]: the projection reads the pair's colour itself
     hipLaunchKernelGGL(raster_color_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, a.colors, a.N, a.is_sh, w.rgb);
   }
+  const float* colors_pc = a.sh_degree == 0 && a.is_sh == WM_COLORS_PER_CAMERA ? a.colors : nullptr;
   hipLaunchKernelGGL(raster_project_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)C), dim3(256), 0, s, a.means, a.quats, a.scales, a.viewmats,
-                     a.Ks, a.N, a.C, a.width, a.height, a.near_plane, a.far_plane, a.eps2d, a.radius_clip, a.antialiased, a.opacities, w.rgb, w.g2d, w.counts, a.radii_out);
+                     a.Ks, a.N, a.C, a.width, a.height, a.near_plane, a.far_plane, a.eps2d, a.radius_clip, a.antialiased, a.opacities, w.rgb, colors_pc, w.g2d, w.counts, a.radii_out);
   if (a.sh_degree > 0) launch_sh_colors(a, w.g2d, s);
   hipError_t e = hipMemsetAsync(w.counts + CN, 0, 8, s);
   if (e != hipSuccess) return e;

@@ -52,6 +52,7 @@ __global__ __launch_bounds__(256) void raster_locate_sorted_kernel(const unsigne
 }
 
 // _torch_impl.py:11-29,45-61 (quaternion, scale -> covariance), :250-283 (world -> camera), :78-133 (perspective), :329-355 (conic)
+// is_sh = WM_COLORS_PER_CAMERA: colors_in is [C,N,3] (not read) and v_colors [C,N,3] gets every pair's summed colour terms, zeros where culled
 // M2D: also write v_means2d [C,N,2] (and, with 12-float records, v_means2d_abs): the summed pair terms, zero where culled
 // CAM: also write cam_part [C][12][waves] (fp64): per wave the sum over its Gaussians of the pair's viewmats terms, component 4 i + j =
 //      v_R[i][j] (j < 3) or v_t[i] (j = 3).  v_t += (v_tx, v_ty, v_tz) (from mc = Rv m + t); v_R += outer(v_t, m) + (vS + vS^T) Rv cov
@@ -111,6 +112,7 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
           if constexpr (REC == PAIR_REC_ABS) { v_means2d_abs[2 * idx] = 0.f; v_means2d_abs[2 * idx + 1] = 0.f; }
         }
       }
+      if (is_sh == WM_COLORS_PER_CAMERA && live) { v_colors[3 * idx] = 0.f; v_colors[3 * idx + 1] = 0.f; v_colors[3 * idx + 2] = 0.f; }
       if constexpr (!CAM) continue;
     }
     if (!CAM || (live && cnt > 0)) {
@@ -131,6 +133,7 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
       const float comp = antialiased ? __int_as_float(g2d[idx].pad) : 1.0f;
       a_op += antialiased ? comp * p[5] : p[5];
       a_col[0] += p[6]; a_col[1] += p[7]; a_col[2] += p[8];
+      if (is_sh == WM_COLORS_PER_CAMERA) { v_colors[3 * idx] = p[6]; v_colors[3 * idx + 1] = p[7]; v_colors[3 * idx + 2] = p[8]; }   // [C,N,3]: the pair's own
       // forward, as raster_project_kernel
       const float* V = viewmats + 16 * c;
       const float Rv[9] = {V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
@@ -256,6 +259,7 @@ __global__ __launch_bounds__(256) void raster_project_bwd_kernel(const float* __
   v_means[3 * g] = a_m[0]; v_means[3 * g + 1] = a_m[1]; v_means[3 * g + 2] = a_m[2];
   v_scales[3 * g] = vs[0]; v_scales[3 * g + 1] = vs[1]; v_scales[3 * g + 2] = vs[2];
   v_opac[g] = a_op;
+  if (is_sh == WM_COLORS_PER_CAMERA) return;   // v_colors [C,N,3] is written per pair above
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     float vc = a_col[i];

@@ -259,9 +259,12 @@ hipError_t wm_launch_cam_update(float* pred, const float* delta, float* out, int
 hipError_t wm_launch_cam_matrices(const float* params, float* poses, float* intrs, int S, int H, int W, hipStream_t s);
 
 // ------------------------------------------------------------------ 3D-Gaussian rasteriser (raster.hip)
+#ifndef WM_COLORS_PER_CAMERA
+#define WM_COLORS_PER_CAMERA 2   // include/wm_hip.h: the third value of colors_are_sh0
+#endif
 struct WmRasterArgs {
   const float* means; const float* quats; const float* scales; const float* opacities;  // [N,3] [N,4 wxyz] [N,3] [N]
-  const float* colors; int is_sh;       // [N,3]: degree-0 SH coefficients (is_sh = 1) or final colours
+  const float* colors; int is_sh;       // [N,3]: degree-0 SH coefficients (is_sh = 1) or final colours (0); WM_COLORS_PER_CAMERA: final colours [C,N,3]
   int N;
   // view-dependent colour (raster_sh.hip): sh_degree 1-3 makes colors the SH coefficients [N,n_coeffs,3], (sh_degree + 1)^2 <= n_coeffs,
   // evaluated along means - campos [C,3] (the cameras' world positions); is_sh is then not read.  sh_degree = 0: as above
@@ -375,6 +378,27 @@ hipError_t wm_launch_bilagrid_slice_bwd(const WmBilagridArgs& a, const float* v_
 size_t wm_bilagrid_tv_ws_bytes(int B, int C, int L, int H, int W);
 hipError_t wm_launch_bilagrid_tv(const float* x, int B, int C, int L, int H, int W, float* out, void* ws, size_t ws_bytes, hipStream_t s);
 hipError_t wm_launch_bilagrid_tv_bwd(const float* x, int B, int C, int L, int H, int W, const float* g, float* v_x, hipStream_t s);
+
+// ------------------------------------------------------------------ appearance module: per-camera colour MLP (appearance.hip)
+// gsplat's AppearanceOptModule for feature_dim 32, embed_dim 16, width 64, depth 2; n_bases = (module sh_degree + 1)^2, degree: the call's
+constexpr int WM_APPEARANCE_TILE = 128;         // Gaussians per block tile (four waves of 32)
+constexpr int WM_APPEARANCE_MAX_BLOCKS = 512;   // the backward's persistent grid: min(tiles, this) blocks, each a contiguous run of tiles
+struct WmAppearanceArgs {
+  const float* features;                       // [N,32]
+  const float* embeds; const int* embed_ids;   // [n_embeds,16], int32 [C] on the device; embed_ids null: zero embeddings
+  const float* dirs;                           // [C,N,3], normalised inside
+  const float* W1; const float* b1; const float* W2; const float* b2; const float* W3; const float* b3;   // [64,48+n_bases] [64] [64,64] [64] [3,64] [3]
+  int N, C, n_embeds, n_bases, degree;
+};
+struct WmAppearanceGrads {
+  const float* v_out;                          // [C,N,3]
+  float* v_features; float* v_dirs;            // [N,32] [C,N,3]
+  float* v_embeds;                             // [n_embeds,16], optional
+  float* v_W1; float* v_b1; float* v_W2; float* v_b2; float* v_W3; float* v_b3;
+};
+size_t wm_appearance_bwd_workspace_bytes(int N, int C);
+hipError_t wm_launch_appearance_fwd(const WmAppearanceArgs& a, float* out, hipStream_t s);
+hipError_t wm_launch_appearance_bwd(const WmAppearanceArgs& a, const WmAppearanceGrads& v, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ------------------------------------------------------------------ voxel merge of splats (splat_prune.hip)
 size_t wm_prune_workspace_bytes(size_t N);

@@ -2167,6 +2167,7 @@ static bool raster_fill(WmRasterArgs& a, const float* means, const float* quats,
   a.N = n_gaussians; a.viewmats = viewmats; a.Ks = Ks; a.C = n_cameras; a.width = width; a.height = height;
   // checked here, in front of the first HIP call
   if (sh_degree < 0 || sh_degree > 3 || (sh_degree > 0 && ((sh_degree + 1) * (sh_degree + 1) > n_coeffs || !campos))) return false;
+  if (colors_are_sh0 < 0 || colors_are_sh0 > WM_COLORS_PER_CAMERA || (colors_are_sh0 == WM_COLORS_PER_CAMERA && sh_degree > 0)) return false;
   return wm_raster_options_valid(a);
 }
 extern "C" wm_status wm_rasterize_splats_opt(const float* means, const float* quats, const float* scales, const float* opacities,
@@ -2445,6 +2446,46 @@ extern "C" wm_status wm_bilagrid_tv(const float* x, int B, int C, int L, int H, 
 extern "C" wm_status wm_bilagrid_tv_backward(const float* x, int B, int C, int L, int H, int W, const float* g, float* v_x, void* stream) {
   if (!x || !g || !v_x) return WM_ERR_INVALID;
   return bilagrid_status(wm_launch_bilagrid_tv_bwd(x, B, C, L, H, W, g, v_x, (hipStream_t)stream));
+}
+// ---- appearance module (appearance.hip)
+static bool appearance_fill(WmAppearanceArgs& a, const float* features, const float* embeds, int n_embeds, const int* embed_ids, const float* dirs,
+                            const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3, int n_gaussians,
+                            int n_cameras, int module_sh_degree, int sh_degree) {
+  memset(&a, 0, sizeof(a));
+  if (!features || !dirs || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || n_gaussians <= 0 || n_cameras <= 0) return false;
+  if (module_sh_degree < 0 || module_sh_degree > 3 || sh_degree < 0 || sh_degree > module_sh_degree) return false;
+  if (embed_ids && (!embeds || n_embeds <= 0)) return false;
+  if ((size_t)n_gaussians * n_cameras >= (1ull << 29)) return false;
+  a.features = features; a.embeds = embeds; a.embed_ids = embed_ids; a.dirs = dirs; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.W3 = W3; a.b3 = b3;
+  a.N = n_gaussians; a.C = n_cameras; a.n_embeds = n_embeds; a.n_bases = (module_sh_degree + 1) * (module_sh_degree + 1); a.degree = sh_degree;
+  return true;
+}
+extern "C" wm_status wm_appearance_forward(const float* features, const float* embeds, int n_embeds, const int* embed_ids, const float* dirs,
+                                           const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3,
+                                           int n_gaussians, int n_cameras, int module_sh_degree, int sh_degree, float* out, void* stream) {
+  WmAppearanceArgs a;
+  if (!out || !appearance_fill(a, features, embeds, n_embeds, embed_ids, dirs, W1, b1, W2, b2, W3, b3, n_gaussians, n_cameras, module_sh_degree, sh_degree))
+    return WM_ERR_INVALID;
+  return bilagrid_status(wm_launch_appearance_fwd(a, out, (hipStream_t)stream));
+}
+extern "C" size_t wm_appearance_backward_workspace_bytes(int n_gaussians, int n_cameras) {
+  return wm_appearance_bwd_workspace_bytes(n_gaussians, n_cameras);
+}
+extern "C" wm_status wm_appearance_backward(const float* features, const float* embeds, int n_embeds, const int* embed_ids, const float* dirs,
+                                            const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3,
+                                            int n_gaussians, int n_cameras, int module_sh_degree, int sh_degree, const float* v_out,
+                                            float* v_features, float* v_dirs, float* v_embeds, float* v_W1, float* v_b1, float* v_W2, float* v_b2,
+                                            float* v_W3, float* v_b3, void* workspace, size_t workspace_bytes, void* stream) {
+  WmAppearanceArgs a;
+  if (!appearance_fill(a, features, embeds, n_embeds, embed_ids, dirs, W1, b1, W2, b2, W3, b3, n_gaussians, n_cameras, module_sh_degree, sh_degree))
+    return WM_ERR_INVALID;
+  if (!v_out || !v_features || !v_dirs || !v_W1 || !v_b1 || !v_W2 || !v_b2 || !v_W3 || !v_b3 || !workspace) return WM_ERR_INVALID;
+  if (v_embeds && (!embeds || n_embeds <= 0)) return WM_ERR_INVALID;
+  if (workspace_bytes < wm_appearance_bwd_workspace_bytes(n_gaussians, n_cameras)) return WM_ERR_INVALID;
+  WmAppearanceGrads v;
+  v.v_out = v_out; v.v_features = v_features; v.v_dirs = v_dirs; v.v_embeds = v_embeds; v.v_W1 = v_W1; v.v_b1 = v_b1; v.v_W2 = v_W2; v.v_b2 = v_b2;
+  v.v_W3 = v_W3; v.v_b3 = v_b3;
+  return bilagrid_status(wm_launch_appearance_bwd(a, v, workspace, workspace_bytes, (hipStream_t)stream));
 }
 extern "C" wm_status wm_op_layernorm(const float* x, void* y, const float* w, const float* b, int rows, int D, float eps, int out_f32,
                                      int dtype, void* stream) {

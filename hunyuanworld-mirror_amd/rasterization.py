@@ -22,6 +22,11 @@ and ``wm_rasterize_splats_backward_sh`` on every route.  The colour of a (camera
 in the bands at or above ``(sh_degree + 1)^2``, ``means.grad`` includes the direction's term, and with ``camera_grad`` ``campos`` is a
 second graph tensor beside ``viewmats``, so that ``camtoworlds.grad`` is the sum of both.  ``sh_degree`` 0 and ``None`` go as before.
 
+Per-camera colours: ``colors [C,N,3]`` with ``sh_degree=None`` (post-activation colours with a camera axis, as the reference trainer's
+``--app_opt`` passes them: ``sigmoid(app_module(...) + colors)``, simple_trainer_worldmirror.py:603-611) render pair (c, g) with
+``colors[c, g]`` as it is, on every route, through the entries with options (``colors_are_sh0 = WM_COLORS_PER_CAMERA``); ``colors.grad`` is
+``[C,N,3]`` with exact zeros where a camera culled the Gaussian.  A leading size other than the number of cameras is a ``ValueError``.
+
 ``rasterize_splats(..., return_info=True)`` also returns what gsplat.rasterization's ``info`` gives a densification strategy
 (strategy.DefaultStrategy): the projected ``means2d`` as part of the graph, so that ``retain_grad()`` works and ``.grad`` (and,
 with absgrad, the plain attribute ``.absgrad``) is there after ``loss.backward()``, and the per-(camera, Gaussian) ``radii``.
@@ -81,13 +86,13 @@ class _RasterizeSplats(torch.autograd.Function):
         grads, _, _, v_vm, v_cp, v_bg = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False, ctx.needs_input_grad[11],
                                                   ctx.needs_input_grad[12], want_bg, alpha)
         # camtoworlds, Ks: no gradient of their own (camtoworlds gets its through viewmats and campos)
-        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0] and not ctx.state[10], ctx.needs_input_grad[6:11]),
+        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0] == 1 and not ctx.state[10], ctx.needs_input_grad[6:11]),
                 v_vm, v_cp, None, None, _shape_bg(v_bg, ctx.bg_meta))
 
 
 def _cin(colors, is_sh, sh_degree):
     """what the kernels read: all of the SH coefficients [N,K,3] for sh_degree 1-3, band 0 for degree 0, the colours [N,3] otherwise"""
-    return colors[:, 0, :] if is_sh and not sh_degree else colors
+    return colors[:, 0, :] if is_sh == 1 and not sh_degree else colors
 
 
 def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_cam=False, want_campos=False, want_bg=False, alpha=None):
@@ -248,7 +253,7 @@ class _CompositeWithInfo(torch.autograd.Function):
         if ctx.want_absgrad and m2 is not None:
             m2.absgrad = v2d_abs
         ctx.shared["v_means2d"] = v2d
-        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0] and not ctx.state[10], ctx.needs_input_grad[4:9]), v_vm, v_cp,
+        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0] == 1 and not ctx.state[10], ctx.needs_input_grad[4:9]), v_vm, v_cp,
                 _shape_bg(v_bg, ctx.bg_meta))
 
 
@@ -259,6 +264,16 @@ class _Opts(collections.namedtuple("_Opts", "antialiased depth_mode eps2d near_p
     def struct(self, backgrounds=None):
         return _lib.wm_raster_options(int(self.antialiased), int(self.depth_mode), float(self.eps2d), float(self.near_plane), float(self.far_plane),
                                       float(self.radius_clip), None if backgrounds is None else backgrounds.data_ptr())
+
+
+PER_CAMERA = 2     # include/wm_hip.h WM_COLORS_PER_CAMERA
+
+
+def _per_camera(colors, V, N):
+    """colors [C,N,3] with sh_degree None: one post-activation colour per (camera, Gaussian); sh_degree is None, so it is never SH"""
+    if tuple(colors.shape) != (V, N, 3):
+        raise ValueError(f"per-camera colors must be [C, N, 3] = [{V}, {N}, 3], not {tuple(colors.shape)}")
+    return colors
 
 
 _OPTION_DEFAULTS = dict(near_plane=0.01, far_plane=1e10, eps2d=0.3, radius_clip=0.0)
@@ -298,7 +313,10 @@ class Rasterizer:
         if means.device.type != "cuda":
             raise RuntimeError("the rasteriser runs in libwm_hip.so on the GPU: move the splats to a HIP device")
         L = 0
-        if colors.dim() == 3:            # SH coefficients [N, K, 3]
+        if colors.dim() == 3 and sh_degree is None:      # post-activation colours per camera [C, N, 3]
+            cin, is_sh = _per_camera(colors, int(camtoworlds.shape[0]), int(means.shape[0])), PER_CAMERA
+            opts = opts or _Opts(0, 0, **_OPTION_DEFAULTS)   # this colour form lives in the entries with options
+        elif colors.dim() == 3:          # SH coefficients [N, K, 3]
             if sh_degree is None or not 0 <= int(sh_degree) <= 3:
                 raise NotImplementedError(f"SH degrees 0 to 3 are built, not sh_degree = {sh_degree}")
             L, K = int(sh_degree), int(colors.shape[1])
@@ -452,7 +470,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
     """gsplat.rasterization (gsplat/rendering.py) as the reference's post-3DGS trainer calls it (simple_trainer_worldmirror.py:619-642):
     -> (render_colors [C,H,W,3 | 1 | 4], render_alphas [C,H,W,1], info).  viewmats [C,4,4] are WORLD-TO-CAMERA, as in gsplat; a viewmats
     that requires grad receives the camera gradient directly and, with sh_degree > 0, also through campos = inv(viewmats)[:, :3, 3], taken
-    in the graph.  colors: [N,3] with sh_degree None, or SH coefficients [N,K,3] with sh_degree 0-3.  render_mode: "RGB", "D" (accumulated
+    in the graph.  colors: [N,3] or per-camera [C,N,3] with sh_degree None, or SH coefficients [N,K,3] with sh_degree 0-3.  render_mode: "RGB", "D" (accumulated
     depth), "ED" (expected depth), "RGB+D", "RGB+ED"; backgrounds [C,3] (differentiable) reach the colour channels only.  info is that of
     Rasterizer.rasterize_splats(return_info=True): means2d (with .grad, and .absgrad with absgrad=True, after backward), radii, width,
     height, n_cameras, gaussian_ids = None.  Whatever the kernels do not do raises NotImplementedError naming the argument."""
@@ -465,10 +483,13 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
             raise NotImplementedError(f"rasterization(): {name} = {locals()[name]!r} is not built")
     if unsupported:
         raise NotImplementedError(f"rasterization(): arguments not built: {sorted(unsupported)}")
-    if colors.shape[-1] != 3 or colors.dim() != (2 if sh_degree is None else 3):
+    per_camera = sh_degree is None and colors.dim() == 3 and colors.shape[-1] == 3
+    if per_camera:
+        _per_camera(colors, int(viewmats.shape[0]), int(means.shape[0]))
+    elif colors.shape[-1] != 3 or colors.dim() != (2 if sh_degree is None else 3):
         raise NotImplementedError(f"rasterization(): colors of shape {tuple(colors.shape)} with sh_degree = {sh_degree}: 3 colour channels, "
-                                  "[N,3] or SH coefficients [N,K,3], are built")
-    L, is_sh = 0, 0
+                                  "[N,3], [C,N,3] (sh_degree None) or SH coefficients [N,K,3], are built")
+    L, is_sh = 0, PER_CAMERA if per_camera else 0
     if sh_degree is not None:
         L, is_sh = int(sh_degree), 1
         if not 0 <= L <= 3:

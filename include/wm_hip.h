@@ -499,7 +499,17 @@ typedef struct wm_raster_options {
  * max_isects / *n_isects and WM_ERR_STATE exactly as wm_rasterize_splats; wm_rasterize_means2d works on the workspace this call leaves.
  * out_depth holds the depth channel of the chosen depth_mode.  WM_ERR_INVALID, before anything is launched, for eps2d < 0,
  * near_plane >= far_plane, radius_clip < 0, depth_mode or antialiased outside {0, 1}, sh_degree outside 0..3, (sh_degree + 1)^2 > n_coeffs
- * or a null campos with sh_degree > 0.  With null (default) options the outputs are those of the entries above, bit for bit. */
+ * or a null campos with sh_degree > 0.  With null (default) options the outputs are those of the entries above, bit for bit.
+ * Per-camera colours: colors_are_sh0 = WM_COLORS_PER_CAMERA makes colors [C,N,3], post-activation colours with a camera axis (one of the
+ * colour shapes gsplat.rasterization takes with sh_degree = None, gsplat/rendering.py's colour handling ahead of the SH branch at :509-525;
+ * the reference trainer's --app_opt passes sigmoid(app_module(...) + colors), simple_trainer_worldmirror.py:603-611): the pair (c, g) is
+ * rendered with colors[c,g,:] as it is (no + 0.5, no clamp); n_coeffs and campos are not read and sh_degree must be 0.  The backward's
+ * v_colors is then [C,N,3]: per pair the sum of its tiles' colour terms, exact zeros where the camera culled the Gaussian, every slot
+ * written.  All other outputs and the workspace sizes are those of colors [N,3].  WM_ERR_INVALID, before anything is launched, for
+ * colors_are_sh0 outside {0, 1, 2} and for WM_COLORS_PER_CAMERA with sh_degree > 0. */
+#ifndef WM_COLORS_PER_CAMERA
+#define WM_COLORS_PER_CAMERA 2
+#endif
 wm_status wm_rasterize_splats_opt(const float* means, const float* quats, const float* scales, const float* opacities,
                                   const float* colors, int colors_are_sh0, int n_coeffs, int sh_degree, const float* campos,
                                   int n_gaussians, const float* viewmats, const float* Ks, int n_cameras, int width, int height,
@@ -669,6 +679,35 @@ size_t wm_bilagrid_tv_workspace_bytes(int B, int C, int L, int H, int W);
 wm_status wm_bilagrid_tv(const float* x, int B, int C, int L, int H, int W, float* out, void* workspace, size_t workspace_bytes,
                          void* stream);
 wm_status wm_bilagrid_tv_backward(const float* x, int B, int C, int L, int H, int W, const float* g, float* v_x, void* stream);
+
+/* Appearance optimisation of the post-3DGS trainer — replaces gsplat's AppearanceOptModule (examples/utils.py:51-114), which
+ * simple_trainer_worldmirror.py builds under --app_opt (:532-552) and evaluates per step (:603-611): per (camera c, Gaussian g) pair
+ *   h = [embeds[embed_ids[c]] (16) | features[g] (32) | B_k(dirs[c,g] / max(|dirs[c,g]|, 1e-12)), k < (module_sh_degree + 1)^2],
+ *   out[c,g,:] = W3 relu(W2 relu(W1 h + b1) + b2) + b3, with B_k = 0 for k >= (sh_degree + 1)^2 (bands the call does not use); pre-sigmoid.
+ * B_k: the real SH basis of raster_sh / gsplat's _eval_sh_bases_fast.  Built for feature_dim 32, embed_dim 16, mlp_width 64, mlp_depth 2:
+ * W1 [64, 48 + (module_sh_degree + 1)^2] (columns in the module's order: embedding, features, basis), b1 [64], W2 [64,64], b2 [64], W3 [3,64],
+ * b3 [3]; embeds [n_embeds,16]; embed_ids int32 [C] ON THE DEVICE or null (zero embeddings; an id outside [0, n_embeds) also reads zeros
+ * and receives no gradient); features [N,32], dirs [C,N,3], out [C,N,3]; all contiguous fp32.  0 <= sh_degree <= module_sh_degree <= 3.
+ * All arithmetic is fp32 (the matrix products on the exact fp32-input MFMA); nothing of size [C,N,64] is written.
+ * backward (examples/utils.py:51-114 differentiated): v_out [C,N,3] -> v_features [N,32] (summed over the cameras in camera order by one
+ *   writer), v_dirs [C,N,3] (through the basis and the normalisation; finite for a zero direction), v_W1 .. v_b3 in the shapes above (basis
+ *   columns of bands the call does not use: exact zeros), v_embeds [n_embeds,16] (optional; every element written, rows no camera names
+ *   are zeros, a repeated id sums in camera order).  ReLU's gradient is taken where the pre-activation is > 0.  The activations are
+ *   recomputed, none is stored.  The weight gradients are summed without atomics: a grid of min(ceil(N / 128), 512) blocks, each over a
+ *   contiguous run of 128-Gaussian tiles, leaves one partial set per block in the workspace and a second kernel adds them in block order:
+ *   identical bits run to run.  workspace: wm_appearance_backward_workspace_bytes bytes (about 30 KB + 1 KB per camera, per block); a
+ *   smaller one returns WM_ERR_INVALID before anything is launched.
+ * Both calls are asynchronous on stream and never synchronise the host.  WM_ERR_INVALID, before anything is launched: a size <= 0, a degree
+ * outside the ranges above, N * C >= 2^29, a null pointer where none is allowed. */
+wm_status wm_appearance_forward(const float* features, const float* embeds, int n_embeds, const int* embed_ids, const float* dirs,
+                                const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3,
+                                int n_gaussians, int n_cameras, int module_sh_degree, int sh_degree, float* out, void* stream);
+size_t wm_appearance_backward_workspace_bytes(int n_gaussians, int n_cameras);
+wm_status wm_appearance_backward(const float* features, const float* embeds, int n_embeds, const int* embed_ids, const float* dirs,
+                                 const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3,
+                                 int n_gaussians, int n_cameras, int module_sh_degree, int sh_degree, const float* v_out,
+                                 float* v_features, float* v_dirs, float* v_embeds, float* v_W1, float* v_b1, float* v_W2, float* v_b2,
+                                 float* v_W3, float* v_b3, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
