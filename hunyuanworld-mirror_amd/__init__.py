@@ -5,7 +5,7 @@ from .geometry import (create_confidence_mask, depth_edge, depth_to_world_coords
                        normals_edge)
 from .ingest import load_and_preprocess_images, preprocess_rgb  # noqa: F401
 from .rasterization import Rasterizer, rasterization  # noqa: F401
-from .losses import fused_ssim, photometric_loss  # noqa: F401
+from .losses import depth_loss, fused_ssim, photometric_loss, project_depth_points  # noqa: F401
 from .bilagrid import BilateralGrid, slice, total_variation_loss  # noqa: F401
 from .appearance import AppearanceOptModule  # noqa: F401
 from .strategy import DefaultStrategy  # noqa: F401

@@ -72,6 +72,7 @@ EXPORTS = [
     "wm_bilagrid_slice", "wm_bilagrid_slice_backward_workspace_bytes", "wm_bilagrid_slice_backward", "wm_bilagrid_tv_workspace_bytes",
     "wm_bilagrid_tv", "wm_bilagrid_tv_backward",
     "wm_appearance_forward", "wm_appearance_backward_workspace_bytes", "wm_appearance_backward",
+    "wm_depth_loss_workspace_bytes", "wm_depth_loss", "wm_depth_loss_backward", "wm_project_depth_points",
 ]
 
 _lib = None
@@ -242,6 +243,14 @@ def lib() -> C.CDLL:
     L.wm_bilagrid_tv.restype = i32
     L.wm_bilagrid_tv_backward.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.wm_bilagrid_tv_backward.restype = i32
+    L.wm_depth_loss_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    L.wm_depth_loss_workspace_bytes.restype = C.c_size_t
+    L.wm_depth_loss.argtypes = [vp, i64p, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, C.c_size_t, vp]
+    L.wm_depth_loss.restype = i32
+    L.wm_depth_loss_backward.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64p, vp, C.c_size_t, vp]
+    L.wm_depth_loss_backward.restype = i32
+    L.wm_project_depth_points.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.wm_project_depth_points.restype = i32
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_forward.restype = i32
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]

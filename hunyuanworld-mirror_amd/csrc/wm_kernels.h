@@ -379,6 +379,24 @@ size_t wm_bilagrid_tv_ws_bytes(int B, int C, int L, int H, int W);
 hipError_t wm_launch_bilagrid_tv(const float* x, int B, int C, int L, int H, int W, float* out, void* ws, size_t ws_bytes, hipStream_t s);
 hipError_t wm_launch_bilagrid_tv_bwd(const float* x, int B, int C, int L, int H, int W, const float* g, float* v_x, hipStream_t s);
 
+// ------------------------------------------------------------------ sparse disparity loss and point projection (depthloss.hip)
+// depth [C,H,W] fp32 by element strides (sC, sH, sW): channel 3 of a [C,H,W,4] render is read in place; points [C,M,2], depth_gt [C,M]
+// contiguous fp32, valid [C,M] bytes (0 / 1) or null = every row
+struct WmDepthLossArgs {
+  const float* depth; const int64_t* strides;          // host, 3
+  const float* points; const float* depth_gt; const unsigned char* valid;
+  int C, H, W, M;
+  void* workspace; size_t workspace_bytes;
+};
+size_t wm_depthloss_workspace_bytes(int C, int H, int W, int M, int want_backward);   // 0 for sizes the launchers refuse
+// forward: the mean to a device float; want_backward also leaves one coefficient per row in the workspace
+hipError_t wm_launch_depthloss_fwd(const WmDepthLossArgs& a, int want_backward, float* out, hipStream_t s);
+// backward: reads C, H, W, M, points and the workspace of a alone (not the image, depth_gt or valid); gout a device float; v_depth is written
+// (every element) with v_strides (host, 3)
+hipError_t wm_launch_depthloss_bwd(const WmDepthLossArgs& a, const float* gout, float* v_depth, const int64_t* v_strides, hipStream_t s);
+hipError_t wm_launch_depth_project(const float* points_world, const float* camtoworlds, const float* Ks, const unsigned char* visible, int C, int P,
+                                   int W, int H, float* points, float* depths, unsigned char* valid, hipStream_t s);
+
 // ------------------------------------------------------------------ appearance module: per-camera colour MLP (appearance.hip)
 // gsplat's AppearanceOptModule for feature_dim 32, embed_dim 16, width 64, depth 2; n_bases = (module sh_degree + 1)^2, degree: the call's
 constexpr int WM_APPEARANCE_TILE = 128;         // Gaussians per block tile (four waves of 32)

@@ -2487,6 +2487,46 @@ extern "C" wm_status wm_appearance_backward(const float* features, const float* 
   v.v_W3 = v_W3; v.v_b3 = v_b3;
   return bilagrid_status(wm_launch_appearance_bwd(a, v, workspace, workspace_bytes, (hipStream_t)stream));
 }
+// ---- sparse disparity loss and point projection (depthloss.hip)
+extern "C" size_t wm_depth_loss_workspace_bytes(int C, int H, int W, int M, int want_backward) {
+  return wm_depthloss_workspace_bytes(C, H, W, M, want_backward);
+}
+static bool depth_loss_args(WmDepthLossArgs& a, const float* depth, const int64_t* strides, int C, int H, int W, const float* points,
+                            const float* depth_gt, const unsigned char* valid, int M, void* workspace, size_t workspace_bytes, bool backward) {
+  if (!depth || !strides || !workspace || C < 1 || H < 2 || W < 2 || M < 0) return false;      // the reference divides by W - 1 and H - 1
+  if (M > 0 && (!points || !depth_gt)) return false;
+  const size_t need = wm_depthloss_workspace_bytes(C, H, W, M, backward ? 1 : 0);
+  if (need == 0 || workspace_bytes < need) return false;
+  memset(&a, 0, sizeof(a));
+  a.depth = depth; a.strides = strides; a.points = points; a.depth_gt = depth_gt; a.valid = valid; a.C = C; a.H = H; a.W = W; a.M = M;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  return true;
+}
+extern "C" wm_status wm_depth_loss(const float* depth, const int64_t* strides, int C, int H, int W, const float* points, const float* depth_gt,
+                                   const unsigned char* valid, int M, int want_backward, float* out_loss, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  WmDepthLossArgs a;
+  if (!out_loss || !depth_loss_args(a, depth, strides, C, H, W, points, depth_gt, valid, M, workspace, workspace_bytes, want_backward != 0))
+    return WM_ERR_INVALID;
+  return bilagrid_status(wm_launch_depthloss_fwd(a, want_backward, out_loss, (hipStream_t)stream));
+}
+extern "C" wm_status wm_depth_loss_backward(int C, int H, int W, const float* points, int M, const float* g, float* v_depth,
+                                            const int64_t* v_strides, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!g || !v_depth || !v_strides || !workspace || C < 1 || H < 2 || W < 2 || M < 0 || (M > 0 && !points)) return WM_ERR_INVALID;
+  const size_t need = wm_depthloss_workspace_bytes(C, H, W, M, 1);
+  if (need == 0 || workspace_bytes < need) return WM_ERR_INVALID;
+  WmDepthLossArgs a;
+  memset(&a, 0, sizeof(a));
+  a.points = points; a.C = C; a.H = H; a.W = W; a.M = M; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  return bilagrid_status(wm_launch_depthloss_bwd(a, g, v_depth, v_strides, (hipStream_t)stream));
+}
+extern "C" wm_status wm_project_depth_points(const float* points_world, const float* camtoworlds, const float* Ks, const unsigned char* visible,
+                                             int C, int P, int width, int height, float* points, float* depths, unsigned char* valid,
+                                             void* stream) {
+  if (!camtoworlds || !Ks || C < 1 || P < 0 || width < 1 || height < 1) return WM_ERR_INVALID;
+  if (P > 0 && (!points_world || !points || !depths || !valid)) return WM_ERR_INVALID;
+  return bilagrid_status(wm_launch_depth_project(points_world, camtoworlds, Ks, visible, C, P, width, height, points, depths, valid, (hipStream_t)stream));
+}
 extern "C" wm_status wm_op_layernorm(const float* x, void* y, const float* w, const float* b, int rows, int D, float eps, int out_f32,
                                      int dtype, void* stream) {
   WmLnArgs a;

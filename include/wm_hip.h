@@ -709,6 +709,50 @@ wm_status wm_appearance_backward(const float* features, const float* embeds, int
                                  float* v_features, float* v_dirs, float* v_embeds, float* v_W1, float* v_b1, float* v_W2, float* v_b2,
                                  float* v_W3, float* v_b3, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Depth supervision of the post-3DGS trainer: the sparse disparity loss of gsplat's simple_trainer_worldmirror.py:793-811 (the
+ * `if cfg.depth_loss:` block: normalise the pixel coordinates with (width - 1, height - 1), F.grid_sample(align_corners=True), disparity,
+ * F.l1_loss against 1 / depths_gt; scene_scale and depth_lambda stay with the caller), and the projection that produces its points,
+ * examples/datasets/colmap.py:412-433 (the `if self.load_depths:` block of Dataset.__getitem__).
+ * loss.  depth: fp32 [C,H,W] addressed by ELEMENT strides (sC, sH, sW) (host array, read during the call): channel 3 of a [C,H,W,4]
+ *   render is read in place.  points [C,M,2] (x, y) in pixels with pixel centres at integers, depth_gt [C,M], contiguous fp32; valid [C,M]
+ *   bytes, 0 = the row does not exist (its coordinates and its depth_gt are never read and may be NaN), or NULL = every row counts.
+ *   Row (c, m) reads camera c's image at x0 = floor(x), y0 = floor(y), fx = x - x0, fy = y - y0:
+ *     d = (1-fx)(1-fy) D[y0,x0] + fx (1-fy) D[y0,x0+1] + (1-fx) fy D[y0+1,x0] + fx fy D[y0+1,x0+1], a corner outside the image counting as 0
+ *     (zero padding: x in (W - 1, W) and y in (H - 1, H), which the projection keeps, lose their right / lower corners; a point
+ *     further out than one pixel samples 0);  disp = d > 0 ? 1 / d : 0;  term = |disp - 1 / depth_gt|.
+ *   *out_loss (device float) = sum of the terms / n, n = the number of valid rows, both found on the device in the same pass; the sum
+ *   runs in fp64 in a fixed order and is rounded once.  n = 0 (M = 0 included) gives NaN, as torch's mean of an empty tensor.
+ * backward.  v_depth (fp32, EVERY element written, addressed by the element strides v_strides = (sC, sH, sW), a host array: pass the depth
+ *   image's own strides to write a gradient laid out as the image is) =
+ *     v_depth[c,y,x] = (*g / n) * sum_m w_m(y,x) * sign(disp_m - 1 / depth_gt_m) * (-1 / d_m^2)
+ *   over the valid rows of camera c whose four corners hold (y, x), w_m the corner's bilinear weight; sign(0) = 0 and a row with
+ *   d_m <= 0 adds nothing; n = 0 gives zeros.  g: device float.  points and depth_gt get no gradient.  A pixel's sum runs in row order
+ *   (a stable sort by cell, then a merge by row index), without floating-point atomics: identical bits run to run and between two
+ *   layouts of the same depth values.  A cell's rows are walked by one lane, so a call's time grows with the largest number of rows in
+ *   one cell (all M rows of a camera in one cell: O(M) steps of one lane).  CONTRACT: the same sizes, points and workspace as the forward
+ *   call with want_backward = 1, the workspace UNTOUCHED in between: that call leaves n and one coefficient per row there, so the
+ *   backward reads neither the depth image nor depth_gt nor valid again and does not take them.
+ * workspace: wm_depth_loss_workspace_bytes(C, H, W, M, want_backward) bytes: want_backward = 0: 16 bytes per 256 rows; 1: about 20 bytes
+ *   per row + 4 per pixel + the sort's scratch, counted as 8 bytes per row + 1 MiB (a rule of this library, the same number on every
+ *   machine; the backward returns WM_ERR_HIP should the sort ever ask for more).  0 for sizes the calls refuse.
+ * wm_project_depth_points.  points_world [P,3], camtoworlds [C,4,4], Ks [C,3,3] contiguous fp32; visible [C,P] bytes or NULL (stands
+ *   for the reference's per-image point_indices) -> points [C,P,2], depths [C,P] fp32, valid [C,P] bytes.  p_cam = R^T (p_world - t) with
+ *   [R | t] the top three rows of camtoworld: the RIGID inverse, taken inside the call per camera in fp64 (R is assumed orthonormal; the
+ *   reference inverts the 4 x 4); q = K p_cam, (x, y) = q.xy / q.z, depth = p_cam.z, all in fp64 with one rounding per output;
+ *   valid = visible && 0 <= x < width && 0 <= y < height && depth > 0, tested on the fp64 values.  Nothing is compacted: the loss takes
+ *   valid, so cameras with different numbers of points need no ragged layout.
+ * All calls are asynchronous on stream and never synchronise the host.  WM_ERR_INVALID, before anything is launched: a null pointer where
+ * none is allowed, C < 1, H < 2 or W < 2 (the reference's normalisation divides by W - 1 and H - 1; the projection accepts 1), M < 0 or
+ * P < 0, C (H + 1) (W + 1) >= 2^31 - 1, C M >= 2^30, a workspace that is too small.  M = 0 is legal: the n = 0 case. */
+size_t wm_depth_loss_workspace_bytes(int C, int H, int W, int M, int want_backward);
+wm_status wm_depth_loss(const float* depth, const int64_t* strides, int C, int H, int W, const float* points, const float* depth_gt,
+                        const unsigned char* valid, int M, int want_backward, float* out_loss, void* workspace, size_t workspace_bytes,
+                        void* stream);
+wm_status wm_depth_loss_backward(int C, int H, int W, const float* points, int M, const float* g, float* v_depth,
+                                 const int64_t* v_strides, void* workspace, size_t workspace_bytes, void* stream);
+wm_status wm_project_depth_points(const float* points_world, const float* camtoworlds, const float* Ks, const unsigned char* visible,
+                                  int C, int P, int width, int height, float* points, float* depths, unsigned char* valid, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
