@@ -73,6 +73,7 @@ EXPORTS = [
     "wm_bilagrid_tv", "wm_bilagrid_tv_backward",
     "wm_appearance_forward", "wm_appearance_backward_workspace_bytes", "wm_appearance_backward",
     "wm_depth_loss_workspace_bytes", "wm_depth_loss", "wm_depth_loss_backward", "wm_project_depth_points",
+    "wm_export_splats_workspace_bytes", "wm_export_splats_payload_bytes", "wm_export_splats", "wm_pack_rows_workspace_bytes", "wm_pack_rows",
 ]
 
 _lib = None
@@ -251,6 +252,17 @@ def lib() -> C.CDLL:
     L.wm_depth_loss_backward.restype = i32
     L.wm_project_depth_points.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.wm_project_depth_points.restype = i32
+    i64 = C.c_int64
+    L.wm_export_splats_workspace_bytes.argtypes = [i64, i32, i32]
+    L.wm_export_splats_workspace_bytes.restype = C.c_size_t
+    L.wm_export_splats_payload_bytes.argtypes = [i64, i32, i32]
+    L.wm_export_splats_payload_bytes.restype = C.c_size_t
+    L.wm_export_splats.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(i32), vp]
+    L.wm_export_splats.restype = i32
+    L.wm_pack_rows_workspace_bytes.argtypes = [i64]
+    L.wm_pack_rows_workspace_bytes.restype = C.c_size_t
+    L.wm_pack_rows.argtypes = [C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, vp, i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(i32), vp]
+    L.wm_pack_rows.restype = i32
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_forward.restype = i32
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]

@@ -753,6 +753,54 @@ wm_status wm_depth_loss_backward(int C, int H, int W, const float* points, int M
 wm_status wm_project_depth_points(const float* points_world, const float* camtoworlds, const float* Ks, const unsigned char* visible,
                                   int C, int P, int width, int height, float* points, float* depths, unsigned char* valid, void* stream);
 
+/* ---- Splat export (csrc/export.hip): the file bodies of gsplat's export_splats, gsplat/exporter.py:475-553 with :363-417 ("ply"),
+ * :420-472 ("splat"), :194-360 ("ply_compressed") and the Morton order of :56-85, and of the hand-off file of
+ * src/utils/save_utils.py:133-188 (save_gs_ply).  The body is produced on the device in the byte order of the file; the caller writes the
+ * text header and copies the body to the host once.
+ * inputs.  means [N,3], scales [N,3] (log), quats [N,4], opacities [N] (logit), sh0 [N,3], shN [N,K,3] (K = 0: may be NULL), contiguous fp32
+ *   on the device.  K <= 15 (degree 3).
+ * keep.  A row is kept when all of its 14 + 3K numbers are finite and, for WM_EXPORT_PLY_COMPRESSED, 1 / (1 + exp(-opacity)) >
+ *   opacity_threshold (the reference's default is 1 / 255).  Kept rows stay in input order.  *n_kept (host) is written before the call
+ *   returns: the call synchronises the stream ONCE, to read that count, and launches the packing kernels behind it; the body itself is
+ *   complete in stream order.  It occupies the first payload_bytes(*n_kept, K, format) bytes of out.
+ * WM_EXPORT_PLY.  fp32 rows [x y z | f_dc_0..2 | f_rest_0..3K-1 | opacity | scale_0..2 | rot_0..3], f_rest channel-major (column c K + k is
+ *   shN[i, k, c]), the parameters as given.
+ * WM_EXPORT_SPLAT.  32-byte records in Morton order: 3 x f32 mean, 3 x f32 exp(scale), 4 x u8 trunc(clamp(255 [0.5 + C0 sh0,
+ *   sigmoid(opacity)], 0, 255)), 4 x u8 trunc(clamp(q / |q| 128 + 128, 0, 255)).
+ * WM_EXPORT_PLY_COMPRESSED.  [18 floats per chunk of 256 splats of the Morton order | 4 x u32 per splat | 3K bytes per splat]: the chunk's
+ *   min / max of the means, of the log-scales (clamped to +-20) and of 0.5 + C0 sh0; position 11-10-11, rotation 2 + 3 x 10, scale 11-10-11,
+ *   colour and sigmoid(opacity) 8-8-8-8, each field clamp(floor(v (2^b - 1) + 0.5), 0, 2^b - 1); sh bytes trunc(clamp((x / 8 + 0.5) 256, 0, 255)).
+ * Morton order.  floor((c - min) / len * 1024) per axis over the kept means (len = 0 -> 1), low 10 bits, interleaved z y x; a stable sort,
+ *   so equal codes stay in input order.
+ * All arithmetic is fp32 in the reference's operation order without fused multiply-adds; the results are bitwise reproducible.
+ * Defined here where the reference is not: a chunk quantity with max == min packs as field 0; no kept row gives *n_kept = 0 and an empty
+ *   body; a non-finite opacity drops that row alone (the reference drops every row).
+ * workspace: the _workspace_bytes value for (N, K, format): 12 bytes per row, for the two Morton formats 16 more per row + 24 per 256 rows,
+ *   and the library scan's / sort's scratch counted as 8 bytes per row + 1 MiB (a rule of this library, the same number on every machine;
+ *   WM_ERR_HIP should the library ever ask for more).  out_bytes >= the _payload_bytes value for (N, K, format), the size if every row is kept.
+ *   Both size calls return 0 for arguments the export refuses.
+ * WM_ERR_INVALID, before anything is launched: a null pointer where none is allowed (N = 0 allows null tensors and a null out), N < 0,
+ *   N >= 2^31, K < 0, K > 15, an unknown format, a workspace or an output buffer that is too small. */
+typedef enum { WM_EXPORT_PLY = 0, WM_EXPORT_SPLAT = 1, WM_EXPORT_PLY_COMPRESSED = 2 } wm_export_format;
+size_t wm_export_splats_workspace_bytes(int64_t N, int K, int format);
+size_t wm_export_splats_payload_bytes(int64_t n_kept, int K, int format);
+wm_status wm_export_splats(const float* means, const float* scales, const float* quats, const float* opacities, const float* sh0,
+                           const float* shN, int64_t N, int K, int format, float opacity_threshold, void* workspace, size_t workspace_bytes,
+                           void* out, size_t out_bytes, int* n_kept, void* stream);
+/* The row packer behind WM_EXPORT_PLY, for any column list (src/utils/save_utils.py:154-185: the masked gathers, the zero normals,
+ * scales.log() and the concatenation of save_gs_ply).  out [n_kept, n_cols] fp32: out[r, c] = f_c(col_ptrs[c][i_r * col_strides[c]]) for
+ * the r-th row i_r with keep[i_r] != 0 (keep: N bytes on the device, NULL = every row), f_c = identity (WM_PACK_NONE) or log
+ * (WM_PACK_LOG, the library's logf); col_ptrs[c] = NULL is a column of zeros.  col_ptrs, col_strides (in elements) and col_transforms are
+ * host arrays of n_cols entries, 1 <= n_cols <= 64; the pointers in col_ptrs are device pointers.  *n_kept and the one stream
+ * synchronisation as above.  workspace: the _workspace_bytes value for N (12 bytes per row + the scan's scratch as above);
+ * out_bytes >= N * n_cols * 4.  WM_ERR_INVALID, before anything is launched: a null array, n_cols outside 1..64, a negative stride, an
+ * unknown transform, N < 0, N >= 2^31, a null or too small workspace, a too small or (N > 0) null out. */
+typedef enum { WM_PACK_NONE = 0, WM_PACK_LOG = 1 } wm_pack_transform;
+size_t wm_pack_rows_workspace_bytes(int64_t N);
+wm_status wm_pack_rows(const float* const* col_ptrs, const int* col_strides, const int* col_transforms, int n_cols,
+                       const unsigned char* keep, int64_t N, void* workspace, size_t workspace_bytes, float* out, size_t out_bytes,
+                       int* n_kept, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
