@@ -322,3 +322,14 @@ def make_config(cfg, backbone_dtype="bf16", head_dtype="f16") -> wm_config:
 def ptr(t):
     """Device/host pointer of a torch tensor (or None)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(dev):
+    """The current torch stream of device `dev`, as the entries take it."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def check(st, name):
+    """Raise for a non-zero status of the entry `name`."""
+    if st != 0:
+        raise RuntimeError(f"{name} failed with status {st}")

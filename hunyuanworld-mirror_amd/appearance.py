@@ -17,24 +17,15 @@ call ``sh_degree`` at most the module's.  Anything else raises ``NotImplementedE
 must live on a HIP device."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import nn
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 FEATURE_DIM, EMBED_DIM, MLP_WIDTH, MLP_DEPTH = 32, 16, 64, 2
 TILE = 128          # csrc/wm_kernels.h WM_APPEARANCE_TILE: Gaussians per block tile
 MAX_BLOCKS = 512    # WM_APPEARANCE_MAX_BLOCKS: the backward's grid is min(ceil(N / TILE), MAX_BLOCKS) blocks
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class _Appearance(torch.autograd.Function):
@@ -59,11 +50,10 @@ class _Appearance(torch.autograd.Function):
         grads = [torch.empty_like(t) for t in (W1, b1, W2, b2, W3, b3)]
         ws = torch.empty(max(L_.wm_appearance_backward_workspace_bytes(N, Cn), 1), device=dev, dtype=torch.uint8)
         with torch.cuda.device(dev):
-            st = L_.wm_appearance_backward(_p(features), _p(embeds), int(embeds.shape[0]), _p(ids), _p(dirs), _p(W1), _p(b1), _p(W2), _p(b2),
-                                           _p(W3), _p(b3), N, Cn, module_degree, degree, _p(v_out), _p(v_features), _p(v_dirs), _p(v_embeds),
-                                           *(_p(g) for g in grads), _p(ws), ws.numel(), _stream(dev))
-        if st != 0:
-            raise RuntimeError(f"wm_appearance_backward failed with status {st}")
+            st = L_.wm_appearance_backward(ptr(features), ptr(embeds), int(embeds.shape[0]), ptr(ids), ptr(dirs), ptr(W1), ptr(b1), ptr(W2), ptr(b2),
+                                           ptr(W3), ptr(b3), N, Cn, module_degree, degree, ptr(v_out), ptr(v_features), ptr(v_dirs), ptr(v_embeds),
+                                           *(ptr(g) for g in grads), ptr(ws), ws.numel(), stream(dev))
+        check(st, "wm_appearance_backward")
         return (v_features, v_dirs, v_embeds, *grads, None, None, None)
 
 
@@ -71,10 +61,9 @@ def _forward(features, dirs, embeds, W1, b1, W2, b2, W3, b3, ids, module_degree,
     Cn, N = int(dirs.shape[0]), int(dirs.shape[1])
     out = torch.empty((Cn, N, 3), device=features.device, dtype=torch.float32)
     with torch.cuda.device(features.device):
-        st = _lib.lib().wm_appearance_forward(_p(features), _p(embeds), int(embeds.shape[0]), _p(ids), _p(dirs), _p(W1), _p(b1), _p(W2), _p(b2),
-                                              _p(W3), _p(b3), N, Cn, module_degree, degree, _p(out), _stream(features.device))
-    if st != 0:
-        raise RuntimeError(f"wm_appearance_forward failed with status {st}")
+        st = _lib.lib().wm_appearance_forward(ptr(features), ptr(embeds), int(embeds.shape[0]), ptr(ids), ptr(dirs), ptr(W1), ptr(b1), ptr(W2), ptr(b2),
+                                              ptr(W3), ptr(b3), N, Cn, module_degree, degree, ptr(out), stream(features.device))
+    check(st, "wm_appearance_forward")
     return out
 
 

@@ -13,28 +13,14 @@ NotImplementedError; ``color_correct`` (an evaluation-time least-squares fit) an
 ``slice4d``: they need tensorly) are not part of this library.  No CPU fallback: tensors must live on a HIP device."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 from torch import nn
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 MAX_CELLS = 4096      # include/wm_hip.h: L * Hg * Wg the grid gradient keeps in registers
 MAX_AXIS = 1024
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _status(st, name):
-    if st != 0:
-        raise RuntimeError(f"{name} failed with status {st}")
 
 
 def _slice_forward(grids, idx, xy, rgb):
@@ -43,8 +29,8 @@ def _slice_forward(grids, idx, xy, rgb):
     B, n = int(rgb.shape[0]), int(rgb.shape[1])
     out = torch.empty_like(rgb)
     with torch.cuda.device(rgb.device):
-        st = _lib.lib().wm_bilagrid_slice(_p(grids), G, L, Hg, Wg, _p(idx), _p(xy), _p(rgb), B, n, _p(out), _stream(rgb.device))
-    _status(st, "wm_bilagrid_slice")
+        st = _lib.lib().wm_bilagrid_slice(ptr(grids), G, L, Hg, Wg, ptr(idx), ptr(xy), ptr(rgb), B, n, ptr(out), stream(rgb.device))
+    check(st, "wm_bilagrid_slice")
     return out
 
 
@@ -69,9 +55,9 @@ class _Slice(torch.autograd.Function):
         need = L_.wm_bilagrid_slice_backward_workspace_bytes(G, L, Hg, Wg, B, n) if want_g else 0
         ws = torch.empty(max(need, 1), device=dev, dtype=torch.uint8)
         with torch.cuda.device(dev):
-            st = L_.wm_bilagrid_slice_backward(_p(grids), G, L, Hg, Wg, _p(idx), _p(xy), _p(rgb), B, n, _p(v_out),
-                                               _p(v_grids) if want_g else None, _p(v_rgb) if want_rgb else None, _p(ws), ws.numel(), _stream(dev))
-        _status(st, "wm_bilagrid_slice_backward")
+            st = L_.wm_bilagrid_slice_backward(ptr(grids), G, L, Hg, Wg, ptr(idx), ptr(xy), ptr(rgb), B, n, ptr(v_out),
+                                               ptr(v_grids) if want_g else None, ptr(v_rgb) if want_rgb else None, ptr(ws), ws.numel(), stream(dev))
+        check(st, "wm_bilagrid_slice_backward")
         return v_grids, v_rgb, None, None        # xy: the trainer's constant meshgrid, no gradient
 
 
@@ -145,8 +131,8 @@ class _TotalVariation(torch.autograd.Function):
         g = g.to(torch.float32).contiguous()          # a device scalar: no host sync
         v_x = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            st = _lib.lib().wm_bilagrid_tv_backward(_p(x), B, Ch, L, H, W, _p(g), _p(v_x), _stream(x.device))
-        _status(st, "wm_bilagrid_tv_backward")
+            st = _lib.lib().wm_bilagrid_tv_backward(ptr(x), B, Ch, L, H, W, ptr(g), ptr(v_x), stream(x.device))
+        check(st, "wm_bilagrid_tv_backward")
         return v_x
 
 
@@ -156,8 +142,8 @@ def _tv_forward(x):
     out = torch.empty((), device=x.device, dtype=torch.float32)
     ws = torch.empty(max(L_.wm_bilagrid_tv_workspace_bytes(B, Ch, L, H, W), 1), device=x.device, dtype=torch.uint8)
     with torch.cuda.device(x.device):
-        st = L_.wm_bilagrid_tv(_p(x), B, Ch, L, H, W, _p(out), _p(ws), ws.numel(), _stream(x.device))
-    _status(st, "wm_bilagrid_tv")
+        st = L_.wm_bilagrid_tv(ptr(x), B, Ch, L, H, W, ptr(out), ptr(ws), ws.numel(), stream(x.device))
+    check(st, "wm_bilagrid_tv")
     return out
 
 

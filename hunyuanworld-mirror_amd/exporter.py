@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 FORMATS = {"ply": 0, "splat": 1, "ply_compressed": 2}
 CHUNK_PROPERTIES = ("min_x", "min_y", "min_z", "max_x", "max_y", "max_z", "min_scale_x", "min_scale_y", "min_scale_z", "max_scale_x",
@@ -97,11 +98,9 @@ def export_splats(means: torch.Tensor, scales: torch.Tensor, quats: torch.Tensor
     out = torch.empty(max(out_bytes, 1), device=dev, dtype=torch.uint8)
     n_kept = C.c_int(0)
     with torch.cuda.device(dev):
-        st = L.wm_export_splats(*[C.c_void_p(x.data_ptr() if x.numel() else None) for x in t], N, K, fmt, OPACITY_THRESHOLD,
-                                C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(out.data_ptr()), out_bytes, C.byref(n_kept),
-                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if st != 0:
-        raise RuntimeError(f"wm_export_splats failed with status {st}")
+        st = L.wm_export_splats(*[ptr(x if x.numel() else None) for x in t], N, K, fmt, OPACITY_THRESHOLD, ptr(ws), ws_bytes, ptr(out), out_bytes,
+                                C.byref(n_kept), stream(dev))
+    check(st, "wm_export_splats")
     n = int(n_kept.value)
     header = {"ply": ply_header, "ply_compressed": ply_compressed_header}.get(format, lambda n_, k_: b"")(n, K)
     data = header + _body(out, L.wm_export_splats_payload_bytes(n, K, fmt))
@@ -126,11 +125,9 @@ def _pack_rows(columns, keep: Optional[torch.Tensor], N: int, dev: torch.device)
     out = torch.empty(max(out_bytes, 4), device=dev, dtype=torch.uint8)
     n_kept = C.c_int(0)
     with torch.cuda.device(dev):
-        st = L.wm_pack_rows(ptrs, strides, xfs, n_cols, C.c_void_p(keep.data_ptr() if keep is not None and N else None), N,
-                            C.c_void_p(ws.data_ptr()), ws_bytes, C.c_void_p(out.data_ptr()), out_bytes, C.byref(n_kept),
-                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if st != 0:
-        raise RuntimeError(f"wm_pack_rows failed with status {st}")
+        st = L.wm_pack_rows(ptrs, strides, xfs, n_cols, ptr(keep if N else None), N, ptr(ws), ws_bytes, ptr(out), out_bytes, C.byref(n_kept),
+                            stream(dev))
+    check(st, "wm_pack_rows")
     return out, int(n_kept.value)
 
 

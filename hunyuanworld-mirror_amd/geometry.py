@@ -8,6 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._lib import ptr, stream
 
 
 def depth_to_world_coords_points(depth_map: Optional[torch.Tensor], extrinsic: torch.Tensor, intrinsic: torch.Tensor,
@@ -27,9 +28,7 @@ def depth_to_world_coords_points(depth_map: Optional[torch.Tensor], extrinsic: t
     world = torch.empty(B, H, W, 3, device=d.device)
     cam = torch.empty(B, H, W, 3, device=d.device)
     mask = torch.empty(B, H, W, device=d.device, dtype=torch.uint8)
-    s = C.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    if _lib.lib().wm_depth_to_world(p(d), p(e), p(k), p(world), p(cam), p(mask), B, H, W, C.c_float(eps), s) != 0:
+    if _lib.lib().wm_depth_to_world(ptr(d), ptr(e), ptr(k), ptr(world), ptr(cam), ptr(mask), B, H, W, C.c_float(eps), stream(d.device)) != 0:
         raise RuntimeError("wm_depth_to_world failed")
     return world, cam, mask.bool()
 
@@ -47,9 +46,7 @@ def create_confidence_mask(confidence: torch.Tensor, conf_threshold_percent: flo
     L = _lib.lib()
     wsb = L.wm_confidence_mask_workspace_bytes(n)
     ws = torch.empty(wsb, device=c.device, dtype=torch.uint8)
-    s = C.c_void_p(torch.cuda.current_stream(c.device).cuda_stream)
-    if L.wm_confidence_mask(C.c_void_p(c.data_ptr()), n, C.c_float(conf_threshold_percent), C.c_void_p(mask.data_ptr()),
-                            C.c_void_p(ws.data_ptr()), wsb, s) != 0:
+    if L.wm_confidence_mask(ptr(c), n, C.c_float(conf_threshold_percent), ptr(mask), ptr(ws), wsb, stream(c.device)) != 0:
         raise RuntimeError("wm_confidence_mask failed")
     return mask.bool()
 
@@ -90,10 +87,8 @@ def depth_edge(depth: torch.Tensor, atol: Optional[float] = None, rtol: Optional
     if out.numel() == 0:
         return out.bool()
     m = _view_mask(mask, depth.shape, d.device)
-    s = C.c_void_p(torch.cuda.current_stream(d.device).cuda_stream)
-    st = _lib.lib().wm_depth_edge(C.c_void_p(d.data_ptr()), None if m is None else C.c_void_p(m.data_ptr()), S, H, W, k,
-                                  int(atol is not None), C.c_float(atol or 0.0), int(rtol is not None), C.c_float(rtol or 0.0),
-                                  C.c_void_p(out.data_ptr()), s)
+    st = _lib.lib().wm_depth_edge(ptr(d), ptr(m), S, H, W, k, int(atol is not None), C.c_float(atol or 0.0), int(rtol is not None),
+                                  C.c_float(rtol or 0.0), ptr(out), stream(d.device))
     if st != 0:
         raise RuntimeError(f"wm_depth_edge failed ({st})")
     return out.bool()
@@ -112,9 +107,7 @@ def normals_edge(normals: torch.Tensor, tol: float, kernel_size: int = 3, mask: 
     if out.numel() == 0:
         return out.bool()
     m = _view_mask(mask, normals.shape[:-1], n.device)
-    s = C.c_void_p(torch.cuda.current_stream(n.device).cuda_stream)
-    st = _lib.lib().wm_normals_edge(C.c_void_p(n.data_ptr()), None if m is None else C.c_void_p(m.data_ptr()), S, H, W, k,
-                                    C.c_double(tol), C.c_void_p(out.data_ptr()), s)
+    st = _lib.lib().wm_normals_edge(ptr(n), ptr(m), S, H, W, k, C.c_double(tol), ptr(out), stream(n.device))
     if st != 0:
         raise RuntimeError(f"wm_normals_edge failed ({st})")
     return out.bool()
@@ -154,11 +147,9 @@ def filter_points_mask(depth_conf: torch.Tensor, depth: torch.Tensor, normals: t
         L = _lib.lib()
         wsb = L.wm_point_filter_mask_workspace_bytes(S, H, W)
         ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
-        s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        st = L.wm_point_filter_mask(p(c), p(d), p(n), S, H, W, int(bool(apply_confidence_mask)), C.c_double(confidence_percentile),
+        st = L.wm_point_filter_mask(ptr(c), ptr(d), ptr(n), S, H, W, int(bool(apply_confidence_mask)), C.c_double(confidence_percentile),
                                     int(bool(apply_edge_mask)), C.c_double(edge_normal_threshold), C.c_float(edge_depth_threshold),
-                                    p(thr), p(out), p(ws), wsb, s)
+                                    ptr(thr), ptr(out), ptr(ws), wsb, stream(dev))
         if st != 0:
             raise RuntimeError(f"wm_point_filter_mask failed ({st})")
     return (out.bool(), thr) if return_thresholds else out.bool()

@@ -31,9 +31,7 @@ def preprocess_rgb(img_u8: torch.Tensor, preprocessing_mode: str = "crop", outpu
     out = torch.empty(3, oh.value, ow.value, device=img_u8.device)
     wsb = L.wm_preprocess_image_workspace_bytes(H, W, mode, output_size)
     ws = torch.empty(wsb, device=img_u8.device, dtype=torch.uint8)
-    s = C.c_void_p(torch.cuda.current_stream(img_u8.device).cuda_stream)
-    if L.wm_preprocess_image(C.c_void_p(img_u8.data_ptr()), H, W, mode, output_size, C.c_void_p(out.data_ptr()),
-                             C.c_void_p(ws.data_ptr()), wsb, s) != 0:
+    if L.wm_preprocess_image(_lib.ptr(img_u8), H, W, mode, output_size, _lib.ptr(out), _lib.ptr(ws), wsb, _lib.stream(img_u8.device)) != 0:
         raise RuntimeError("wm_preprocess_image failed")
     return out
 

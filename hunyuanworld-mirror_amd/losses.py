@@ -24,6 +24,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 _PADDING = {"same": 0, "valid": 1}
 
@@ -59,11 +60,9 @@ def _forward(a: torch.Tensor, b: torch.Tensor, valid: int, want_backward: bool):
     need = size(B, Ch, H, W)
     ws = torch.empty(need, device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
-        st = L.wm_photometric_loss(C.c_void_p(a.data_ptr()), _strides(a), C.c_void_p(b.data_ptr()), _strides(b), B, Ch, H, W, valid,
-                                   1 if want_backward else 0, C.c_void_p(ssim.data_ptr()), C.c_void_p(l1.data_ptr()),
-                                   C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if st != 0:
-        raise RuntimeError(f"wm_photometric_loss failed with status {st}")
+        st = L.wm_photometric_loss(ptr(a), _strides(a), ptr(b), _strides(b), B, Ch, H, W, valid, 1 if want_backward else 0, ptr(ssim), ptr(l1),
+                                   ptr(ws), ws.numel(), stream(dev))
+    check(st, "wm_photometric_loss")
     return ssim, l1, ws
 
 
@@ -94,11 +93,9 @@ class _PhotometricLoss(torch.autograd.Function):
         grad = torch.empty_like(a)                          # a's strides (forward made sure of it)
         ws = ctx.ws
         with torch.cuda.device(dev):
-            st = L.wm_photometric_loss_backward(C.c_void_p(a.data_ptr()), _strides(a), C.c_void_p(b.data_ptr()), _strides(b), B, Ch, H, W,
-                                                ctx.valid, C.c_void_p(g.data_ptr()), C.c_void_p(g.data_ptr() + 4), C.c_void_p(grad.data_ptr()),
-                                                C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if st != 0:
-            raise RuntimeError(f"wm_photometric_loss_backward failed with status {st}")
+            st = L.wm_photometric_loss_backward(ptr(a), _strides(a), ptr(b), _strides(b), B, Ch, H, W, ctx.valid, ptr(g[0]), ptr(g[1]), ptr(grad),
+                                                ptr(ws), ws.numel(), stream(dev))
+        check(st, "wm_photometric_loss_backward")
         return grad.to(ctx.dtype), None, None               # the target: no gradient
 
 
@@ -171,11 +168,9 @@ def _depth_forward(d, p, gt, v, M, want_backward: bool):
     out = torch.empty((), device=dev, dtype=torch.float32)
     ws = torch.empty(L.wm_depth_loss_workspace_bytes(Cn, H, W, M, 1 if want_backward else 0), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
-        st = L.wm_depth_loss(C.c_void_p(d.data_ptr()), _strides3(d), Cn, H, W, C.c_void_p(p.data_ptr()), C.c_void_p(gt.data_ptr()),
-                             C.c_void_p(v.data_ptr() if v is not None else None), M, 1 if want_backward else 0, C.c_void_p(out.data_ptr()),
-                             C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if st != 0:
-        raise RuntimeError(f"wm_depth_loss failed with status {st}")
+        st = L.wm_depth_loss(ptr(d), _strides3(d), Cn, H, W, ptr(p), ptr(gt), ptr(v), M, 1 if want_backward else 0, ptr(out), ptr(ws), ws.numel(),
+                             stream(dev))
+    check(st, "wm_depth_loss")
     return out, ws
 
 
@@ -201,11 +196,8 @@ class _DepthLoss(torch.autograd.Function):
         grad = torch.empty((Cn, H, W), device=dev, dtype=torch.float32)        # dense, whatever the strides of the image were
         ws = ctx.ws
         with torch.cuda.device(dev):
-            st = L.wm_depth_loss_backward(Cn, H, W, C.c_void_p(p.data_ptr()), ctx.M, C.c_void_p(g.data_ptr()), C.c_void_p(grad.data_ptr()),
-                                          _strides3(grad), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if st != 0:
-            raise RuntimeError(f"wm_depth_loss_backward failed with status {st}")
+            st = L.wm_depth_loss_backward(Cn, H, W, ptr(p), ctx.M, ptr(g), ptr(grad), _strides3(grad), ptr(ws), ws.numel(), stream(dev))
+        check(st, "wm_depth_loss_backward")
         return grad.reshape(ctx.shape).to(ctx.dtype), None, None, None, None, None
 
 
@@ -253,10 +245,7 @@ def project_depth_points(points_world: torch.Tensor, camtoworlds: torch.Tensor, 
     depths = torch.empty((Cn, P), device=dev, dtype=torch.float32)
     valid = torch.empty((Cn, P), device=dev, dtype=torch.bool)
     with torch.cuda.device(dev):
-        st = L.wm_project_depth_points(C.c_void_p(pw.data_ptr()), C.c_void_p(c2w.data_ptr()), C.c_void_p(K.data_ptr()),
-                                       C.c_void_p(vis.data_ptr() if vis is not None else None), Cn, P, int(width), int(height),
-                                       C.c_void_p(points.data_ptr()), C.c_void_p(depths.data_ptr()), C.c_void_p(valid.data_ptr()),
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if st != 0:
-        raise RuntimeError(f"wm_project_depth_points failed with status {st}")
+        st = L.wm_project_depth_points(ptr(pw), ptr(c2w), ptr(K), ptr(vis), Cn, P, int(width), int(height), ptr(points), ptr(depths), ptr(valid),
+                                       stream(dev))
+    check(st, "wm_project_depth_points")
     return points, depths, valid

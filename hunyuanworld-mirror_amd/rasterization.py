@@ -1,30 +1,30 @@
-"""Host-side mirror of the reference's ``Rasterizer`` (src/models/models/rasterization.py:17-93) over the C ABI entry
-``wm_rasterize_splats`` (hand-written HIP: projection, tile binning, radix sort, tile compositing).  Same method names,
-argument order and return triples, so ``model.gs_renderer.rasterizer.rasterize_batches(...)`` as called by
-``render_interpolated_video`` (src/utils/render_utils.py:242-312) and ``GaussianSplatRenderer.render``
+"""Host-side mirror of the reference's ``Rasterizer`` (src/models/models/rasterization.py:17-93) over the C ABI entries
+``wm_rasterize_splats_opt`` / ``wm_rasterize_splats_backward_opt`` (hand-written HIP: projection, tile binning, radix sort, tile
+compositing).  Same method names, argument order and return triples, so ``model.gs_renderer.rasterizer.rasterize_batches(...)`` as
+called by ``render_interpolated_video`` (src/utils/render_utils.py:242-312) and ``GaussianSplatRenderer.render``
 (rasterization.py:221-241) keeps working.  No CPU fallback: tensors must live on a HIP device.
 
-Differentiable: when autograd is recording and any of means / quats / scales / opacities / colors requires grad, the call goes
-through ``wm_rasterize_splats_backward`` on ``.backward()`` (what gsplat's CUDA extension gives the reference's post-3DGS
+Differentiable: when autograd is recording and any of means / quats / scales / opacities / colors requires grad, ``.backward()`` is
+one ``wm_rasterize_splats_backward_opt`` call (what gsplat's CUDA extension gives the reference's post-3DGS
 optimisation).  No packed / sparse gradients.
 
 Cameras: by default ``camtoworlds`` and ``Ks`` get no gradient (``None``).  ``Rasterizer(camera_grad=True)`` makes ``camtoworlds``
 differentiable (gsplat: the ``viewmats`` gradient of ``_FullyFusedProjection``, which the reference trainer's ``--pose_opt`` trains a
 pose.CameraOptModule on): the inverse ``viewmats = inv(camtoworlds)`` is then taken once in the graph, the kernels see its values,
-``wm_rasterize_splats_backward_cam`` returns the gradient of the rendered images with respect to ``viewmats`` and torch's own inverse
+the backward call returns the gradient of the rendered images with respect to ``viewmats`` and torch's own inverse
 backward carries it on to ``camtoworlds`` and whatever produced it.  It works on both routes and when no splat tensor requires grad
 (pose-only refinement); forward outputs are the same bits either way.  ``Ks`` gets ``None`` in every case, as in gsplat.
 
 View-dependent colour: ``colors [N,K,3]`` with ``sh_degree`` 1-3, ``(sh_degree + 1)^2 <= K`` (gsplat/rendering.py:509-525; the reference
-trainer raises ``sh_degree_to_use`` while it trains, simple_trainer_worldmirror.py:613, :738-746), goes through ``wm_rasterize_splats_sh``
-and ``wm_rasterize_splats_backward_sh`` on every route.  The colour of a (camera, Gaussian) pair is evaluated along ``means - campos``,
-``campos = camtoworlds[:, :3, 3]`` (gsplat's ``inverse(viewmats)[:, :3, 3]``); ``colors.grad`` has the full ``[N,K,3]`` shape with exact zeros
-in the bands at or above ``(sh_degree + 1)^2``, ``means.grad`` includes the direction's term, and with ``camera_grad`` ``campos`` is a
-second graph tensor beside ``viewmats``, so that ``camtoworlds.grad`` is the sum of both.  ``sh_degree`` 0 and ``None`` go as before.
+trainer raises ``sh_degree_to_use`` while it trains, simple_trainer_worldmirror.py:613, :738-746), works on every route.  The colour of
+a (camera, Gaussian) pair is evaluated along ``means - campos``, ``campos = camtoworlds[:, :3, 3]`` (gsplat's
+``inverse(viewmats)[:, :3, 3]``); ``colors.grad`` has the full ``[N,K,3]`` shape with exact zeros in the bands at or above
+``(sh_degree + 1)^2``, ``means.grad`` includes the direction's term, and with ``camera_grad`` ``campos`` is a second graph tensor beside
+``viewmats``, so that ``camtoworlds.grad`` is the sum of both.  ``sh_degree`` 0 and ``None`` go as before.
 
 Per-camera colours: ``colors [C,N,3]`` with ``sh_degree=None`` (post-activation colours with a camera axis, as the reference trainer's
 ``--app_opt`` passes them: ``sigmoid(app_module(...) + colors)``, simple_trainer_worldmirror.py:603-611) render pair (c, g) with
-``colors[c, g]`` as it is, on every route, through the entries with options (``colors_are_sh0 = WM_COLORS_PER_CAMERA``); ``colors.grad`` is
+``colors[c, g]`` as it is, on every route (``colors_are_sh0 = WM_COLORS_PER_CAMERA``); ``colors.grad`` is
 ``[C,N,3]`` with exact zeros where a camera culled the Gaussian.  A leading size other than the number of cameras is a ``ValueError``.
 
 ``rasterize_splats(..., return_info=True)`` also returns what gsplat.rasterization's ``info`` gives a densification strategy
@@ -37,11 +37,12 @@ gsplat's own call: the module-level ``rasterization(...)`` has gsplat.rasterizat
 return (gsplat/rendering.py), as the reference's post-3DGS trainer calls it (simple_trainer_worldmirror.py:619-642, :741-752): world-to-camera
 ``viewmats`` (differentiable where they require grad), ``render_mode`` "RGB" | "D" | "ED" | "RGB+D" | "RGB+ED", ``rasterize_mode`` "classic" |
 "antialiased", ``near_plane``, ``far_plane``, ``eps2d``, ``radius_clip`` and differentiable ``backgrounds [C,3]``.  These options travel as one
-``wm_raster_options`` struct to ``wm_rasterize_splats_opt`` / ``wm_rasterize_splats_backward_opt``.  ``Rasterizer`` takes
+``wm_raster_options`` struct (an ``_Opts`` here) on every call.  ``Rasterizer`` takes
 ``rasterization_mode="antialiased"`` and the same keywords except ``render_mode`` (its triple stays rgb, expected depth, alpha, as in the
-reference class); a classic ``Rasterizer`` called with none of them goes through the entries without options, as before — with gsplat's default
-values both routes give the same bits.  What the kernels do not do (packed, sparse_grad, distributed, tile_size != 16, non-pinhole cameras,
-with_ut, with_eval3d, colour channels other than 3, unknown keywords) raises ``NotImplementedError`` naming the argument."""
+reference class); what is not given takes gsplat's default value.  Every call of either surface goes through the ``_opt`` pair: the C ABI
+keeps its older entries without options as wrappers around that pair, which give the same bits.  What the kernels do not do (packed,
+sparse_grad, distributed, tile_size != 16, non-pinhole cameras, with_ut, with_eval3d, colour channels other than 3, unknown keywords)
+raises ``NotImplementedError`` naming the argument."""
 from __future__ import annotations
 
 import collections
@@ -50,6 +51,7 @@ import weakref
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
@@ -65,29 +67,42 @@ class _RasterizeSplats(torch.autograd.Function):
                 backgrounds):
         # viewmats: None, or with camera_grad inv(camtoworlds) as a graph tensor: the input that receives the camera gradient;
         # campos: None, or with camera_grad and sh_degree > 0 the camera positions as a graph tensor: receives the colour's camera term
-        # opts: None (today's entries) or the _Opts of the _opt entries; backgrounds: None or [C,3], receives its gradient
+        # opts: the _Opts of the call; backgrounds: None or [C,3], receives its gradient
         rgb, depth, alpha, state = rz._forward(means, quats, scales, opacities, _cin(colors, is_sh, sh_degree), is_sh, camtoworlds, Ks, width, height,
                                                own_workspace=True, viewmats=viewmats, sh_degree=sh_degree, campos=campos, opts=opts,
                                                backgrounds=backgrounds)
         ctx.state, ctx.geom = state, (is_sh, width, height)
-        ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
-        ctx.bg_meta = None if backgrounds is None else (backgrounds.shape, backgrounds.dtype)
-        if backgrounds is None:
-            ctx.save_for_backward(depth)     # the one forward output the backward reads
-        else:
-            ctx.save_for_backward(depth, alpha)     # v_backgrounds reads the forward's alpha
+        _keep(ctx, (means, quats, scales, opacities, colors), backgrounds, depth, alpha)
         return rgb, depth, alpha
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
-        depth, alpha = (*ctx.saved_tensors, None)[:2]
-        want_bg = ctx.bg_meta is not None and ctx.needs_input_grad[15]
-        grads, _, _, v_vm, v_cp, v_bg = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), False, False, ctx.needs_input_grad[11],
-                                                  ctx.needs_input_grad[12], want_bg, alpha)
+        grads, _, _, v_vm, v_cp, v_bg = _node_backward(ctx, (v_rgb, v_depth, v_alpha), False, False, first=6)
         # camtoworlds, Ks: no gradient of their own (camtoworlds gets its through viewmats and campos)
-        return (None, None, None, None, None, None, *_shape_grads(grads, ctx.meta, ctx.geom[0] == 1 and not ctx.state[10], ctx.needs_input_grad[6:11]),
-                v_vm, v_cp, None, None, _shape_bg(v_bg, ctx.bg_meta))
+        return (None, None, None, None, None, None, *grads, v_vm, v_cp, None, None, v_bg)
+
+
+def _keep(ctx, splat_in, backgrounds, depth, alpha):
+    """what a node's backward needs beside ctx.state and ctx.geom: the shapes and dtypes its gradients go back in, and the forward outputs
+    the backward call reads"""
+    ctx.meta = [(t.shape, t.dtype) for t in splat_in]
+    ctx.bg_meta = None if backgrounds is None else (backgrounds.shape, backgrounds.dtype)
+    if backgrounds is None:
+        ctx.save_for_backward(depth)     # the one forward output the backward reads
+    else:
+        ctx.save_for_backward(depth, alpha)     # v_backgrounds reads the forward's alpha
+
+
+def _node_backward(ctx, cotangents, want_means2d, want_absgrad, first):
+    """_backward for a node whose inputs are ..., means, quats, scales, opacities, colors, viewmats, campos, ..., backgrounds with means at
+    index `first` -> the five splat gradients and v_backgrounds in their inputs' shapes and dtypes, the rest as _backward returns it"""
+    depth, alpha = (*ctx.saved_tensors, None)[:2]
+    need = ctx.needs_input_grad
+    grads, v2d, v2d_abs, v_vm, v_cp, v_bg = _backward(ctx.state, depth, ctx.geom, cotangents, want_means2d, want_absgrad, need[first + 5],
+                                                      need[first + 6], ctx.bg_meta is not None and need[-1], alpha)
+    grads = _shape_grads(grads, ctx.meta, ctx.geom[0] == 1 and not ctx.state.sh_degree, need[first:first + 5])
+    return grads, v2d, v2d_abs, v_vm, v_cp, _shape_bg(v_bg, ctx.bg_meta)
 
 
 def _cin(colors, is_sh, sh_degree):
@@ -95,83 +110,38 @@ def _cin(colors, is_sh, sh_degree):
     return colors[:, 0, :] if is_sh == 1 and not sh_degree else colors
 
 
+# what _forward hands to _backward and _means2d: its fp32 inputs, the workspace it filled and the pair capacity / count of that workspace
+_State = collections.namedtuple("_State", "means quats scales opacities cin viewmats Ks ws cap n sh_degree campos opts backgrounds")
+
+
 def _backward(state, depth, geom, cotangents, want_means2d, want_absgrad, want_cam=False, want_campos=False, want_bg=False, alpha=None):
-    """One fused backward call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs, v_viewmats, v_campos,
-    v_backgrounds (each None unless asked for).  Which entry runs:
-      forward with options (state[12] is an _Opts)  wm_rasterize_splats_backward_opt, whatever else is asked for; v_backgrounds [C,3] reads
-                                                    the forward's alpha
-      forward without options, SH degree 1-3        the _sh entry (g_colors [N,K,3]; v_campos [C,3]: gradient of the camera positions)
-      ... want_cam                                  the _cam entry (v_viewmats [C,4,4]: gradient of the world-to-camera matrices)
-      ... want_means2d                              the _ex entry
-      ... none of these                             wm_rasterize_splats_backward
-    The five splat gradients are the same bits on every one of them."""
-    L = _lib.lib()
-    means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, n, sh_degree, campos, opts, bg = state
+    """One fused wm_rasterize_splats_backward_opt call -> [g_means, g_quats, g_scales, g_opacities, g_colors], v_means2d, v_means2d_abs,
+    v_viewmats, v_campos, v_backgrounds (each None unless asked for): g_colors is [N,K,3] for SH degree 1-3, v_viewmats [C,4,4] the gradient
+    of the world-to-camera matrices, v_campos [C,3] that of the camera positions (SH degree 1-3 only), and v_backgrounds [C,3] reads the
+    forward's alpha.  The five splat gradients are the same bits whatever else is asked for."""
+    L, s = _lib.lib(), state
     is_sh, width, height = geom
-    dev = means.device
-    N, V = int(means.shape[0]), int(viewmats.shape[0])
+    dev = s.means.device
+    N, V = int(s.means.shape[0]), int(s.viewmats.shape[0])
     cot = [torch.zeros((V, height, width, ch), device=dev) if v is None else _f32(v) for v, ch in zip(cotangents, (3, 1, 1))]
-    g_means, g_quats, g_scales = torch.empty_like(means), torch.empty_like(quats), torch.empty_like(scales)
-    g_opac, g_col = torch.empty_like(opacities), torch.empty_like(cin)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    v2d = v2d_abs = v_vm = v_cp = v_bg = None
-    if opts is not None:
-        if want_means2d:
-            v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
-            v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
-        want_absgrad = bool(want_means2d and want_absgrad)
-        v_vm = torch.empty((V, 4, 4), device=dev, dtype=torch.float32) if want_cam else None
-        v_cp = torch.empty((V, 3), device=dev, dtype=torch.float32) if want_campos and sh_degree else None
-        v_bg = torch.empty((V, 3), device=dev, dtype=torch.float32) if want_bg and bg is not None else None
-        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_opt(N, V, width, height, n, int(want_absgrad), int(v_vm is not None), sh_degree,
-                                                                      int(v_cp is not None), int(v_bg is not None)), device=dev, dtype=torch.uint8)
-        st = L.wm_rasterize_splats_backward_opt(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, int(cin.shape[1]) if sh_degree else 0,
-                                                sh_degree, p(campos) if sh_degree else None, N, p(viewmats), p(Ks), V, width, height,
-                                                C.byref(opts.struct(bg)), p(ws), ws.numel(), cap, n, None, p(depth),
-                                                None if v_bg is None else p(_f32(alpha)), p(cot[0]), p(cot[1]), p(cot[2]), p(g_means), p(g_quats),
-                                                p(g_scales), p(g_opac), p(g_col), p(v2d), p(v2d_abs), int(want_absgrad), p(v_vm), p(v_cp), p(v_bg),
-                                                p(gws), gws.numel(), stream)
-    elif sh_degree:
-        if want_means2d:
-            v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
-            v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
-        want_absgrad = bool(want_means2d and want_absgrad)
-        v_vm = torch.empty((V, 4, 4), device=dev, dtype=torch.float32) if want_cam else None
-        v_cp = torch.empty((V, 3), device=dev, dtype=torch.float32) if want_campos else None
-        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_sh(N, V, width, height, n, int(want_absgrad), int(bool(want_cam)), int(bool(want_campos))),
-                          device=dev, dtype=torch.uint8)
-        st = L.wm_rasterize_splats_backward_sh(p(means), p(quats), p(scales), p(opacities), p(cin), int(cin.shape[1]), sh_degree, p(campos), N,
-                                               p(viewmats), p(Ks), V, width, height, p(ws), ws.numel(), cap, n, None, p(depth), None,
-                                               p(cot[0]), p(cot[1]), p(cot[2]), p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col),
-                                               p(v2d), p(v2d_abs), int(want_absgrad), p(v_vm), p(v_cp), p(gws), gws.numel(), stream)
-    elif want_cam:
-        if want_means2d:
-            v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
-            v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
-        want_absgrad = bool(want_means2d and want_absgrad)
-        v_vm = torch.empty((V, 4, 4), device=dev, dtype=torch.float32)
-        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_cam(N, V, width, height, n, int(want_absgrad)), device=dev, dtype=torch.uint8)
-        st = L.wm_rasterize_splats_backward_cam(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
-                                                p(ws), ws.numel(), cap, n, None, p(depth), None, p(cot[0]), p(cot[1]), p(cot[2]),
-                                                p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col), p(v2d), p(v2d_abs), int(want_absgrad),
-                                                p(v_vm), p(gws), gws.numel(), stream)
-    elif not want_means2d:
-        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes(N, V, width, height, n), device=dev, dtype=torch.uint8)
-        st = L.wm_rasterize_splats_backward(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
-                                            p(ws), ws.numel(), cap, n, None, p(depth), None, p(cot[0]), p(cot[1]), p(cot[2]),
-                                            p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col), p(gws), gws.numel(), stream)
-    else:
-        v2d = torch.empty((V, N, 2), device=dev, dtype=torch.float32)
-        v2d_abs = torch.empty((V, N, 2), device=dev, dtype=torch.float32) if want_absgrad else None
-        gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_ex(N, V, width, height, n, int(want_absgrad)), device=dev, dtype=torch.uint8)
-        st = L.wm_rasterize_splats_backward_ex(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, p(viewmats), p(Ks), V, width, height,
-                                               p(ws), ws.numel(), cap, n, None, p(depth), None, p(cot[0]), p(cot[1]), p(cot[2]),
-                                               p(g_means), p(g_quats), p(g_scales), p(g_opac), p(g_col), p(v2d), p(v2d_abs), int(want_absgrad),
-                                               p(gws), gws.numel(), stream)
-    if st != 0:
-        raise RuntimeError(f"wm_rasterize_splats_backward failed with status {st}")
-    return [g_means, g_quats, g_scales, g_opac, g_col], v2d, v2d_abs, v_vm, v_cp, v_bg
+    grads = [torch.empty_like(t) for t in (s.means, s.quats, s.scales, s.opacities, s.cin)]
+    want_absgrad = bool(want_means2d and want_absgrad)
+    f32 = dict(device=dev, dtype=torch.float32)
+    v2d = torch.empty((V, N, 2), **f32) if want_means2d else None
+    v2d_abs = torch.empty((V, N, 2), **f32) if want_absgrad else None
+    v_vm = torch.empty((V, 4, 4), **f32) if want_cam else None
+    v_cp = torch.empty((V, 3), **f32) if want_campos and s.sh_degree else None
+    v_bg = torch.empty((V, 3), **f32) if want_bg and s.backgrounds is not None else None
+    gws = torch.empty(L.wm_rasterize_backward_workspace_bytes_opt(N, V, width, height, s.n, int(want_absgrad), int(v_vm is not None), s.sh_degree,
+                                                                  int(v_cp is not None), int(v_bg is not None)), device=dev, dtype=torch.uint8)
+    st = L.wm_rasterize_splats_backward_opt(ptr(s.means), ptr(s.quats), ptr(s.scales), ptr(s.opacities), ptr(s.cin), is_sh,
+                                            int(s.cin.shape[1]) if s.sh_degree else 0, s.sh_degree, ptr(s.campos) if s.sh_degree else None, N,
+                                            ptr(s.viewmats), ptr(s.Ks), V, width, height, C.byref(s.opts.struct(s.backgrounds)), ptr(s.ws),
+                                            s.ws.numel(), s.cap, s.n, None, ptr(depth), None if v_bg is None else ptr(_f32(alpha)),
+                                            ptr(cot[0]), ptr(cot[1]), ptr(cot[2]), *(ptr(g) for g in grads), ptr(v2d), ptr(v2d_abs),
+                                            int(want_absgrad), ptr(v_vm), ptr(v_cp), ptr(v_bg), ptr(gws), gws.numel(), stream(dev))
+    check(st, "wm_rasterize_splats_backward")
+    return grads, v2d, v2d_abs, v_vm, v_cp, v_bg
 
 
 def _shape_bg(v_bg, meta):
@@ -233,28 +203,19 @@ class _CompositeWithInfo(torch.autograd.Function):
     def forward(ctx, shared, geom, want_absgrad, means2d, means, quats, scales, opacities, colors, viewmats, campos, backgrounds):
         rgb, depth, alpha = shared.pop("out")
         ctx.state, ctx.geom, ctx.want_absgrad = shared.pop("state"), geom, want_absgrad
-        ctx.meta = [(t.shape, t.dtype) for t in (means, quats, scales, opacities, colors)]
-        ctx.bg_meta = None if backgrounds is None else (backgrounds.shape, backgrounds.dtype)
         ctx.means2d_ref, ctx.shared = shared["means2d_ref"], shared
-        if backgrounds is None:
-            ctx.save_for_backward(depth)
-        else:
-            ctx.save_for_backward(depth, alpha)
+        _keep(ctx, (means, quats, scales, opacities, colors), backgrounds, depth, alpha)
         return rgb, depth, alpha
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, v_rgb, v_depth, v_alpha):
-        depth, alpha = (*ctx.saved_tensors, None)[:2]
-        want_bg = ctx.bg_meta is not None and ctx.needs_input_grad[11]
-        grads, v2d, v2d_abs, v_vm, v_cp, v_bg = _backward(ctx.state, depth, ctx.geom, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad,
-                                                          ctx.needs_input_grad[9], ctx.needs_input_grad[10], want_bg, alpha)
+        grads, v2d, v2d_abs, v_vm, v_cp, v_bg = _node_backward(ctx, (v_rgb, v_depth, v_alpha), True, ctx.want_absgrad, first=4)
         m2 = ctx.means2d_ref()
         if ctx.want_absgrad and m2 is not None:
             m2.absgrad = v2d_abs
         ctx.shared["v_means2d"] = v2d
-        return (None, None, None, v2d, *_shape_grads(grads, ctx.meta, ctx.geom[0] == 1 and not ctx.state[10], ctx.needs_input_grad[4:9]), v_vm, v_cp,
-                _shape_bg(v_bg, ctx.bg_meta))
+        return (None, None, None, v2d, *grads, v_vm, v_cp, v_bg)
 
 
 class _Opts(collections.namedtuple("_Opts", "antialiased depth_mode eps2d near_plane far_plane radius_clip")):
@@ -302,20 +263,16 @@ class Rasterizer:
         is always the unpacked [C,N,...] one).  absgrad (None: self.abs_grad) is read on the return_info route only.
         near_plane / far_plane / eps2d / radius_clip (gsplat's defaults 0.01 / 1e10 / 0.3 / 0) and backgrounds [C,3] (differentiable) are
         gsplat.rasterization's; depth stays the expected depth (the reference class hard-wires render_mode "RGB+ED", so render_mode here is a
-        TypeError as it is there).  A classic rasteriser called with none of them takes the entries without options."""
+        TypeError as it is there).  They reach the kernels as an _Opts on every call, given or not."""
         if kwargs:
             raise TypeError(f"unsupported gsplat.rasterization arguments: {sorted(kwargs)}")
         given = dict(near_plane=near_plane, far_plane=far_plane, eps2d=eps2d, radius_clip=radius_clip)
-        opts = None
-        if self.rasterization_mode == "antialiased" or backgrounds is not None or any(v is not None for v in given.values()):
-            opts = _Opts(int(self.rasterization_mode == "antialiased"), 0,
-                         **{k: _OPTION_DEFAULTS[k] if v is None else float(v) for k, v in given.items()})
+        opts = _Opts(int(self.rasterization_mode == "antialiased"), 0, **{k: _OPTION_DEFAULTS[k] if v is None else float(v) for k, v in given.items()})
         if means.device.type != "cuda":
             raise RuntimeError("the rasteriser runs in libwm_hip.so on the GPU: move the splats to a HIP device")
         L = 0
         if colors.dim() == 3 and sh_degree is None:      # post-activation colours per camera [C, N, 3]
             cin, is_sh = _per_camera(colors, int(camtoworlds.shape[0]), int(means.shape[0])), PER_CAMERA
-            opts = opts or _Opts(0, 0, **_OPTION_DEFAULTS)   # this colour form lives in the entries with options
         elif colors.dim() == 3:          # SH coefficients [N, K, 3]
             if sh_degree is None or not 0 <= int(sh_degree) <= 3:
                 raise NotImplementedError(f"SH degrees 0 to 3 are built, not sh_degree = {sh_degree}")
@@ -353,7 +310,7 @@ class Rasterizer:
             return torch.linalg.inv(camtoworlds.to(torch.float32))
         return None
 
-    def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad, sh_degree=0, opts=None, backgrounds=None, cameras=None):
+    def _with_info(self, splat_in, cin, is_sh, camtoworlds, Ks, width, height, want_absgrad, sh_degree, opts, backgrounds=None, cameras=None):
         """cameras: None (camtoworlds given), or (viewmats, campos) with camtoworlds = None: the world-to-camera matrices themselves and, for SH
         degree 1-3, the camera positions, graph tensors where they require grad (the module-level rasterization())"""
         if cameras is None:
@@ -382,24 +339,21 @@ class Rasterizer:
     @staticmethod
     def _means2d(state, radii, width, height):
         """the pixel-space means of the forward that left `state`, [C,N,2], zero where culled"""
-        means, viewmats, ws, cap = state[0], state[5], state[7], state[8]
-        N, V = int(means.shape[0]), int(viewmats.shape[0])
-        m2 = torch.empty((V, N, 2), device=means.device, dtype=torch.float32)
-        st = _lib.lib().wm_rasterize_means2d(C.c_void_p(ws.data_ptr()), ws.numel(), N, V, width, height, cap, C.c_void_p(radii.data_ptr()),
-                                             C.c_void_p(m2.data_ptr()), C.c_void_p(torch.cuda.current_stream(means.device).cuda_stream))
-        if st != 0:
-            raise RuntimeError(f"wm_rasterize_means2d failed with status {st}")
+        N, V = int(state.means.shape[0]), int(state.viewmats.shape[0])
+        m2 = torch.empty((V, N, 2), device=state.means.device, dtype=torch.float32)
+        st = _lib.lib().wm_rasterize_means2d(ptr(state.ws), state.ws.numel(), N, V, width, height, state.cap, ptr(radii), ptr(m2),
+                                             stream(state.means.device))
+        check(st, "wm_rasterize_means2d")
         return m2
 
-    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, radii=None, viewmats=None,
-                 sh_degree=0, campos=None, opts=None, backgrounds=None):
-        """One wm_rasterize_splats call (sh_degree 1-3: wm_rasterize_splats_sh, cin the coefficients [N,K,3]; with opts, an _Opts, and
-        backgrounds [C,3] or None: wm_rasterize_splats_opt in either colour form; camtoworlds may then be None when viewmats, and for SH
-        degree 1-3 campos, are given).  own_workspace: a workspace
-        of this call's own (kept by the autograd node until its backward has run) instead of the rasteriser's reusable one.  radii:
-        optional [C,N,2] int32 output.  viewmats, campos: the inverse of camtoworlds and its translation column where the caller has taken
-        them already (camera_grad); their values are used, detached.
-        -> rgb, depth, alpha, state for the backward."""
+    def _forward(self, means, quats, scales, opacities, cin, is_sh, camtoworlds, Ks, width, height, own_workspace, opts, radii=None, viewmats=None,
+                 sh_degree=0, campos=None, backgrounds=None):
+        """One wm_rasterize_splats_opt call.  cin: the colours [N,3] or [C,N,3], or for sh_degree 1-3 the coefficients [N,K,3]; opts: the
+        _Opts of the call; backgrounds: [C,3] or None; camtoworlds may be None when viewmats, and for SH degree 1-3 campos, are given.
+        own_workspace: a workspace of this call's own (kept by the autograd node until its backward has run) instead of the rasteriser's
+        reusable one.  radii: optional [C,N,2] int32 output.  viewmats, campos: the inverse of camtoworlds and its translation column where
+        the caller has taken them already (camera_grad); their values are used, detached.
+        -> rgb, depth, alpha, the _State for the backward."""
         L = _lib.lib()
         dev = means.device
         N, V = int(means.shape[0]), int((viewmats if camtoworlds is None else camtoworlds).shape[0])
@@ -415,8 +369,6 @@ class Rasterizer:
         rgb = torch.empty((V, height, width, 3), device=dev, dtype=torch.float32)
         depth = torch.empty((V, height, width, 1), device=dev, dtype=torch.float32)
         alpha = torch.empty((V, height, width, 1), device=dev, dtype=torch.float32)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         cap = max(self._cap, 8 * N * V, 1 << 16)
         n = C.c_ulonglong(0)
         ws = None if own_workspace else self._ws
@@ -427,16 +379,10 @@ class Rasterizer:
             if not own_workspace:
                 self._ws = ws
             self._cap = cap
-            tail = (p(viewmats), p(Ks), V, width, height, p(rgb), p(depth), p(alpha), None if radii is None else p(radii), p(ws), ws.numel(), cap,
-                    C.byref(n), stream)
-            if opts is not None:
-                st = L.wm_rasterize_splats_opt(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, int(cin.shape[1]) if sh_degree else 0,
-                                               sh_degree, p(campos) if sh_degree else None, N, tail[0], tail[1], V, width, height,
-                                               C.byref(opts.struct(backgrounds)), *tail[5:])
-            elif sh_degree:
-                st = L.wm_rasterize_splats_sh(p(means), p(quats), p(scales), p(opacities), p(cin), int(cin.shape[1]), sh_degree, p(campos), N, *tail)
-            else:
-                st = L.wm_rasterize_splats(p(means), p(quats), p(scales), p(opacities), p(cin), is_sh, N, *tail)
+            st = L.wm_rasterize_splats_opt(ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(cin), is_sh, int(cin.shape[1]) if sh_degree else 0,
+                                           sh_degree, ptr(campos) if sh_degree else None, N, ptr(viewmats), ptr(Ks), V, width, height,
+                                           C.byref(opts.struct(backgrounds)), ptr(rgb), ptr(depth), ptr(alpha), ptr(radii), ptr(ws), ws.numel(), cap,
+                                           C.byref(n), stream(dev))
             if st == 0:
                 break
             if st == 3 and n.value > cap:   # WM_ERR_STATE: more (Gaussian, tile) pairs than the workspace holds
@@ -446,7 +392,8 @@ class Rasterizer:
         else:
             raise RuntimeError("wm_rasterize_splats: workspace re-size did not converge")
         self.last_n_isects = int(n.value)
-        return rgb, depth, alpha, (means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, int(n.value), int(sh_degree), campos, opts, backgrounds)
+        return rgb, depth, alpha, _State(means, quats, scales, opacities, cin, viewmats, Ks, ws, cap, int(n.value), int(sh_degree), campos, opts,
+                                         backgrounds)
 
     # rasterization.py:68-93 (NB: the reference passes what it calls `viewmats` on as `camtoworlds`)
     def rasterize_batches(self, means, quats, scales, opacities, colors, viewmats, Ks, width, height, **kwargs):

@@ -15,17 +15,10 @@ from typing import Any, Dict, Optional, Tuple
 import torch
 
 from . import _lib
+from ._lib import check, ptr, stream
 
 KEEP, DUP, SPLIT0, SPLIT1 = 0, 1, 2, 3
 GATHER_MODES = {"copy": 0, "zero_new": 1, "means": 2, "scales": 3, "opacities_revised": 4}
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _check(t, dtype, name):
@@ -46,10 +39,9 @@ def densify_accumulate(grads: torch.Tensor, radii: torch.Tensor, width: int, hei
         raise ValueError("shapes: grads / radii [C,N,2], grad2d / count / radii_state [N]")
     if N == 0:
         return
-    st = _lib.lib().wm_densify_accumulate(_p(grads), _p(radii), N, V, int(width), int(height), _p(grad2d), _p(count), _p(radii_state),
-                                          _stream(grads.device))
-    if st != 0:
-        raise RuntimeError(f"wm_densify_accumulate failed with status {st}")
+    st = _lib.lib().wm_densify_accumulate(ptr(grads), ptr(radii), N, V, int(width), int(height), ptr(grad2d), ptr(count), ptr(radii_state),
+                                          stream(grads.device))
+    check(st, "wm_densify_accumulate")
 
 
 def densify_plan(grad2d, count, radii_state, scales, opacities, *, grow_grad2d, grow_scale3d, grow_scale2d, prune_opa, prune_scale3d,
@@ -70,11 +62,10 @@ def densify_plan(grad2d, count, radii_state, scales, opacities, *, grow_grad2d, 
     rows = torch.empty((3, 3 * N), device=dev, dtype=torch.int32)
     ws = torch.empty(L.wm_densify_plan_workspace_bytes(N), device=dev, dtype=torch.uint8)
     counts = (C.c_int * 4)()
-    st = L.wm_densify_plan(_p(grad2d), _p(count), _p(radii_state), _p(sc), _p(op), N, grow_grad2d, grow_scale3d, grow_scale2d, prune_opa,
-                           prune_scale3d, prune_scale2d, int(use_scale2d), int(prune_big), int(revised_opacity), _p(rows[0]), _p(rows[1]),
-                           _p(rows[2]), C.byref(counts), _p(ws), ws.numel(), _stream(dev))
-    if st != 0:
-        raise RuntimeError(f"wm_densify_plan failed with status {st}")
+    st = L.wm_densify_plan(ptr(grad2d), ptr(count), ptr(radii_state), ptr(sc), ptr(op), N, grow_grad2d, grow_scale3d, grow_scale2d, prune_opa,
+                           prune_scale3d, prune_scale2d, int(use_scale2d), int(prune_big), int(revised_opacity), ptr(rows[0]), ptr(rows[1]),
+                           ptr(rows[2]), C.byref(counts), ptr(ws), ws.numel(), stream(dev))
+    check(st, "wm_densify_plan")
     n_dupli, n_split, n_prune, n_out = (int(x) for x in counts)
     return {"src": rows[0, :n_out], "kind": rows[1, :n_out], "rank": rows[2, :n_out], "n_dupli": n_dupli, "n_split": n_split,
             "n_prune": n_prune, "n_out": n_out, "n_in": N}
@@ -97,10 +88,9 @@ def densify_gather(t: torch.Tensor, plan: Dict[str, Any], mode: str = "copy", qu
             raise ValueError("noise: [2, N, 3]")
     else:
         quats = scales = noise = None
-    st = _lib.lib().wm_densify_gather(_p(x), _p(out), N, R, GATHER_MODES[mode], _p(plan["src"]), _p(plan["kind"]), _p(plan["rank"]), n_out,
-                                      _p(quats), _p(scales), _p(noise), _stream(x.device))
-    if st != 0:
-        raise RuntimeError(f"wm_densify_gather({mode}) failed with status {st}")
+    st = _lib.lib().wm_densify_gather(ptr(x), ptr(out), N, R, GATHER_MODES[mode], ptr(plan["src"]), ptr(plan["kind"]), ptr(plan["rank"]), n_out,
+                                      ptr(quats), ptr(scales), ptr(noise), stream(x.device))
+    check(st, f"wm_densify_gather({mode})")
     return out
 
 

@@ -19,14 +19,10 @@ from typing import Any, Dict, Optional
 import torch
 
 from . import _lib
-from .strategy import _check, _p, _stream
+from ._lib import check, ptr, stream
+from .strategy import _check
 
 MAX_MULTINOMIAL = 2 ** 24       # torch.multinomial's limit on the number of categories (ops.py:30)
-
-
-def _status(st: int, name: str) -> None:
-    if st != 0:
-        raise RuntimeError(f"{name} failed with status {st}")
 
 
 def _idx(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -46,8 +42,8 @@ def mcmc_inject_noise(means, quats, scales, opacities, noise, scaler: float) -> 
         raise ValueError("opacities: [N] or [N,1]")
     if N == 0:
         return
-    _status(_lib.lib().wm_mcmc_inject_noise(_p(means), _p(quats), _p(scales), _p(opacities), _p(noise), float(scaler), N, _stream(means.device)),
-            "wm_mcmc_inject_noise")
+    check(_lib.lib().wm_mcmc_inject_noise(ptr(means), ptr(quats), ptr(scales), ptr(opacities), ptr(noise), float(scaler), N, stream(means.device)),
+          "wm_mcmc_inject_noise")
 
 
 def mcmc_partition(opacities: torch.Tensor, min_opacity: float, mask: Optional[torch.Tensor] = None):
@@ -66,8 +62,8 @@ def mcmc_partition(opacities: torch.Tensor, min_opacity: float, mask: Optional[t
     L = _lib.lib()
     ws = torch.empty(L.wm_mcmc_partition_workspace_bytes(N), device=dev, dtype=torch.uint8)
     counts = (C.c_int * 2)()
-    _status(L.wm_mcmc_partition(_p(op), _p(mask), N, float(min_opacity), _p(rows[0]), _p(rows[1]), C.byref(counts), _p(ws), ws.numel(),
-                                _stream(dev)), "wm_mcmc_partition")
+    check(L.wm_mcmc_partition(ptr(op), ptr(mask), N, float(min_opacity), ptr(rows[0]), ptr(rows[1]), C.byref(counts), ptr(ws), ws.numel(),
+                              stream(dev)), "wm_mcmc_partition")
     return rows[0, :int(counts[0])], rows[1, :int(counts[1])]
 
 
@@ -83,8 +79,8 @@ def mcmc_relocation(opacities: torch.Tensor, scales: torch.Tensor, sampled: torc
     new_op, new_sc = torch.empty(n, device=dev), torch.empty((n, 3), device=dev)
     hist = torch.zeros(N, device=dev, dtype=torch.int32)
     if n:
-        _status(_lib.lib().wm_mcmc_relocation(_p(op), _p(sc), _p(sampled), n, N, float(min_opacity), _p(new_op), _p(new_sc), _p(hist), _stream(dev)),
-                "wm_mcmc_relocation")
+        check(_lib.lib().wm_mcmc_relocation(ptr(op), ptr(sc), ptr(sampled), n, N, float(min_opacity), ptr(new_op), ptr(new_sc), ptr(hist), stream(dev)),
+              "wm_mcmc_relocation")
     return (new_op, new_sc, hist) if return_counts else (new_op, new_sc)
 
 
@@ -101,7 +97,7 @@ def mcmc_scatter(t: torch.Tensor, sampled: torch.Tensor, dest: torch.Tensor, val
         _check(values, torch.float32, "values")
         if values.numel() != n * R:
             raise ValueError("values: one row per drawn index")
-    _status(_lib.lib().wm_mcmc_scatter(_p(t), rows, R, _p(sampled), _p(dest), _p(values), n, _stream(t.device)), "wm_mcmc_scatter")
+    check(_lib.lib().wm_mcmc_scatter(ptr(t), rows, R, ptr(sampled), ptr(dest), ptr(values), n, stream(t.device)), "wm_mcmc_scatter")
 
 
 def mcmc_zero_rows(t: torch.Tensor, idx: torch.Tensor) -> None:
@@ -110,7 +106,7 @@ def mcmc_zero_rows(t: torch.Tensor, idx: torch.Tensor) -> None:
     if idx.numel() == 0:
         return
     rows = int(t.shape[0])
-    _status(_lib.lib().wm_mcmc_zero_rows(_p(t), rows, t.numel() // rows, _p(idx), idx.numel(), _stream(t.device)), "wm_mcmc_zero_rows")
+    check(_lib.lib().wm_mcmc_zero_rows(ptr(t), rows, t.numel() // rows, ptr(idx), idx.numel(), stream(t.device)), "wm_mcmc_zero_rows")
 
 
 def _multinomial_sample(probs: torch.Tensor, n: int, generator: Optional[torch.Generator]) -> torch.Tensor:
