@@ -89,6 +89,8 @@ def lib() -> C.CDLL:
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
     L = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
+    # restype is set only where it is not ctypes' default c_int (wm_status / int); tests/test_cabi_cpu.py holds every entry's
+    # argtypes and restype against its prototype in include/wm_hip.h
     L.wm_create.argtypes = [C.POINTER(wm_config), i32, C.POINTER(vp)]
     L.wm_destroy.argtypes = [vp]
     L.wm_destroy.restype = None
@@ -134,148 +136,105 @@ def lib() -> C.CDLL:
     L.wm_host_to_16.argtypes = [vp, vp, C.c_size_t, i32]
     L.wm_host_to_16.restype = None
     L.wm_depth_to_world.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]
-    L.wm_depth_to_world.restype = i32
     L.wm_confidence_mask_workspace_bytes.argtypes = [C.c_size_t]
     L.wm_confidence_mask_workspace_bytes.restype = C.c_size_t
     L.wm_confidence_mask.argtypes = [vp, C.c_size_t, f32, vp, vp, C.c_size_t, vp]
-    L.wm_confidence_mask.restype = i32
     L.wm_depth_edge.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, vp]
-    L.wm_depth_edge.restype = i32
     L.wm_normals_edge.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, vp, vp]
-    L.wm_normals_edge.restype = i32
     L.wm_point_filter_mask_workspace_bytes.argtypes = [i32, i32, i32]
     L.wm_point_filter_mask_workspace_bytes.restype = C.c_size_t
     L.wm_point_filter_mask.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.c_double, i32, C.c_double, f32, vp, vp, vp, C.c_size_t, vp]
-    L.wm_point_filter_mask.restype = i32
     L.wm_op_up_conv_n32.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]
-    L.wm_op_up_conv_n32.restype = i32
     L.wm_op_conv3x3_gemm16.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-    L.wm_op_conv3x3_gemm16.restype = i32
+    L.wm_op_conv3x3_up.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.wm_op_conv_ex.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    L.wm_op_conv_ex.restype = i32
     L.wm_op_upconv3x3_tap.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.wm_op_upconv3x3_tap.restype = i32
     L.wm_op_tconv.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
-    L.wm_op_tconv.restype = i32
     L.wm_op_upconv_gather.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    L.wm_op_upconv_gather.restype = i32
     L.wm_prune_gs_workspace_bytes.argtypes = [C.c_size_t]
     L.wm_prune_gs_workspace_bytes.restype = C.c_size_t
     L.wm_prune_gs.argtypes = [vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, C.POINTER(i32), vp, C.c_size_t, vp]
-    L.wm_prune_gs.restype = i32
     L.wm_rasterize_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_size_t]
     L.wm_rasterize_workspace_bytes.restype = C.c_size_t
     L.wm_rasterize_splats.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t,
                                       C.POINTER(C.c_ulonglong), vp]
-    L.wm_rasterize_splats.restype = i32
     L.wm_rasterize_backward_workspace_bytes.argtypes = [i32, i32, i32, i32, C.c_size_t]
     L.wm_rasterize_backward_workspace_bytes.restype = C.c_size_t
     L.wm_rasterize_splats_backward.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    L.wm_rasterize_splats_backward.restype = i32
     L.wm_rasterize_backward_workspace_bytes_ex.argtypes = [i32, i32, i32, i32, C.c_size_t, i32]
     L.wm_rasterize_backward_workspace_bytes_ex.restype = C.c_size_t
     L.wm_rasterize_splats_backward_ex.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, C.c_size_t, vp]
-    L.wm_rasterize_splats_backward_ex.restype = i32
     L.wm_rasterize_backward_workspace_bytes_cam.argtypes = [i32, i32, i32, i32, C.c_size_t, i32]
     L.wm_rasterize_backward_workspace_bytes_cam.restype = C.c_size_t
     L.wm_rasterize_splats_backward_cam.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, C.c_size_t, vp]
-    L.wm_rasterize_splats_backward_cam.restype = i32
     L.wm_rasterize_splats_sh.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t,
                                          C.POINTER(C.c_ulonglong), vp]
-    L.wm_rasterize_splats_sh.restype = i32
     L.wm_rasterize_backward_workspace_bytes_sh.argtypes = [i32, i32, i32, i32, C.c_size_t, i32, i32, i32]
     L.wm_rasterize_backward_workspace_bytes_sh.restype = C.c_size_t
     L.wm_rasterize_splats_backward_sh.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, C.c_size_t, C.c_size_t, C.c_size_t,
                                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_size_t, vp]
-    L.wm_rasterize_splats_backward_sh.restype = i32
     optp = C.POINTER(wm_raster_options)
     L.wm_rasterize_splats_opt.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, optp, vp, vp, vp, vp, vp, C.c_size_t,
                                           C.c_size_t, C.POINTER(C.c_ulonglong), vp]
-    L.wm_rasterize_splats_opt.restype = i32
     L.wm_rasterize_backward_workspace_bytes_opt.argtypes = [i32, i32, i32, i32, C.c_size_t, i32, i32, i32, i32, i32]
     L.wm_rasterize_backward_workspace_bytes_opt.restype = C.c_size_t
     L.wm_rasterize_splats_backward_opt.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, optp, vp, C.c_size_t, C.c_size_t,
                                                    C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.c_size_t, vp]
-    L.wm_rasterize_splats_backward_opt.restype = i32
     L.wm_rasterize_means2d.argtypes = [vp, C.c_size_t, i32, i32, i32, i32, C.c_size_t, vp, vp, vp]
-    L.wm_rasterize_means2d.restype = i32
     L.wm_densify_accumulate.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.wm_densify_accumulate.restype = i32
     L.wm_densify_plan_workspace_bytes.argtypes = [C.c_size_t]
     L.wm_densify_plan_workspace_bytes.restype = C.c_size_t
     L.wm_densify_plan.argtypes = [vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, f32, i32, i32, i32, vp, vp, vp, C.POINTER(i32 * 4), vp,
                                   C.c_size_t, vp]
-    L.wm_densify_plan.restype = i32
     L.wm_densify_gather.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.wm_densify_gather.restype = i32
     L.wm_mcmc_inject_noise.argtypes = [vp, vp, vp, vp, vp, f32, i32, vp]
-    L.wm_mcmc_inject_noise.restype = i32
     L.wm_mcmc_partition_workspace_bytes.argtypes = [C.c_size_t]
     L.wm_mcmc_partition_workspace_bytes.restype = C.c_size_t
     L.wm_mcmc_partition.argtypes = [vp, vp, i32, f32, vp, vp, C.POINTER(i32 * 2), vp, C.c_size_t, vp]
-    L.wm_mcmc_partition.restype = i32
     L.wm_mcmc_relocation.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp]
-    L.wm_mcmc_relocation.restype = i32
     L.wm_mcmc_scatter.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
-    L.wm_mcmc_scatter.restype = i32
     L.wm_mcmc_zero_rows.argtypes = [vp, i32, i32, vp, i32, vp]
-    L.wm_mcmc_zero_rows.restype = i32
     i64p = C.POINTER(C.c_int64)
     L.wm_photometric_loss_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.wm_photometric_loss_workspace_bytes.restype = C.c_size_t
     L.wm_photometric_loss_forward_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.wm_photometric_loss_forward_workspace_bytes.restype = C.c_size_t
     L.wm_photometric_loss.argtypes = [vp, i64p, vp, i64p, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]
-    L.wm_photometric_loss.restype = i32
     L.wm_photometric_loss_backward.argtypes = [vp, i64p, vp, i64p, i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
-    L.wm_photometric_loss_backward.restype = i32
     L.wm_bilagrid_slice.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp]
-    L.wm_bilagrid_slice.restype = i32
     L.wm_bilagrid_slice_backward_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
     L.wm_bilagrid_slice_backward_workspace_bytes.restype = C.c_size_t
     L.wm_bilagrid_slice_backward.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
-    L.wm_bilagrid_slice_backward.restype = i32
     L.wm_bilagrid_tv_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
     L.wm_bilagrid_tv_workspace_bytes.restype = C.c_size_t
     L.wm_bilagrid_tv.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]
-    L.wm_bilagrid_tv.restype = i32
     L.wm_bilagrid_tv_backward.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    L.wm_bilagrid_tv_backward.restype = i32
     L.wm_depth_loss_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
     L.wm_depth_loss_workspace_bytes.restype = C.c_size_t
     L.wm_depth_loss.argtypes = [vp, i64p, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, C.c_size_t, vp]
-    L.wm_depth_loss.restype = i32
     L.wm_depth_loss_backward.argtypes = [i32, i32, i32, vp, i32, vp, vp, i64p, vp, C.c_size_t, vp]
-    L.wm_depth_loss_backward.restype = i32
     L.wm_project_depth_points.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    L.wm_project_depth_points.restype = i32
     i64 = C.c_int64
     L.wm_export_splats_workspace_bytes.argtypes = [i64, i32, i32]
     L.wm_export_splats_workspace_bytes.restype = C.c_size_t
     L.wm_export_splats_payload_bytes.argtypes = [i64, i32, i32]
     L.wm_export_splats_payload_bytes.restype = C.c_size_t
     L.wm_export_splats.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(i32), vp]
-    L.wm_export_splats.restype = i32
     L.wm_pack_rows_workspace_bytes.argtypes = [i64]
     L.wm_pack_rows_workspace_bytes.restype = C.c_size_t
     L.wm_pack_rows.argtypes = [C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, vp, i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(i32), vp]
-    L.wm_pack_rows.restype = i32
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
-    L.wm_appearance_forward.restype = i32
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
     L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t
     L.wm_appearance_backward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                          C.c_size_t, vp]
-    L.wm_appearance_backward.restype = i32
     L.wm_preprocess_image_size.argtypes = [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
-    L.wm_preprocess_image_size.restype = i32
     L.wm_preprocess_image_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.wm_preprocess_image_workspace_bytes.restype = C.c_size_t
     L.wm_preprocess_image.argtypes = [vp, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]
-    L.wm_preprocess_image.restype = i32
     L.wm_op_im2col.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.wm_op_im2col7.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp]
     L.wm_op_dino_tokens.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -297,7 +256,6 @@ def lib() -> C.CDLL:
     L.wm_op_dpt_tap_front.argtypes = [i32, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, i32, i32,
                                       C.POINTER(vp), C.POINTER(i32), vp]
     L.wm_set_tuning.argtypes = [C.c_char_p, i32]
-    L.wm_set_tuning.restype = i32
     _lib = L
     return L
 

@@ -4,7 +4,7 @@
 // The resize is Pillow's 8-bit resample (libImaging/Resample.c, the call at inference_utils.py:86): two separable
 // passes, horizontal first with a uint8 intermediate, per-output-pixel windows of normalised Keys-bicubic weights
 // quantised to 22 fractional bits.  The integer weight tables are built on the host in double precision exactly as
-// Pillow builds them (wm_model.cpp: wm_resample_coeffs); the kernels only do integer multiply-adds, so the result is
+// Pillow builds them (wm_api_scene.cpp: wm_resample_coeffs); the kernels only do integer multiply-adds, so the result is
 // bit-identical to Pillow's.  HBM-bound byte work: one thread per output pixel, 3 channels each.
 #include "wm_common.h"
 #include "wm_kernels.h"

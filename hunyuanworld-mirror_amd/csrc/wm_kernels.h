@@ -1,4 +1,5 @@
-// Internal launcher interface between the host orchestrator (wm_model.cpp) and the HIP kernels.
+// Internal launcher interface between the host side (the orchestrator wm_model.cpp, the entry files wm_api_ops.cpp and wm_api_scene.cpp)
+// and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -467,6 +468,6 @@ hipError_t wm_launch_prune_gs(const float* means, const float* quats, const floa
 #define WM_TUNE_ENUM(name_, key_) WM_TUNE_##name_,
 enum { WM_TUNE_KEYS(WM_TUNE_ENUM) WM_TUNE_COUNT };
 #undef WM_TUNE_ENUM
-extern int wm_tuning[WM_TUNE_COUNT];   // defined beside wm_set_tuning (wm_model.cpp)
+extern int wm_tuning[WM_TUNE_COUNT];   // one definition, beside wm_set_tuning in wm_model.cpp; the launchers and wm_api_ops.cpp read it too
 inline int wm_tune(int key, int dflt) { return wm_tuning[key] < 0 ? dflt : wm_tuning[key]; }
 

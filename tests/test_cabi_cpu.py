@@ -31,6 +31,58 @@ def test_exports_match_header(L):
         assert hasattr(L, n), n
 
 
+_C_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "wm_status": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t,
+              "int64_t": C.c_int64, "unsigned long long": C.c_ulonglong}
+
+
+def _ctype_matches(decl, ctype):
+    """Does the ctypes class `ctype` pass what the C declaration `decl` (a parameter with its name, or a return type) takes?"""
+    if "*" in decl or "[" in decl:
+        if ctype is C.c_char_p:
+            return re.match(r"const\s+char\s*\*", decl) is not None
+        return ctype is C.c_void_p or (isinstance(ctype, type) and issubclass(ctype, C._Pointer))
+    return ctype is _C_SCALARS[decl]      # an unknown scalar type is a KeyError: teach the table, do not skip
+
+
+def test_ctypes_table_matches_header_prototypes(L):
+    """Every prototype of include/wm_hip.h against the argtypes / restype that _lib.lib() declares: the same number of arguments, a
+    pointer where the header has one (`*` or `[]`), the same scalar type elsewhere, and the same return class (ctypes' default c_int
+    where restype is unset).  An entry without argtypes fails, and so does a prototype the pattern below cannot read."""
+    raw = open(os.path.join(ROOT, "include", "wm_hip.h")).read()
+    names = set(re.findall(r"\b(wm_[a-z0-9_]+)\s*\(", raw)) - {"wm_status"}       # as test_exports_match_header finds them
+    hdr = re.sub(r"/\*.*?\*/", " ", raw, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    hdr = re.sub(r"^\s*#[^\n]*", " ", hdr, flags=re.M)
+    protos = {m.group(2): (m.group(1), m.group(3)) for m in re.finditer(r"([^;{}()]*?)\b(wm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)}
+    assert set(protos) == names, set(protos) ^ names
+    from hunyuanworld_mirror_amd import _lib
+    lib = _lib.lib()
+    bad = []
+    for name, (ret, args) in sorted(protos.items()):
+        fn = getattr(lib, name)
+        params = [" ".join(a.split()) for a in args.split(",")]
+        params = [] if params == ["void"] else params
+        if fn.argtypes is None:
+            bad.append(f"{name}: no argtypes")
+            continue
+        if len(fn.argtypes) != len(params):
+            bad.append(f"{name}: {len(fn.argtypes)} argtypes, {len(params)} parameters")
+            continue
+        for i, (p, t) in enumerate(zip(params, fn.argtypes)):
+            # a scalar parameter is `[const] type name`: drop the qualifier and the name
+            decl = p if ("*" in p or "[" in p) else " ".join(w for w in p.split()[:-1] if w != "const")
+            if not _ctype_matches(decl, t):
+                bad.append(f"{name}: argument {i} `{p}` declared as {t.__name__}")
+        ret = " ".join(w for w in ret.split() if w != "extern")
+        if ret == "void":
+            ok = fn.restype is None
+        else:
+            ok = fn.restype is not None and _ctype_matches(ret, fn.restype)
+        if not ok:
+            bad.append(f"{name}: returns `{ret}`, restype {getattr(fn.restype, '__name__', fn.restype)}")
+    assert not bad, "\n".join(bad)
+
+
 def test_shipped_library_reads_no_wm_environment_switch(L):
     """The product build must not be steerable from the environment (a WM_ATTN_DEBUG_SKIP in the shipped library could
     return wrong results).  The environment layer that every historical WM_* switch went through is gone from the sources — neither its
