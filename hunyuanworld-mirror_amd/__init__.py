@@ -12,3 +12,4 @@ from .strategy import DefaultStrategy  # noqa: F401
 from .strategy_mcmc import MCMCStrategy  # noqa: F401
 from .pose import CameraOptModule  # noqa: F401
 from .exporter import export_splats, load_gaussian_ply, process_ply_to_splat, save_gs_ply, splats_from_ply  # noqa: F401
+from .colmap import colmap_points_from_depth, load_colmap, save_colmap, save_points_ply, save_scene_ply  # noqa: F401

@@ -74,6 +74,8 @@ EXPORTS = [
     "wm_appearance_forward", "wm_appearance_backward_workspace_bytes", "wm_appearance_backward",
     "wm_depth_loss_workspace_bytes", "wm_depth_loss", "wm_depth_loss_backward", "wm_project_depth_points",
     "wm_export_splats_workspace_bytes", "wm_export_splats_payload_bytes", "wm_export_splats", "wm_pack_rows_workspace_bytes", "wm_pack_rows",
+    "wm_colmap_select_workspace_bytes", "wm_colmap_select", "wm_colmap_gather", "wm_colmap_pack_workspace_bytes", "wm_colmap_pack",
+    "wm_pack_point_ply_workspace_bytes", "wm_pack_point_ply",
 ]
 
 _lib = None
@@ -226,6 +228,17 @@ def lib() -> C.CDLL:
     L.wm_pack_rows_workspace_bytes.argtypes = [i64]
     L.wm_pack_rows_workspace_bytes.restype = C.c_size_t
     L.wm_pack_rows.argtypes = [C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, vp, i64, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(i32), vp]
+    f64 = C.c_double
+    L.wm_colmap_select_workspace_bytes.argtypes = [i32, i32, i32]
+    L.wm_colmap_select_workspace_bytes.restype = C.c_size_t
+    L.wm_colmap_select.argtypes = [vp, vp, i32, i32, i32, f32, f64, vp, C.c_size_t, i64p, i64p, vp]
+    L.wm_colmap_gather.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, f64, f64, vp, C.c_size_t, i64, vp, vp, vp, vp]
+    L.wm_colmap_pack_workspace_bytes.argtypes = [i64, i32]
+    L.wm_colmap_pack_workspace_bytes.restype = C.c_size_t
+    L.wm_colmap_pack.argtypes = [vp, vp, vp, vp, i32, i64, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
+    L.wm_pack_point_ply_workspace_bytes.argtypes = [i64]
+    L.wm_pack_point_ply_workspace_bytes.restype = C.c_size_t
+    L.wm_pack_point_ply.argtypes = [vp, vp, vp, i32, i64, vp, C.c_size_t, vp, C.c_size_t, i64p, vp]
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
     L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t

@@ -6,3 +6,21 @@
 // For entries whose launcher checks sizes itself and answers hipErrorInvalidValue: that is the caller's mistake, not a HIP failure.
 // Entries that report every launcher error as WM_ERR_HIP write `== hipSuccess ? WM_OK : WM_ERR_HIP` out and do not come through here.
 static inline wm_status wm_status_of(hipError_t e) { return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP; }
+
+// ------------------------------------------------------------------ COLMAP hand-off (colmap.hip), entries in wm_api_scene.cpp
+// select: candidates (depth > eps) of [S,H,W], the top K confidences among them; leaves its state in the workspace, synchronises the stream once and
+// writes *n_kept and counts[S] (host).  gather: reads that state and writes the kept points in candidate order.  Sizes: S H W < 2^31.
+size_t wm_colmap_select_ws_bytes(int S, int H, int W);      // 0 for sizes the launchers refuse
+hipError_t wm_launch_colmap_select(const float* depth, const float* conf, int S, int H, int W, float eps, double percent, void* workspace,
+                                   long long* n_kept, long long* counts, hipStream_t s);
+hipError_t wm_launch_colmap_gather(const float* depth, const float* conf, const float* images, const float* c2w, const float* intr, int S, int H, int W,
+                                   float eps, double scale_x, double scale_y, const void* workspace, long long n_kept, float* points,
+                                   unsigned char* colors, int* xyf, hipStream_t s);
+// the per-point bodies of points3D.bin (59 P bytes) and images.bin (24 P bytes); either may be null; counts [S] int64 on the device
+size_t wm_colmap_pack_ws_bytes(long long P, int S);
+hipError_t wm_launch_colmap_pack(const float* points, const unsigned char* colors, const int* xyf, const long long* counts, int S, long long P,
+                                 void* workspace, void* points3d, void* points2d, hipStream_t s);
+// 15-byte rows (3 f32, 3 u8) of the rows with keep != 0, or with finite coordinates (filter_finite), or of every row; synchronises only to count
+size_t wm_point_ply_ws_bytes(long long N);
+hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors, const unsigned char* keep, int filter_finite, long long N,
+                               void* workspace, void* out, long long* n_kept, hipStream_t s);

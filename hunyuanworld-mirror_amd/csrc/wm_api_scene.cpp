@@ -548,3 +548,48 @@ extern "C" wm_status wm_depth_to_world(const float* depth, const float* extrinsi
   if (!depth || !extrinsic || !intrinsic || B < 0 || H < 0 || W < 0) return WM_ERR_INVALID;
   return wm_launch_depth_to_world(depth, extrinsic, intrinsic, world, cam, mask, B, H, W, eps, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
 }
+
+// ---------------------------------------------------------------- COLMAP hand-off (colmap.hip)
+extern "C" size_t wm_colmap_select_workspace_bytes(int S, int H, int W) { return wm_colmap_select_ws_bytes(S, H, W); }
+// replaces infer.py:296-324 (the per-view unprojection mask, the boolean indexing, the concatenation and the global confidence top-k)
+extern "C" wm_status wm_colmap_select(const float* depth, const float* conf, int S, int H, int W, float eps, double conf_threshold_percent,
+                                      void* workspace, size_t workspace_bytes, int64_t* n_kept, int64_t* counts, void* stream) {
+  const size_t need = wm_colmap_select_ws_bytes(S, H, W);
+  if (!depth || !conf || !workspace || !n_kept || !counts || need == 0 || workspace_bytes < need) return WM_ERR_INVALID;
+  static_assert(sizeof(long long) == sizeof(int64_t), "int64_t is long long here");
+  return wm_status_of(wm_launch_colmap_select(depth, conf, S, H, W, eps, conf_threshold_percent, workspace, (long long*)n_kept, (long long*)counts,
+                                              (hipStream_t)stream));
+}
+// replaces infer.py:303-313, 329-335 (the kept rows of the world points, the colours and the pixel grid, and the rescaling of x and y)
+extern "C" wm_status wm_colmap_gather(const float* depth, const float* conf, const float* images, const float* camtoworlds, const float* intrinsics,
+                                      int S, int H, int W, float eps, double scale_x, double scale_y, const void* workspace, size_t workspace_bytes,
+                                      int64_t n_kept, float* points, unsigned char* colors, int32_t* xyf, void* stream) {
+  const size_t need = wm_colmap_select_ws_bytes(S, H, W);
+  if (!depth || !conf || !images || !camtoworlds || !intrinsics || !workspace || need == 0 || workspace_bytes < need) return WM_ERR_INVALID;
+  if (n_kept < 0 || (n_kept > 0 && (!points || !colors || !xyf))) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_colmap_gather(depth, conf, images, camtoworlds, intrinsics, S, H, W, eps, scale_x, scale_y, workspace, n_kept, points,
+                                              colors, xyf, (hipStream_t)stream));
+}
+extern "C" size_t wm_colmap_pack_workspace_bytes(int64_t P, int S) { return wm_colmap_pack_ws_bytes(P, S); }
+// replaces src/utils/build_pycolmap_recon.py:36-51, 76-77 (add_point3D, Point2D and track.add_element per point) and the per-point part of
+// pycolmap's Reconstruction.write (infer.py:356)
+extern "C" wm_status wm_colmap_pack(const float* points, const unsigned char* colors, const int32_t* xyf, const int64_t* counts, int S, int64_t P,
+                                    void* workspace, size_t workspace_bytes, void* points3d, size_t points3d_bytes, void* points2d,
+                                    size_t points2d_bytes, void* stream) {
+  const size_t need = wm_colmap_pack_ws_bytes(P, S);
+  if (need == 0 || !workspace || workspace_bytes < need) return WM_ERR_INVALID;
+  if (P > 0 && ((points3d && (!points || !colors || !counts)) || (points2d && !xyf))) return WM_ERR_INVALID;
+  if ((points3d && points3d_bytes < (size_t)P * 59) || (points2d && points2d_bytes < (size_t)P * 24)) return WM_ERR_INVALID;
+  if (((size_t)points3d & 3) || ((size_t)points2d & 7)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_colmap_pack(points, colors, xyf, (const long long*)counts, S, P, workspace, points3d, points2d, (hipStream_t)stream));
+}
+extern "C" size_t wm_pack_point_ply_workspace_bytes(int64_t N) { return wm_point_ply_ws_bytes(N); }
+// replaces src/utils/save_utils.py:86-111 and :119-127 (the finite filter or the mask, and the structured array of x y z red green blue)
+extern "C" wm_status wm_pack_point_ply(const float* points, const unsigned char* colors, const unsigned char* keep, int filter_finite, int64_t N,
+                                       void* workspace, size_t workspace_bytes, void* out, size_t out_bytes, int64_t* n_kept, void* stream) {
+  const size_t need = wm_point_ply_ws_bytes(N);
+  if (need == 0 || !workspace || workspace_bytes < need || !n_kept) return WM_ERR_INVALID;
+  if (N > 0 && (!points || !colors || !out)) return WM_ERR_INVALID;
+  if (out_bytes < (size_t)N * 15 || ((size_t)out & 3)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_point_ply(points, colors, keep, filter_finite, N, workspace, out, (long long*)n_kept, (hipStream_t)stream));
+}

@@ -801,6 +801,45 @@ wm_status wm_pack_rows(const float* const* col_ptrs, const int* col_strides, con
                        const unsigned char* keep, int64_t N, void* workspace, size_t workspace_bytes, float* out, size_t out_bytes,
                        int* n_kept, void* stream);
 
+/* ---- COLMAP hand-off (csrc/colmap.hip): the sparse model the post-3DGS trainer starts from, infer.py:269-358 with
+ * src/utils/build_pycolmap_recon.py, and the coloured point clouds of src/utils/save_utils.py:81-130.
+ * selection (infer.py:296-335).  depth, conf [S,H,W] and images [S,3,H,W] contiguous fp32 on the device, camtoworlds [S,4,4] (the inverse
+ *   of the stored world-to-camera pose) and intrinsics [S,3,3] at H x W.  A pixel is a candidate when depth > eps (the mask of
+ *   wm_depth_to_world); the candidates are ordered view-major, row-major inside a view.  Of the N_valid candidates the
+ *   K = max(1, ceil(N_valid (100 - p) / 100)) highest confidences are kept (p <= 0: all; the arithmetic in double), conf <= 1e-5 counting
+ *   as -inf and ties at the K-th value going to the lowest candidate index (the rules of wm_confidence_mask).  The kept candidates keep their
+ *   order: positions come from prefix sums, never from atomics, and do not depend on block scheduling.
+ *   The select entry leaves its state in the workspace, synchronises the stream ONCE and writes *n_kept and counts[S] (host: kept points in all
+ *   and per view; N_valid = 0 gives zeros).  The gather entry, given the same arguments and the untouched workspace, writes points [n_kept,3]
+ *   fp32 (the expressions of wm_depth_to_world), colors [n_kept,3] u8 = trunc(clamp(image, 0, 1) 255) (the reference does not clamp; NaN
+ *   gives 0) and xyf [n_kept,3] int32 = (trunc(x scale_x), trunc(y scale_y), view), the products in double as numpy takes them.
+ *   workspace: the _workspace_bytes value for (S, H, W): about 12 bytes per 512 pixels; 0 for S, H or W < 1 or S H W >= 2^31.
+ * packing (build_pycolmap_recon.py:36-51, 76-77 and the per-point part of pycolmap's write).  points [P,3] fp32, colors [P,3] u8, xyf [P,3]
+ *   int32, counts [S] int64 on the device, the points view-major with counts[i] of view i.  points3d receives 59 bytes per point: u64 id =
+ *   index + 1, 3 x f64 xyz, 3 x u8 rgb, f64 error = -1, u64 track length = 1, u32 image_id = view + 1, u32 point2D_idx = index - (points
+ *   of earlier views).  points2d receives 24 bytes per point: f64 x, f64 y, u64 point3D_id.  Little-endian, no padding; either buffer may
+ *   be NULL.  points3d must be 4-byte and points2d 8-byte aligned.  The caller owns the headers and the per-image headers that go between
+ *   the views' runs of points2d.  No synchronisation.  workspace: the _workspace_bytes value for (P, S); 0 for P < 0, P >= 2^31, S < 1.
+ * point-cloud PLY rows (save_utils.py:86-111, 119-127): 15 bytes per kept row, 3 x f32 xyz and 3 x u8 rgb, of the rows with keep[i] != 0
+ *   (keep: N bytes on the device), or, with keep NULL and filter_finite != 0, of the rows whose three coordinates are finite, or of every
+ *   row; input order.  *n_kept (host) is written before the call returns; the call synchronises once when it filters and not otherwise.
+ *   out: 4-byte aligned, out_bytes >= 15 N.  workspace: the _workspace_bytes value for N (about 4 bytes per row); 0 for N < 0, N >= 2^31.
+ * WM_ERR_INVALID, before anything is launched: a null pointer where none is allowed, sizes the size calls refuse, a too small workspace or
+ *   output buffer, a misaligned output. */
+size_t wm_colmap_select_workspace_bytes(int S, int H, int W);
+wm_status wm_colmap_select(const float* depth, const float* conf, int S, int H, int W, float eps, double conf_threshold_percent,
+                           void* workspace, size_t workspace_bytes, int64_t* n_kept, int64_t* counts, void* stream);
+wm_status wm_colmap_gather(const float* depth, const float* conf, const float* images, const float* camtoworlds, const float* intrinsics,
+                           int S, int H, int W, float eps, double scale_x, double scale_y, const void* workspace, size_t workspace_bytes,
+                           int64_t n_kept, float* points, unsigned char* colors, int32_t* xyf, void* stream);
+size_t wm_colmap_pack_workspace_bytes(int64_t P, int S);
+wm_status wm_colmap_pack(const float* points, const unsigned char* colors, const int32_t* xyf, const int64_t* counts, int S, int64_t P,
+                         void* workspace, size_t workspace_bytes, void* points3d, size_t points3d_bytes, void* points2d,
+                         size_t points2d_bytes, void* stream);
+size_t wm_pack_point_ply_workspace_bytes(int64_t N);
+wm_status wm_pack_point_ply(const float* points, const unsigned char* colors, const unsigned char* keep, int filter_finite, int64_t N,
+                            void* workspace, size_t workspace_bytes, void* out, size_t out_bytes, int64_t* n_kept, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
