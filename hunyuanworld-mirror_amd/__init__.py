@@ -13,3 +13,4 @@ from .strategy_mcmc import MCMCStrategy  # noqa: F401
 from .pose import CameraOptModule  # noqa: F401
 from .exporter import export_splats, load_gaussian_ply, process_ply_to_splat, save_gs_ply, splats_from_ply  # noqa: F401
 from .colmap import colmap_points_from_depth, load_colmap, save_colmap, save_points_ply, save_scene_ply  # noqa: F401
+from .splat_init import create_splats_with_optimizers, knn, knn_scales, rgb_to_sh  # noqa: F401

@@ -76,6 +76,7 @@ EXPORTS = [
     "wm_export_splats_workspace_bytes", "wm_export_splats_payload_bytes", "wm_export_splats", "wm_pack_rows_workspace_bytes", "wm_pack_rows",
     "wm_colmap_select_workspace_bytes", "wm_colmap_select", "wm_colmap_gather", "wm_colmap_pack_workspace_bytes", "wm_colmap_pack",
     "wm_pack_point_ply_workspace_bytes", "wm_pack_point_ply",
+    "wm_knn_workspace_bytes", "wm_knn",
 ]
 
 _lib = None
@@ -239,6 +240,9 @@ def lib() -> C.CDLL:
     L.wm_pack_point_ply_workspace_bytes.argtypes = [i64]
     L.wm_pack_point_ply_workspace_bytes.restype = C.c_size_t
     L.wm_pack_point_ply.argtypes = [vp, vp, vp, i32, i64, vp, C.c_size_t, vp, C.c_size_t, i64p, vp]
+    L.wm_knn_workspace_bytes.argtypes = [i64, i32]
+    L.wm_knn_workspace_bytes.restype = C.c_size_t
+    L.wm_knn.argtypes = [vp, i64, i32, vp, C.c_size_t, vp, vp, vp, vp]
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
     L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t

@@ -24,3 +24,10 @@ hipError_t wm_launch_colmap_pack(const float* points, const unsigned char* color
 size_t wm_point_ply_ws_bytes(long long N);
 hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors, const unsigned char* keep, int filter_finite, long long N,
                                void* workspace, void* out, long long* n_kept, hipStream_t s);
+
+// ------------------------------------------------------------------ k nearest neighbours (knn.hip), entries in wm_api_scene.cpp
+// dist [N,K] (ascending, the point itself included) and, when idx is not null, the rows idx [N,K] of the K nearest points of points [N,3] within
+// the cloud itself; exact.  *nonfinite_flag (device) is written 0, or 1 for a NaN / infinite coordinate, and then nothing else is written.
+// No synchronisation.  1 <= K <= 16, K <= N < 2^31.
+size_t wm_knn_ws_bytes(long long N, int K);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspace, float* dist, int* idx, int* nonfinite_flag, hipStream_t s);

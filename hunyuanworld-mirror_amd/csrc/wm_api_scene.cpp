@@ -1,7 +1,7 @@
 // Scene-level entries of the C ABI (include/wm_hip.h): the caller's steps on either side of the forward, each with its *_workspace_bytes.
 // In file order: splat pruning, the rasteriser, densification, MCMC, the photometric loss, the bilateral grid, the appearance module, the
-// depth loss and point projection, then image ingest and the point masks.  Each entry checks its arguments, fills its launcher's args
-// struct, launches on the caller's stream and maps the hipError_t.
+// depth loss and point projection, then image ingest and the point masks, the COLMAP hand-off and the nearest neighbours.  Each entry
+// checks its arguments, fills its launcher's args struct, launches on the caller's stream and maps the hipError_t.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -592,4 +592,15 @@ extern "C" wm_status wm_pack_point_ply(const float* points, const unsigned char*
   if (N > 0 && (!points || !colors || !out)) return WM_ERR_INVALID;
   if (out_bytes < (size_t)N * 15 || ((size_t)out & 3)) return WM_ERR_INVALID;
   return wm_status_of(wm_launch_point_ply(points, colors, keep, filter_finite, N, workspace, out, (long long*)n_kept, (hipStream_t)stream));
+}
+
+// ---------------------------------------------------------------- k nearest neighbours (knn.hip)
+extern "C" size_t wm_knn_workspace_bytes(int64_t N, int K) { return wm_knn_ws_bytes(N, K); }
+// replaces submodules/gsplat/examples/utils.py:141-145 (knn: the copy to the host and scikit-learn's kd-tree) as
+// simple_trainer_worldmirror.py:334-337 calls it
+extern "C" wm_status wm_knn(const float* points, int64_t N, int K, void* workspace, size_t workspace_bytes, float* dist, int32_t* idx,
+                            int32_t* nonfinite_flag, void* stream) {
+  const size_t need = wm_knn_ws_bytes(N, K);
+  if (need == 0 || !points || !workspace || workspace_bytes < need || !dist || !nonfinite_flag) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_knn(points, N, K, workspace, dist, idx, nonfinite_flag, (hipStream_t)stream));
 }

@@ -840,6 +840,25 @@ size_t wm_pack_point_ply_workspace_bytes(int64_t N);
 wm_status wm_pack_point_ply(const float* points, const unsigned char* colors, const unsigned char* keep, int filter_finite, int64_t N,
                             void* workspace, size_t workspace_bytes, void* out, size_t out_bytes, int64_t* n_kept, void* stream);
 
+/* ---- k nearest neighbours of a cloud within itself (csrc/knn.hip): the reference's knn, submodules/gsplat/examples/utils.py:141-145 (a copy
+ * to the host and scikit-learn's kd-tree), as the trainer's splat initialisation calls it, simple_trainer_worldmirror.py:334-337
+ * (scales = log(sqrt(mean(knn(points, 4)[:, 1:]^2)) init_scale)).
+ * points [N,3] contiguous fp32 on the device.  dist [N,K] fp32: row i holds the K smallest values of |x_i - x_j| over ALL j, ascending, the
+ * point itself included (column 0 is 0, as scikit-learn's kneighbors(X) on the fitted set), each computed in fp32 in difference form,
+ * sqrt(dx dx + dy dy + dz dz) with dx = x_i - x_j and no fused multiply-add; duplicates give exact zeros.  idx [N,K] int32 (may be NULL): the
+ * rows j, ties ordered by row (a tie at the K-th place, or a row full of zeros, may keep any of the tied rows).  Rows are in input order.
+ * Exact: the Morton-sorted cell structure only prunes, and every comparison that ends a search is conservative in fp32.  The same input
+ * gives the same bits.  *nonfinite_flag (one int on the device, written by the call): 0, or 1 when a coordinate is NaN or infinite, and
+ * then dist and idx are not written; the caller reads it (the only synchronisation the operation needs).  The call itself does not
+ * synchronise and runs no host loop that depends on the data.
+ * Worst case: a pass of a query costs the points of its 3 x 3 x 3 cells.  A dense part smaller than 2^-21 of the bounding box is one cell
+ * and is scanned by each of its queries; a far outlier scans up to the whole cloud.  Both stay exact.
+ * workspace: the _workspace_bytes value for (N, K): 44 bytes per point + the sort's scratch; 0 for sizes the call refuses.
+ * WM_ERR_INVALID, before anything is launched: K < 1, K > 16, K > N, N >= 2^31, a null pointer other than idx, a too small workspace. */
+size_t wm_knn_workspace_bytes(int64_t N, int K);
+wm_status wm_knn(const float* points, int64_t N, int K, void* workspace, size_t workspace_bytes, float* dist, int32_t* idx,
+                 int32_t* nonfinite_flag, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
