@@ -141,7 +141,7 @@ def lib() -> C.CDLL:
     L.wm_depth_to_world.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]
     L.wm_confidence_mask_workspace_bytes.argtypes = [C.c_size_t]
     L.wm_confidence_mask_workspace_bytes.restype = C.c_size_t
-    L.wm_confidence_mask.argtypes = [vp, C.c_size_t, f32, vp, vp, C.c_size_t, vp]
+    L.wm_confidence_mask.argtypes = [vp, C.c_size_t, C.c_double, vp, vp, C.c_size_t, vp]
     L.wm_depth_edge.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, vp]
     L.wm_normals_edge.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, vp, vp]
     L.wm_point_filter_mask_workspace_bytes.argtypes = [i32, i32, i32]

@@ -64,11 +64,12 @@ CmWs cm_carve(char* base, int S, int H, int W) {
   return w;
 }
 
-// select.hip's key: conf <= 1e-5 -> -inf, then the order-preserving image of the float
+// select.hip's key (conf_key, kept identical): any NaN -> the one top key, conf <= 1e-5 -> -inf, then the order-preserving image of the float
 __device__ __forceinline__ unsigned int cm_key(float c) {
+  if (c != c) return 0xFFFFFFFFu;  // any NaN, either sign, any payload: the one top key, above +inf like torch.topk's NaN-largest
   const float v = c <= 1e-5f ? -INFINITY : c;
   const unsigned int u = __builtin_bit_cast(unsigned int, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone: larger float <=> larger key
 }
 
 // ordered rank of the lanes of a 256-thread block whose flag is set, and the number set; every lane calls it

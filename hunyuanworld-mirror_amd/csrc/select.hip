@@ -2,6 +2,7 @@
 // predicted confidences right after the path).
 //
 //   conf' = conf <= 1e-5 ? -inf : conf;   K = p > 0 ? max(1, ceil(N (100 - p) / 100)) : N;   mask = top-K of conf'
+// with torch.topk's order: a NaN of either sign ranks above +inf, and all NaNs are one value (they tie).
 //
 // HBM-bound integer work: a 4 x 8-bit radix SELECT on the order-preserving uint32 image of conf' finds the K-th
 // largest key exactly (per pass: per-block LDS histogram -> integer atomics -> one small block walks the 256 bins from
@@ -23,7 +24,8 @@ struct SelState {
 };
 
 __device__ __forceinline__ unsigned int conf_key(float c) {
-  const float v = c <= 1e-5f ? -INFINITY : c;  // NaN compares false -> kept as is: sorts above +inf like torch.topk's NaN-largest
+  if (c != c) return 0xFFFFFFFFu;  // any NaN, either sign, any payload: the one top key, above +inf like torch.topk's NaN-largest
+  const float v = c <= 1e-5f ? -INFINITY : c;
   const unsigned int u = __builtin_bit_cast(unsigned int, v);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone: larger float <=> larger key
 }

@@ -509,13 +509,14 @@ extern "C" wm_status wm_preprocess_image(const unsigned char* rgb, int H, int W,
 }
 
 extern "C" size_t wm_confidence_mask_workspace_bytes(size_t n) { return wm_confidence_mask_workspace(n); }
-extern "C" wm_status wm_confidence_mask(const float* conf, size_t n, float conf_threshold_percent, unsigned char* mask, void* workspace,
+extern "C" wm_status wm_confidence_mask(const float* conf, size_t n, double conf_threshold_percent, unsigned char* mask, void* workspace,
                                         size_t workspace_bytes, void* stream) {
   if (!conf || !mask || !workspace || workspace_bytes < wm_confidence_mask_workspace(n)) return WM_ERR_INVALID;
   if (n == 0) return WM_OK;
-  // infer.py:44-48: keep the top ceil(N (100 - p) / 100), at least one; p <= 0 keeps everything
+  // infer.py:44-48: keep the top ceil(N (100 - p) / 100), at least one; p <= 0 keeps everything.  p is the caller's Python float and
+  // the arithmetic is the reference's, in double: an fp32 image of p (33.3f > 33.3) moves K by one at n = 1000
   double keep = (double)n;
-  if (conf_threshold_percent > 0.f) keep = std::ceil((double)n * (100.0 - (double)conf_threshold_percent) / 100.0);
+  if (conf_threshold_percent > 0.0) keep = std::ceil((double)n * (100.0 - conf_threshold_percent) / 100.0);
   size_t K = keep < 1.0 ? 1 : (size_t)keep;
   if (K > n) K = n;
   return wm_launch_confidence_mask(conf, n, (unsigned int)K, mask, workspace, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;

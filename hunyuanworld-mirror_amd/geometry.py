@@ -46,7 +46,7 @@ def create_confidence_mask(confidence: torch.Tensor, conf_threshold_percent: flo
     L = _lib.lib()
     wsb = L.wm_confidence_mask_workspace_bytes(n)
     ws = torch.empty(wsb, device=c.device, dtype=torch.uint8)
-    if L.wm_confidence_mask(ptr(c), n, C.c_float(conf_threshold_percent), ptr(mask), ptr(ws), wsb, stream(c.device)) != 0:
+    if L.wm_confidence_mask(ptr(c), n, C.c_double(conf_threshold_percent), ptr(mask), ptr(ws), wsb, stream(c.device)) != 0:
         raise RuntimeError("wm_confidence_mask failed")
     return mask.bool()
 

@@ -277,11 +277,13 @@ wm_status wm_preprocess_image(const unsigned char* rgb, int H, int W, int mode, 
                               size_t workspace_bytes, void* stream);
 
 /* create_confidence_mask (infer.py:25-59): mask[i] = 1 for the top ceil(n (100 - p) / 100) (at least 1; p <= 0: all)
- * confidences after conf <= 1e-5 -> -inf; exact radix select on the device, ties at the threshold value broken by
- * lowest index (the reference's torch.topk leaves them unspecified).  workspace: wm_confidence_mask_workspace_bytes(n)
- * bytes of device memory.  n < 2^32. */
+ * confidences after conf <= 1e-5 -> -inf; the count is taken in double from the double p, as the reference takes it from its Python
+ * float.  A NaN of either sign ranks above +inf (torch.topk's order); all NaNs tie.  Exact radix select on the device, ties at the
+ * threshold value broken by lowest index (the reference's torch.topk leaves them unspecified).  workspace:
+ * wm_confidence_mask_workspace_bytes(n) bytes of device memory.  n < 2^32.  A NULL conf, mask or workspace, or a workspace smaller
+ * than that, returns WM_ERR_INVALID before anything is launched. */
 size_t wm_confidence_mask_workspace_bytes(size_t n);
-wm_status wm_confidence_mask(const float* conf, size_t n, float conf_threshold_percent, unsigned char* mask, void* workspace,
+wm_status wm_confidence_mask(const float* conf, size_t n, double conf_threshold_percent, unsigned char* mask, void* workspace,
                              size_t workspace_bytes, void* stream);
 
 /* Point-cloud filter masks: the per-view mask app.py:172-206 (run_model) builds for every export.

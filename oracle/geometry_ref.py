@@ -25,15 +25,22 @@ def depth_to_world_coords_points(depth_map, extrinsic, intrinsic, eps=1e-8):
     return world.astype(np.float32), cam, point_mask
 
 
-def create_confidence_mask(confidence, conf_threshold_percent=30.0):
-    """infer.py:25-59 restated in numpy.  Ties at the K-th value: lowest flat index first (stable sort) — the reference's
-    torch.topk leaves that choice unspecified, so fixtures are tie-free at the threshold."""
-    c = np.asarray(confidence, np.float32).reshape(-1).copy()
-    c[c <= 1e-5] = -np.inf                                   # :40
-    n = c.size
+def confidence_mask_count(n, conf_threshold_percent):
+    """infer.py:44-50: the kept count K, in Python floats (fp64) like the reference."""
     k = int(np.ceil(n * (100.0 - conf_threshold_percent) / 100.0)) if conf_threshold_percent > 0 else n   # :44-48
-    k = max(1, k)                                            # :49
-    order = np.argsort(-c, kind="stable")                    # top-k, lowest index first among equals (:52)
+    return max(1, k)                                         # :50
+
+
+def create_confidence_mask(confidence, conf_threshold_percent=30.0):
+    """infer.py:25-59 restated in numpy.  torch.topk's order: a NaN of either sign and any payload is the largest value,
+    above +inf, and all NaNs are equal.  Ties at the K-th value: lowest flat index first (stable sort) — the reference's
+    torch.topk leaves that choice unspecified, so fixtures pinned to it are tie-free at the threshold."""
+    c = np.asarray(confidence, np.float32).reshape(-1).copy()
+    c[c <= np.float32(1e-5)] = -np.inf                       # :40 (torch compares in the tensor's fp32; NaN compares false)
+    n = c.size
+    k = confidence_mask_count(n, conf_threshold_percent)
+    nan = np.isnan(c)
+    order = np.lexsort((np.where(nan, np.float32(0), -c), ~nan))   # NaNs first, then descending; lexsort is stable: lowest index first among equals (:52)
     mask = np.zeros(n, bool)
     mask[order[:k]] = True                                   # :55-56
     return mask

@@ -52,8 +52,10 @@ def _restate_selection(depth, conf, percent):
     cc = torch.where(cc <= 1e-5, torch.full_like(cc, float("-inf")), cc)
     n = len(cand)
     K = max(1, int(np.ceil(n * (100.0 - percent) / 100.0))) if percent > 0 else n
-    order = torch.sort(cc, descending=True, stable=True).indices[:K]          # stable: equal values in candidate order
-    return torch.sort(cand[order]).values.numpy()
+    v = cc.numpy()
+    nan = np.isnan(v)                                                         # torch.topk's order: a NaN of either sign is the largest value
+    order = np.lexsort((np.where(nan, np.float32(0), -v), ~nan))[:K]          # NaNs, then descending; stable: equal values in candidate order
+    return torch.sort(cand[torch.from_numpy(order)]).values.numpy()
 
 
 def _scene(S, H, W, seed, n_valid=None):
@@ -186,6 +188,30 @@ def test_ties_go_to_the_lowest_index():
     assert pts.shape[0] == int(np.ceil(n_valid * 70.0 / 100.0)) == len(keep)
     got = xyf.cpu().numpy().astype(np.int64)
     assert np.array_equal(got[:, 2] * H * W + got[:, 1] * W + got[:, 0], keep)
+
+
+def test_sign_bit_nan_confidence_is_kept_first():
+    """torch.topk ranks a NaN of either sign above +inf.  0xFFC00000, the NaN a host's 0/0 gives, on a valid-depth pixel in the middle of
+    the second view: the only point kept at K = 1, and among the kept at 30 %; a +inf elsewhere does not displace it."""
+    S, H, W = 3, 37, 53
+    z = _scene(S, H, W, seed=5)
+    flat_valid = z["depth"].reshape(-1) > 1e-8
+    at = int(np.nonzero(flat_valid)[0][np.searchsorted(np.nonzero(flat_valid)[0], H * W + 700)])
+    inf_at = int(np.nonzero(flat_valid)[0][10])
+    conf = z["conf"].copy().reshape(-1)
+    conf[at] = np.array([0xFFC00000], np.uint32).view(np.float32)[0]
+    conf[inf_at] = np.inf
+    assert np.isnan(conf[at]) and np.signbit(conf[at]) and flat_valid[at] and inf_at < at
+    conf = conf.reshape(S, H, W)
+    n_valid = int(flat_valid.sum())
+    for percent in (99.99, 30.0):
+        keep = _restate_selection(z["depth"], conf, percent)
+        K = max(1, int(np.ceil(n_valid * (100.0 - percent) / 100.0)))
+        assert len(keep) == K and at in keep
+        pts, cols, xyf, counts = _select(z, percent, (W, H), conf=conf)
+        got = xyf.cpu().numpy().astype(np.int64)
+        assert np.array_equal(got[:, 2] * H * W + got[:, 1] * W + got[:, 0], keep), percent
+    assert K > 1 and len(_restate_selection(z["depth"], conf, 99.99)) == 1          # the first percent kept the NaN alone, past the +inf
 
 
 def test_save_scene_ply_filters(tmp_path):
