@@ -88,7 +88,7 @@ static hipError_t build_up1comp(int dt, int F_, int Co, const float* woc1, const
 struct TapFold {
   void* w16[4] = {nullptr, nullptr, nullptr, nullptr};      // per tap [nh * oc_i][Kp] 16-bit
   float* bias[4] = {nullptr, nullptr, nullptr, nullptr};    // per tap [nh * oc_i]
-  std::vector<std::string> heads;                           // the group's head prefixes, in the order of their row blocks
+  int heads[4] = {0, 0, 0, 0}, nh = 0;                      // the group's heads (HeadId), in the order of their row blocks
   bool valid = false;                                       // false: no group, or a folded weight left the operand type's range (direct form)
 };
 static void free_tapfold(TapFold& t) {
@@ -102,6 +102,85 @@ static void free_tapfold(TapFold& t) {
 // allocated) when a folded weight or bias is not finite, or a weight exceeds the f16 maximum for f16 operands
 static hipError_t build_tapfold(int dt, int nh, int oc, int K, int Kp, const float* const* Wh, const float* const* bh, const float* const* gamma,
                                 const float* const* beta, void** w16_out, float** bias_out, bool* in_range);
+
+// ------------------------------------------------------------------ bound model
+// Everything the forward reads, as device pointers and the few ints taken from shapes: filled by bind_model() at the end of plan(), the one
+// point where both the weights and the shape are final (wm_set_weight / wm_share_weights / wm_set_workspace invalidate the plan).  The
+// forward addresses nothing by name.  A null pointer below is an operand the layer does not have, and is marked so.
+enum HeadId { HD_DEPTH = 0, HD_PTS, HD_NORM, HD_GS, HD_COUNT };   // the DPT heads in the order the forward runs them
+const char* const kHeadPrefix[HD_COUNT] = {"depth_head.", "pts_head.", "norm_head.", "gs_head."};
+inline bool head_enabled(const wm_config& c, int id) {
+  return id == HD_DEPTH ? c.enable_depth : id == HD_PTS ? c.enable_pts : id == HD_NORM ? c.enable_norm : c.enable_gs;
+}
+struct Lin16 { const void* w = nullptr; const float* b = nullptr; };                   // 16-bit matrix [N][Kpad] + fp32 bias
+struct Lin32 { const float* w = nullptr; const float* b = nullptr; int N = 0, K = 0; };   // fp32 Linear [N][K] + bias
+struct Norm { const float* w = nullptr; const float* b = nullptr; };
+struct ConvW { const void* w16 = nullptr; const float* bias = nullptr; int cin = 0, cout = 0; };   // bias null: the conv has none
+struct BlockW {            // one transformer block of the backbone (16-bit operands)
+  Norm norm1, norm2;
+  Lin16 qkv, proj, fc1, fc2;
+  Norm q_norm, k_norm;     // null in the DINO blocks (no q/k-norm)
+  const float *ls1 = nullptr, *ls2 = nullptr;
+};
+struct CamBlockW {         // one block of the camera head's trunk (fp32)
+  Norm norm1, norm2;
+  Lin32 qkv, proj, fc1, fc2;
+  const float *ls1 = nullptr, *ls2 = nullptr;
+};
+struct HeadW {             // one DPT head
+  Norm norm;
+  Lin16 proj[4];
+  Lin16 resize[2];         // ConvTranspose2d (kernel = stride) as a GEMM
+  ConvW resize3;
+  ConvW rn[4];             // layer{i+1}_rn (no bias)
+  ConvW rcu[4][2][2];      // [refinenet - 1][resConfUnit - 1][conv - 1]; refinenet4 has no unit 1
+  ConvW out_conv[4];       // Cin = Cout = the head's feature width (checked by bind_model)
+  ConvW oc1;               // output_conv1
+  const void* oc1_tap = nullptr;      // its tap-major copy [tap][Cout][Cin], null when the repack made none
+  const Up1Comp* comp = nullptr;      // refinenet1.out_conv composed into it, null when wm_reserve built none for this Cout
+  ConvW oc2_0;             // output_conv2.0
+  Lin32 oc2_2;             // output_conv2.2 (1x1, fp32)
+  Lin16 merger;            // input_merger.0 (Gaussian head only)
+  ConvW gs0, gs2;          // gs_renderer.gs_head.0 (no bias) / .2 (Gaussian head only)
+  const TconvPack* tconv[2] = {nullptr, nullptr};   // null: no composed form for this level
+};
+struct Model {
+  Lin16 patch_proj;
+  const float *cls_token = nullptr, *register_tokens = nullptr, *cam_token = nullptr, *reg_token = nullptr;
+  Norm dino_norm;
+  std::vector<BlockW> dino, frame, global;
+  Lin32 pose_embed[2], ray_embed[2];   // enable_cond only
+  Lin16 depth_fc1, depth_fc2;
+  Norm cam_token_norm, cam_out_norm;
+  Lin32 cam_param_embed, cam_adapt, cam_pred_fc1, cam_pred_fc2;
+  std::vector<CamBlockW> cam;
+  HeadW head[HD_COUNT];
+};
+struct HeadBufs {          // the workspace of one head SLOT (the k-th head a call runs, whichever head that is)
+  void *T16 = nullptr, *P16 = nullptr, *P16b = nullptr;   // P16b only with two or more slots
+  float *f0 = nullptr, *f1 = nullptr, *f2 = nullptr, *f3in = nullptr, *f3 = nullptr;
+  float* rn[4] = {nullptr, nullptr, nullptr, nullptr};
+  float* s[4] = {nullptr, nullptr, nullptr, nullptr};
+};
+struct Workspace {
+  float *Xd = nullptr, *Xv = nullptr;
+  uint16_t* A16 = nullptr;
+  char* QKV16 = nullptr;
+  void *O16 = nullptr, *H16 = nullptr;
+  float* tap[4] = {nullptr, nullptr, nullptr, nullptr};
+  char* KVG = nullptr;
+  float *ATT_PO = nullptr, *ATT_ML = nullptr, *LN_STATS = nullptr;
+  int *ATT_FLAGS = nullptr, *ATT_HINT = nullptr, *ATT_STAT = nullptr, *LN_SYNC = nullptr;
+  uint16_t* ZERO256 = nullptr;
+  float *rope_cos = nullptr, *rope_sin = nullptr, *dino_pos = nullptr;
+  float *pr_in = nullptr, *pr_h = nullptr, *pose_tok = nullptr, *ray_tok = nullptr;
+  float *cam_tok_local = nullptr, *cam_tok = nullptr, *cam_e = nullptr, *cam_mod = nullptr, *cam_h = nullptr, *cam_a = nullptr, *cam_qkv = nullptr;
+  float *cam_o = nullptr, *cam_f = nullptr, *cam_pred = nullptr, *cam_delta = nullptr, *cam_init = nullptr, *cam_params = nullptr;
+  HeadBufs hb[4];
+  void* gs_im2col = nullptr;            // enable_gs only
+  float* dpt_pos[4] = {nullptr, nullptr, nullptr, nullptr};
+  float *posx[2] = {nullptr, nullptr}, *posy[2] = {nullptr, nullptr};   // [0] the dense heads' width, [1] the Gaussian head's
+};
 
 struct EvPair { hipEvent_t a, b; };
 
@@ -133,13 +212,14 @@ struct wm_handle {
   size_t arena_bytes = 0;
   bool arena_owned = true;   // false: caller-provided (wm_set_workspace)
   int plan_n = -1, plan_nt = -1, plan_H = -1, plan_W = -1;
-  std::map<std::string, TconvPack> tconv;   // per head and level ("pts_head.0"): rebuilt by wm_reserve after a weight change
+  TconvPack tconv[HD_COUNT][2];             // per head and level: rebuilt by wm_reserve after a weight change
   bool tconv_valid = false;
-  std::map<std::string, Up1Comp> up1comp;   // per head ("pts_head."), rebuilt with the token-conv packs
+  Up1Comp up1comp[HD_COUNT];                // per head, rebuilt with the token-conv packs
   TapFold tapfold;                          // the heads' shared tap front, rebuilt with them
   std::vector<std::string> missing;  // names wm_finalize_weights filled with their init values
-  // shape-dependent device tables (allocated inside the arena by plan())
-  std::map<std::string, void*> buf;
+  // the weights and the workspace (with its shape-dependent device tables) as the forward reads them: bound by plan()
+  Model m;
+  Workspace ws;
   // the DPT heads are mutually independent: each runs on its own stream (forked/joined with events)
   hipStream_t hstream[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t hfork = nullptr, hjoin[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -300,17 +380,10 @@ std::vector<std::pair<std::string, std::vector<int64_t>>> param_spec(const wm_co
 }
 
 // ------------------------------------------------------------------ small accessors
+// (plan() and bind_model() only: the forward reads the bound model)
 const Weight* W(const wm_handle* h, const std::string& n) {
   auto it = h->w.find(n);
   return it == h->w.end() ? nullptr : &it->second;
-}
-const float* F(const wm_handle* h, const std::string& n) {
-  const Weight* w = W(h, n);
-  return w ? w->f32 : nullptr;
-}
-const void* W16(const wm_handle* h, const std::string& n) {
-  const Weight* w = W(h, n);
-  return w ? w->w16 : nullptr;
 }
 
 struct Dims {
@@ -421,8 +494,6 @@ std::vector<std::pair<std::string, size_t>> arena_layout(const wm_handle* h, con
   add("gs_posy", (size_t)d.H * (Fm / 4) * 4 * 2);
   return L;
 }
-
-template <class T> T* B(wm_handle* h, const char* n) { return (T*)h->buf.at(n); }
 
 // torch.linspace(start, end, steps, dtype=float32) (symmetric evaluation, as ATen does)
 void linspace_f32(float start, float end, int steps, std::vector<float>& out) {
@@ -546,8 +617,8 @@ extern "C" wm_status wm_create(const wm_config* cfg, int device, wm_handle** out
 extern "C" void wm_destroy(wm_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  for (auto& kv : h->tconv) free_tconv(kv.second);
-  for (auto& kv : h->up1comp) free_up1comp(kv.second);
+  for (auto& hd : h->tconv) for (TconvPack& t : hd) free_tconv(t);
+  for (Up1Comp& u : h->up1comp) free_up1comp(u);
   free_tapfold(h->tapfold);
   if (h->hfront) (void)hipEventDestroy(h->hfront);
   for (auto& kv : h->w) {
@@ -727,10 +798,169 @@ extern "C" size_t wm_workspace_bytes(const wm_handle* h, int n_local, int n_tota
 
 namespace {
 
-// Builds the workspace for a shape: arena (library-owned unless the caller gave one), buffer map and the shape- /
-// weight-derived device tables.  Called by wm_reserve only — never from the forward pass.
+// The one place where a tensor or a workspace buffer is addressed by name.  Every name goes through Binder: an absent name, or a tensor
+// without the form the forward needs (fp32 / 16-bit repack), is remembered (the first one) and fails wm_reserve with that name.
+struct Binder {
+  const wm_handle* h;
+  const std::map<std::string, char*>& buf;
+  std::string err;
+  void miss(const std::string& what) { if (err.empty()) err = what; }
+  const Weight* tensor(const std::string& n) {
+    const Weight* w = W(h, n);
+    if (!w) miss("no tensor " + n);
+    return w;
+  }
+  const float* f32(const std::string& n) {
+    const Weight* w = tensor(n);
+    if (w && !w->f32) miss(n + " has no fp32 form");
+    return w ? w->f32 : nullptr;
+  }
+  const void* w16(const std::string& n) {
+    const Weight* w = tensor(n);
+    if (w && !w->w16) miss(n + " has no 16-bit form");
+    return w ? w->w16 : nullptr;
+  }
+  Norm norm(const std::string& p) { return {f32(p + ".weight"), f32(p + ".bias")}; }
+  Lin16 lin16(const std::string& p) { return {w16(p + ".weight"), f32(p + ".bias")}; }
+  Lin32 lin32(const std::string& p) {   // N and K from the shape: [N][K...]
+    Lin32 l;
+    l.w = f32(p + ".weight"); l.b = f32(p + ".bias");
+    const Weight* w = tensor(p + ".weight");
+    if (w && !w->shape.empty()) {
+      l.N = (int)w->shape[0]; l.K = 1;
+      for (size_t i = 1; i < w->shape.size(); ++i) l.K *= (int)w->shape[i];
+    }
+    return l;
+  }
+  ConvW conv(const std::string& p, bool bias = true) {   // [Cout][Cin][k][k]
+    ConvW cv;
+    cv.w16 = w16(p + ".weight");
+    const Weight* w = tensor(p + ".weight");
+    if (w && w->shape.size() == 4) { cv.cout = (int)w->shape[0]; cv.cin = (int)w->shape[1]; }
+    else if (w) miss(p + ".weight is not a conv weight");
+    if (bias) cv.bias = f32(p + ".bias");
+    return cv;
+  }
+  template <class T> T* ws(const std::string& n) {
+    auto it = buf.find(n);
+    if (it == buf.end()) { miss("no workspace buffer " + n); return nullptr; }
+    return (T*)it->second;
+  }
+};
+
+// Fills h->m and h->ws from the finalized weights, the composed head weights (tconv / up1comp) and the arena's buffer map
+wm_status bind_model(wm_handle* h, const std::map<std::string, char*>& buf) {
+  const wm_config& c = h->cfg;
+  Binder b{h, buf, std::string()};
+  Model m;
+  Workspace w;
+  const std::string v = "visual_geometry_transformer.", dn = v + "patch_embed.", ch = "cam_head.";
+  auto block = [&](const std::string& p, bool qk_norm) {
+    BlockW k;
+    k.norm1 = b.norm(p + "norm1"); k.norm2 = b.norm(p + "norm2");
+    k.qkv = b.lin16(p + "attn.qkv"); k.proj = b.lin16(p + "attn.proj"); k.fc1 = b.lin16(p + "mlp.fc1"); k.fc2 = b.lin16(p + "mlp.fc2");
+    if (qk_norm) { k.q_norm = b.norm(p + "attn.q_norm"); k.k_norm = b.norm(p + "attn.k_norm"); }   // optional: the DINO blocks have no q/k-norm
+    k.ls1 = b.f32(p + "ls1.gamma"); k.ls2 = b.f32(p + "ls2.gamma");
+    return k;
+  };
+  m.patch_proj = b.lin16(dn + "patch_embed.proj");
+  m.cls_token = b.f32(dn + "cls_token"); m.register_tokens = b.f32(dn + "register_tokens");
+  m.cam_token = b.f32(v + "cam_token"); m.reg_token = b.f32(v + "reg_token");
+  m.dino_norm = b.norm(dn + "norm");
+  for (int i = 0; i < c.dino_depth; ++i) m.dino.push_back(block(dn + "blocks." + std::to_string(i) + ".", false));
+  for (int i = 0; i < c.depth; ++i) {
+    m.frame.push_back(block(v + "frame_blocks." + std::to_string(i) + ".", true));
+    m.global.push_back(block(v + "global_blocks." + std::to_string(i) + ".", true));
+  }
+  if (c.enable_cond) {
+    m.pose_embed[0] = b.lin32(v + "pose_embed.0"); m.pose_embed[1] = b.lin32(v + "pose_embed.2");
+    m.ray_embed[0] = b.lin32(v + "ray_embed.0"); m.ray_embed[1] = b.lin32(v + "ray_embed.2");
+    m.depth_fc1 = b.lin16(v + "depth_embed.proj.2.fc1"); m.depth_fc2 = b.lin16(v + "depth_embed.proj.2.fc2");
+  }
+  if (c.enable_cam) {
+    m.cam_token_norm = b.norm(ch + "token_norm"); m.cam_out_norm = b.norm(ch + "out_norm");
+    m.cam_param_embed = b.lin32(ch + "param_embed"); m.cam_adapt = b.lin32(ch + "adapt_norm_gen.1");
+    m.cam_pred_fc1 = b.lin32(ch + "param_predictor.fc1"); m.cam_pred_fc2 = b.lin32(ch + "param_predictor.fc2");
+    for (int i = 0; i < c.cam_trunk_depth; ++i) {
+      const std::string p = ch + "refine_net." + std::to_string(i) + ".";
+      CamBlockW k;
+      k.norm1 = b.norm(p + "norm1"); k.norm2 = b.norm(p + "norm2");
+      k.qkv = b.lin32(p + "attn.qkv"); k.proj = b.lin32(p + "attn.proj"); k.fc1 = b.lin32(p + "mlp.fc1"); k.fc2 = b.lin32(p + "mlp.fc2");
+      k.ls1 = b.f32(p + "ls1.gamma"); k.ls2 = b.f32(p + "ls2.gamma");
+      m.cam.push_back(k);
+    }
+  }
+  for (int id = 0; id < HD_COUNT; ++id) {
+    if (!head_enabled(c, id)) continue;
+    const std::string p = kHeadPrefix[id], sc = p + "scratch.";
+    const int F_ = id == HD_GS ? c.gs_dim : c.dpt_features;
+    HeadW& hw = m.head[id];
+    hw.norm = b.norm(p + "norm");
+    for (int i = 0; i < 4; ++i) hw.proj[i] = b.lin16(p + "projects." + std::to_string(i));
+    for (int i = 0; i < 2; ++i) hw.resize[i] = b.lin16(p + "resize_layers." + std::to_string(i));
+    hw.resize3 = b.conv(p + "resize_layers.3");
+    for (int i = 0; i < 4; ++i) hw.rn[i] = b.conv(sc + "layer" + std::to_string(i + 1) + "_rn", false);   // optional: Conv2d(bias=False)
+    for (int r = 1; r <= 4; ++r) {
+      const std::string q = sc + "refinenet" + std::to_string(r) + ".";
+      hw.out_conv[r - 1] = b.conv(q + "out_conv");
+      if (hw.out_conv[r - 1].cin != F_ || hw.out_conv[r - 1].cout != F_) b.miss(q + "out_conv.weight is not [F][F][1][1]");
+      for (int u = (r == 4 ? 2 : 1); u <= 2; ++u)
+        for (int cv = 1; cv <= 2; ++cv) hw.rcu[r - 1][u - 1][cv - 1] = b.conv(q + "resConfUnit" + std::to_string(u) + ".conv" + std::to_string(cv));
+    }
+    hw.oc1 = b.conv(sc + "output_conv1");
+    const Weight* w1 = b.tensor(sc + "output_conv1.weight");
+    if (w1 && w1->w16 && w1->tap_major) hw.oc1_tap = (const uint16_t*)w1->w16 + (size_t)hw.oc1.cout * 9 * hw.oc1.cin;   // optional: 3x3 weights only
+    const Up1Comp& u1 = h->up1comp[id];
+    hw.comp = u1.w16 && u1.co == hw.oc1.cout ? &u1 : nullptr;                            // optional: f16 heads of the dense kind only
+    hw.oc2_0 = b.conv(sc + "output_conv2.0");
+    hw.oc2_2 = b.lin32(sc + "output_conv2.2");
+    if (id == HD_GS) {
+      hw.merger = b.lin16(p + "input_merger.0");
+      hw.gs0 = b.conv("gs_renderer.gs_head.0", false);                                   // optional: Conv2d(bias=False)
+      hw.gs2 = b.conv("gs_renderer.gs_head.2");
+    }
+    for (int i = 0; i < 2; ++i) hw.tconv[i] = h->tconv[id][i].w16 ? &h->tconv[id][i] : nullptr;   // optional: 256-feature dense heads only
+  }
+
+  w.Xd = b.ws<float>("Xd"); w.Xv = b.ws<float>("Xv"); w.A16 = b.ws<uint16_t>("A16"); w.QKV16 = b.ws<char>("QKV16");
+  w.O16 = b.ws<void>("O16"); w.H16 = b.ws<void>("H16"); w.KVG = b.ws<char>("KVG");
+  for (int i = 0; i < 4; ++i) w.tap[i] = b.ws<float>("tap" + std::to_string(i));
+  w.ATT_PO = b.ws<float>("ATT_PO"); w.ATT_ML = b.ws<float>("ATT_ML"); w.ATT_FLAGS = b.ws<int>("ATT_FLAGS"); w.ATT_HINT = b.ws<int>("ATT_HINT");
+  w.ATT_STAT = b.ws<int>("ATT_STAT"); w.LN_STATS = b.ws<float>("LN_STATS"); w.LN_SYNC = b.ws<int>("LN_SYNC"); w.ZERO256 = b.ws<uint16_t>("ZERO256");
+  w.rope_cos = b.ws<float>("rope_cos"); w.rope_sin = b.ws<float>("rope_sin"); w.dino_pos = b.ws<float>("dino_pos");
+  w.pr_in = b.ws<float>("pr_in"); w.pr_h = b.ws<float>("pr_h"); w.pose_tok = b.ws<float>("pose_tok"); w.ray_tok = b.ws<float>("ray_tok");
+  w.cam_tok_local = b.ws<float>("cam_tok_local"); w.cam_tok = b.ws<float>("cam_tok"); w.cam_e = b.ws<float>("cam_e"); w.cam_mod = b.ws<float>("cam_mod");
+  w.cam_h = b.ws<float>("cam_h"); w.cam_a = b.ws<float>("cam_a"); w.cam_qkv = b.ws<float>("cam_qkv"); w.cam_o = b.ws<float>("cam_o");
+  w.cam_f = b.ws<float>("cam_f"); w.cam_pred = b.ws<float>("cam_pred"); w.cam_delta = b.ws<float>("cam_delta"); w.cam_init = b.ws<float>("cam_init");
+  w.cam_params = b.ws<float>("cam_params");
+  int nslots = 0;
+  for (int id = 0; id < HD_COUNT; ++id) nslots += head_enabled(c, id) ? 1 : 0;
+  for (int sl = 0; sl < std::max(nslots, 1); ++sl) {
+    const std::string x = "_h" + std::to_string(sl);
+    HeadBufs& q = w.hb[sl];
+    q.T16 = b.ws<void>("dpt_T16" + x); q.P16 = b.ws<void>("dpt_P16" + x);
+    if (nslots >= 2) q.P16b = b.ws<void>("dpt_P16b" + x);   // optional: laid out for the shared tap front only
+    q.f0 = b.ws<float>("dpt_f0" + x); q.f1 = b.ws<float>("dpt_f1" + x); q.f2 = b.ws<float>("dpt_f2" + x); q.f3in = b.ws<float>("dpt_f3in" + x);
+    q.f3 = b.ws<float>("dpt_f3" + x);
+    for (int i = 0; i < 4; ++i) {
+      q.rn[i] = b.ws<float>("dpt_rn" + std::to_string(i + 1) + x);
+      q.s[i] = b.ws<float>("dpt_s" + std::to_string(i) + x);
+    }
+  }
+  if (c.enable_gs) w.gs_im2col = b.ws<void>("gs_im2col");
+  for (int i = 0; i < 4; ++i) w.dpt_pos[i] = b.ws<float>("dpt_pos" + std::to_string(i));
+  w.posx[0] = b.ws<float>("dpt_posx"); w.posy[0] = b.ws<float>("dpt_posy"); w.posx[1] = b.ws<float>("gs_posx"); w.posy[1] = b.ws<float>("gs_posy");
+  if (!b.err.empty()) return fail(h, WM_ERR_STATE, "wm_reserve: " + b.err);
+  h->m = std::move(m);
+  h->ws = w;
+  return WM_OK;
+}
+
+// Builds the workspace for a shape: arena (library-owned unless the caller gave one), the composed head weights, the bound model
+// (bind_model) and the shape- / weight-derived device tables.  Called by wm_reserve only — never from the forward pass.
 wm_status plan(wm_handle* h, const Dims& d) {
   if (h->plan_n == d.n && h->plan_nt == d.nt && h->plan_H == d.H && h->plan_W == d.W) return WM_OK;
+  h->plan_n = -1;   // until this plan is complete the forward has nothing to run on
   const wm_config& c = h->cfg;
   auto L = arena_layout(h, d);
   size_t tot = 0;
@@ -745,9 +975,78 @@ wm_status plan(wm_handle* h, const Dims& d) {
     HIPCHK(h, hipMalloc((void**)&h->arena, tot));
     h->arena_bytes = tot;
   }
-  h->buf.clear();
+  std::map<std::string, char*> buf;
   size_t off = 0;
-  for (auto& kv : L) { h->buf[kv.first] = h->arena + off; off += kv.second; }
+  for (auto& kv : L) { buf[kv.first] = h->arena + off; off += kv.second; }
+
+  // the composed ConvTranspose -> layer_rn GEMMs of the DPT heads (weight-derived only: rebuilt after a weight change, not per shape)
+  if (!h->tconv_valid) {
+    for (auto& hd : h->tconv) for (TconvPack& t : hd) free_tconv(t);
+    for (Up1Comp& u : h->up1comp) free_up1comp(u);
+    if (c.dpt_features == 256)
+      for (int id = HD_DEPTH; id <= HD_NORM; ++id)
+        for (int i = 0; i < 2 && head_enabled(c, id); ++i) {
+          const std::string p = kHeadPrefix[id];
+          const Weight* wct = W(h, p + "resize_layers." + std::to_string(i) + ".weight");
+          const Weight* bct = W(h, p + "resize_layers." + std::to_string(i) + ".bias");
+          const Weight* wrn = W(h, p + "scratch.layer" + std::to_string(i + 1) + "_rn.weight");
+          const int k = i == 0 ? 4 : 2, oc = c.dpt_out_channels[i];
+          if (!wct || !bct || !wrn || wct->host.empty() || bct->host.empty() || wrn->host.empty() || oc % 64) continue;
+          if (wct->host.size() != (size_t)oc * oc * k * k || bct->host.size() != (size_t)oc || wrn->host.size() != (size_t)256 * oc * 9) continue;
+          HIPCHK(h, build_tconv(c.head_dtype, k, oc, oc, 256, wct->host.data(), bct->host.data(), wrn->host.data(), h->tconv[id][i], nullptr));
+        }
+    if (c.head_dtype == WM_DT_F16)
+      for (int id = HD_DEPTH; id <= HD_NORM; ++id) {
+        if (!head_enabled(c, id)) continue;
+        const std::string p = kHeadPrefix[id];
+        const Weight* w1 = W(h, p + "scratch.output_conv1.weight");
+        const Weight* wo = W(h, p + "scratch.refinenet1.out_conv.weight");
+        const Weight* bo = W(h, p + "scratch.refinenet1.out_conv.bias");
+        const int F_ = c.dpt_features;
+        if (!w1 || !wo || !bo || w1->host.empty() || wo->host.empty() || bo->host.empty() || F_ % 64 || w1->shape.size() != 4) continue;
+        const int Co = (int)w1->shape[0];
+        if ((Co != 128 && Co != 64 && Co != 32) || w1->host.size() != (size_t)Co * F_ * 9 || wo->host.size() != (size_t)F_ * F_ || bo->host.size() != (size_t)F_) continue;
+        HIPCHK(h, build_up1comp(c.head_dtype, F_, Co, w1->host.data(), wo->host.data(), bo->host.data(), h->up1comp[id], nullptr));
+      }
+    // the heads' shared tap front: every enabled DPT head reads the same four taps through a LayerNorm(2D) and 1x1 projections of the same widths
+    free_tapfold(h->tapfold);
+    {
+      TapFold tf;   // heads in the order the forward runs them (and numbers their workspace slots)
+      for (int id = 0; id < HD_COUNT; ++id)
+        if (head_enabled(c, id)) tf.heads[tf.nh++] = id;
+      const int D2 = 2 * d.D, Kp = ru(D2, 64);
+      bool ok = tf.nh >= 2;
+      std::vector<const float*> Wh, bh, gm, bt;
+      for (int i = 0; i < 4 && ok; ++i) {
+        const int oci = c.dpt_out_channels[i];
+        Wh.clear(); bh.clear(); gm.clear(); bt.clear();
+        for (int k = 0; k < tf.nh; ++k) {
+          const std::string p = kHeadPrefix[tf.heads[k]];
+          const Weight* w = W(h, p + "projects." + std::to_string(i) + ".weight");
+          const Weight* b = W(h, p + "projects." + std::to_string(i) + ".bias");
+          const Weight* g = W(h, p + "norm.weight");
+          const Weight* e = W(h, p + "norm.bias");
+          // (a head whose tensors are missing or of another size keeps the whole group on the direct form)
+          if (!w || !b || !g || !e || w->host.size() != (size_t)oci * D2 || b->host.size() != (size_t)oci || g->host.size() != (size_t)D2 ||
+              e->host.size() != (size_t)D2 || w->k16 != Kp || (oci & 3)) { ok = false; break; }
+          Wh.push_back(w->host.data()); bh.push_back(b->host.data()); gm.push_back(g->host.data()); bt.push_back(e->host.data());
+        }
+        if (!ok) break;
+        bool in_range = false;
+        HIPCHK(h, build_tapfold(c.head_dtype, tf.nh, oci, D2, Kp, Wh.data(), bh.data(), gm.data(), bt.data(), &tf.w16[i], &tf.bias[i], &in_range));
+        if (!in_range) ok = false;   // gamma now scales a weight: out of the operand type's range -> the direct form for this handle
+      }
+      if (ok) { tf.valid = true; h->tapfold = tf; }
+      else free_tapfold(tf);
+    }
+    h->tconv_valid = true;
+  }
+  // every weight and workspace buffer the forward reads, by name for the last time
+  {
+    const wm_status st = bind_model(h, buf);
+    if (st != WM_OK) return st;
+  }
+  const Workspace& ws = h->ws;
 
   // RoPE tables (rope.py:80-111): angle = pos * 100^(-i/16), i < 16 (table is cat(ang, ang): index e % 16)
   {
@@ -761,8 +1060,8 @@ wm_status plan(wm_handle* h, const Dims& d) {
         cs[(size_t)p * 16 + i] = std::cos(ang);
         sn[(size_t)p * 16 + i] = std::sin(ang);
       }
-    HIPCHK(h, hipMemcpy(h->buf["rope_cos"], cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->buf["rope_sin"], sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(ws.rope_cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(ws.rope_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
   }
   {  // fallback statistics: counters at 0, host mirror allocated once (pinned: the forward copies into it without synchronising)
     const int n = (c.dino_depth + 2 * c.depth) * 3;
@@ -775,23 +1074,23 @@ wm_status plan(wm_handle* h, const Dims& d) {
     memset(h->att_stat_host, 0, (size_t)n * 4);
     h->att_seen.assign(n, 0);
     h->att_general_ttl.assign(n, 0);
-    HIPCHK(h, hipMemset(h->buf["ATT_STAT"], 0, (size_t)n * 4));
+    HIPCHK(h, hipMemset(ws.ATT_STAT, 0, (size_t)n * 4));
   }
-  HIPCHK(h, hipMemset(h->buf["LN_SYNC"], 0, ((size_t)d.Mx / 16 + 2) * 3 * 4));
+  HIPCHK(h, hipMemset(ws.LN_SYNC, 0, ((size_t)d.Mx / 16 + 2) * 3 * 4));
   // the fast attention kernels' sticky fallback hints start empty for a new shape (they index launch blocks)
-  HIPCHK(h, hipMemset(h->buf["ATT_HINT"], 0, (size_t)(c.dino_depth + 2 * c.depth) * 3 * wm_attention_max_blocks((int)d.Mx, d.P < d.Td ? d.P : d.Td, d.heads) * 4));
+  HIPCHK(h, hipMemset(ws.ATT_HINT, 0, (size_t)(c.dino_depth + 2 * c.depth) * 3 * wm_attention_max_blocks((int)d.Mx, d.P < d.Td ? d.P : d.Td, d.heads) * 4));
   // DINO pos-embed for this grid (vision_transformer.py:175-207)
   {
     const Weight* pe = W(h, "visual_geometry_transformer.patch_embed.pos_embed");
     if (!pe || pe->host.empty()) return fail(h, WM_ERR_STATE, "pos_embed not set");
     const int g = c.img_size / c.patch_size, D = d.D;
     if (d.gh == g && d.gw == g) {
-      HIPCHK(h, hipMemcpy(h->buf["dino_pos"], pe->host.data(), (size_t)(1 + d.hw) * D * 4, hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(ws.dino_pos, pe->host.data(), (size_t)(1 + d.hw) * D * 4, hipMemcpyHostToDevice));
     } else {
       std::vector<float> r((size_t)(1 + d.hw) * D);
       memcpy(r.data(), pe->host.data(), (size_t)D * 4);
       wm_host_resample_pos(pe->host.data() + D, g, D, d.gh, d.gw, r.data() + D);
-      HIPCHK(h, hipMemcpy(h->buf["dino_pos"], r.data(), r.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(ws.dino_pos, r.data(), r.size() * 4, hipMemcpyHostToDevice));
     }
   }
   // DPT UV position tables (dense_head.py:253-263)
@@ -806,83 +1105,16 @@ wm_status plan(wm_handle* h, const Dims& d) {
         for (int x = 0; x < d.gw; ++x)
           for (int k = 0; k < C; ++k)
             full[((size_t)y * d.gw + x) * C + k] = k < C / 2 ? tx[(size_t)x * (C / 2) + k] : ty[(size_t)y * (C / 2) + k - C / 2];
-      HIPCHK(h, hipMemcpy(h->buf["dpt_pos" + std::to_string(i)], full.data(), full.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(ws.dpt_pos[i], full.data(), full.size() * 4, hipMemcpyHostToDevice));
     }
     uv_tables(d.W, d.H, c.dpt_features / 2, aspect, tx, ty);
-    HIPCHK(h, hipMemcpy(h->buf["dpt_posx"], tx.data(), tx.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(h->buf["dpt_posy"], ty.data(), ty.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(ws.posx[0], tx.data(), tx.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(ws.posy[0], ty.data(), ty.size() * 4, hipMemcpyHostToDevice));
     if (c.enable_gs) {
       uv_tables(d.W, d.H, c.gs_dim / 2, aspect, tx, ty);
-      HIPCHK(h, hipMemcpy(h->buf["gs_posx"], tx.data(), tx.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(h, hipMemcpy(h->buf["gs_posy"], ty.data(), ty.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(ws.posx[1], tx.data(), tx.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(h, hipMemcpy(ws.posy[1], ty.data(), ty.size() * 4, hipMemcpyHostToDevice));
     }
-  }
-  // the composed ConvTranspose -> layer_rn GEMMs of the DPT heads (weight-derived only: rebuilt after a weight change, not per shape)
-  if (!h->tconv_valid) {
-    for (auto& kv : h->tconv) free_tconv(kv.second);
-  for (auto& kv : h->up1comp) free_up1comp(kv.second);
-    h->tconv.clear();
-    std::vector<std::string> heads;
-    if (c.enable_pts) heads.push_back("pts_head.");
-    if (c.enable_depth) heads.push_back("depth_head.");
-    if (c.enable_norm) heads.push_back("norm_head.");
-    if (c.dpt_features == 256)
-      for (const std::string& p : heads)
-        for (int i = 0; i < 2; ++i) {
-          const Weight* wct = W(h, p + "resize_layers." + std::to_string(i) + ".weight");
-          const Weight* bct = W(h, p + "resize_layers." + std::to_string(i) + ".bias");
-          const Weight* wrn = W(h, p + "scratch.layer" + std::to_string(i + 1) + "_rn.weight");
-          const int k = i == 0 ? 4 : 2, oc = c.dpt_out_channels[i];
-          if (!wct || !bct || !wrn || wct->host.empty() || bct->host.empty() || wrn->host.empty() || oc % 64) continue;
-          if (wct->host.size() != (size_t)oc * oc * k * k || bct->host.size() != (size_t)oc || wrn->host.size() != (size_t)256 * oc * 9) continue;
-          HIPCHK(h, build_tconv(c.head_dtype, k, oc, oc, 256, wct->host.data(), bct->host.data(), wrn->host.data(), h->tconv[p + std::to_string(i)], nullptr));
-        }
-    h->up1comp.clear();
-    if (c.head_dtype == WM_DT_F16)
-      for (const std::string& p : heads) {
-        const Weight* w1 = W(h, p + "scratch.output_conv1.weight");
-        const Weight* wo = W(h, p + "scratch.refinenet1.out_conv.weight");
-        const Weight* bo = W(h, p + "scratch.refinenet1.out_conv.bias");
-        const int F_ = c.dpt_features;
-        if (!w1 || !wo || !bo || w1->host.empty() || wo->host.empty() || bo->host.empty() || F_ % 64 || w1->shape.size() != 4) continue;
-        const int Co = (int)w1->shape[0];
-        if ((Co != 128 && Co != 64 && Co != 32) || w1->host.size() != (size_t)Co * F_ * 9 || wo->host.size() != (size_t)F_ * F_ || bo->host.size() != (size_t)F_) continue;
-        HIPCHK(h, build_up1comp(c.head_dtype, F_, Co, w1->host.data(), wo->host.data(), bo->host.data(), h->up1comp[p], nullptr));
-      }
-    // the heads' shared tap front: every enabled DPT head reads the same four taps through a LayerNorm(2D) and 1x1 projections of the same widths
-    free_tapfold(h->tapfold);
-    {
-      std::vector<std::string> grp;   // in the order the forward runs them (and numbers their workspace slots)
-      if (c.enable_depth) grp.push_back("depth_head.");
-      if (c.enable_pts) grp.push_back("pts_head.");
-      if (c.enable_norm) grp.push_back("norm_head.");
-      if (c.enable_gs) grp.push_back("gs_head.");
-      const int D2 = 2 * d.D, Kp = ru(D2, 64);
-      bool ok = grp.size() >= 2 && grp.size() <= 4;
-      std::vector<const float*> Wh, bh, gm, bt;
-      TapFold tf;
-      for (int i = 0; i < 4 && ok; ++i) {
-        const int oci = c.dpt_out_channels[i];
-        Wh.clear(); bh.clear(); gm.clear(); bt.clear();
-        for (const std::string& p : grp) {
-          const Weight* w = W(h, p + "projects." + std::to_string(i) + ".weight");
-          const Weight* b = W(h, p + "projects." + std::to_string(i) + ".bias");
-          const Weight* g = W(h, p + "norm.weight");
-          const Weight* e = W(h, p + "norm.bias");
-          // (a head whose tensors are missing or of another size keeps the whole group on the direct form)
-          if (!w || !b || !g || !e || w->host.size() != (size_t)oci * D2 || b->host.size() != (size_t)oci || g->host.size() != (size_t)D2 ||
-              e->host.size() != (size_t)D2 || w->k16 != Kp || (oci & 3)) { ok = false; break; }
-          Wh.push_back(w->host.data()); bh.push_back(b->host.data()); gm.push_back(g->host.data()); bt.push_back(e->host.data());
-        }
-        if (!ok) break;
-        bool in_range = false;
-        HIPCHK(h, build_tapfold(c.head_dtype, (int)grp.size(), oci, D2, Kp, Wh.data(), bh.data(), gm.data(), bt.data(), &tf.w16[i], &tf.bias[i], &in_range));
-        if (!in_range) ok = false;   // gamma now scales a weight: out of the operand type's range -> the direct form for this handle
-      }
-      if (ok) { tf.heads = grp; tf.valid = true; h->tapfold = tf; }
-      else free_tapfold(tf);
-    }
-    h->tconv_valid = true;
   }
   // camera init token broadcast [nt][12]
   if (c.enable_cam) {
@@ -891,7 +1123,7 @@ wm_status plan(wm_handle* h, const Dims& d) {
     if (it && !it->host.empty())
       for (int i = 0; i < d.nt; ++i)
         for (int k = 0; k < 9; ++k) v[(size_t)i * 12 + k] = it->host[k];
-    HIPCHK(h, hipMemcpy(h->buf["cam_init"], v.data(), v.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(ws.cam_init, v.data(), v.size() * 4, hipMemcpyHostToDevice));
   }
   h->plan_n = d.n; h->plan_nt = d.nt; h->plan_H = d.H; h->plan_W = d.W;
   return WM_OK;
@@ -981,12 +1213,8 @@ wm_status gemm(Ctx& c, int dt, int epi, const void* A, int lda, const void* Wp, 
   return WM_OK;
 }
 
-wm_status layernorm(Ctx& c, const float* x, int ld_in, void* y, int ld_out, const float* w, const float* b, int D, float eps,
-                    int groups, int rpg, int in_group, int in_off, int out_group, int out_off, int out_f32, int dt) {
-  WmLnArgs a;
-  a.x = x; a.y = y; a.w = w; a.b = b; a.D = D; a.ld_in = ld_in; a.ld_out = ld_out; a.eps = eps;
-  a.groups = groups; a.rows_per_group = rpg; a.in_group = in_group; a.in_off = in_off; a.out_group = out_group; a.out_off = out_off;
-  a.out_f32 = out_f32; a.dtype = dt;
+// a: the caller sets, by field name, what differs from zero
+wm_status layernorm(Ctx& c, const WmLnArgs& a) {
   LCHK(c, wm_launch_layernorm(a, c.s));
   return WM_OK;
 }
@@ -994,31 +1222,35 @@ wm_status layernorm(Ctx& c, const float* x, int ld_in, void* y, int ld_out, cons
 // Block.forward (block.py:72-93) on the fp32 residual stream X [M][D]; seq_len = attention span.
 // tap_half: when non-null, the block's output (the value its last GEMM stores to X) is also written to tap_half[row * 2D + col]
 // by that GEMM's epilogue — the cat([frame_out, global_out], -1) of visual_transformer.py:337-339 without a copy pass.
-// next_norm1: name prefix of the block that follows on the same stream X ("" = none): its norm1 is then computed by this block's fc2
+// next_norm1: norm1 of the block that follows on the same stream X (null = none): it is then computed by this block's fc2
 // epilogue when the shape allows (wm_gemm_fuses_ln) and *ln1_ready tells the caller to pass ln1_done to that block.
-wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_len, int heads, float eps, bool qk_norm,
+wm_status backbone_block(Ctx& c, const BlockW& w, float* X, int M, int seq_len, int heads, float eps,
                          bool rope, int tokens_per_view, int patch_start, bool is_global, float* tap_half = nullptr,
-                         bool ln1_done = false, const std::string& next_norm1 = std::string(), bool* ln1_ready = nullptr) {
+                         bool ln1_done = false, const Norm* next_norm1 = nullptr, bool* ln1_ready = nullptr) {
   wm_handle* h = c.h;
   const Dims& d = c.d;
+  const Workspace& ws = h->ws;
   const int D = d.D, dt = c.bdt;
-  uint16_t* A16 = B<uint16_t>(h, "A16");
-  char* QKV16 = B<char>(h, "QKV16");
+  uint16_t* A16 = ws.A16;
+  char* QKV16 = ws.QKV16;
   const size_t hsz = (size_t)M * D * 2;  // bytes of one of Q/K/V
   void* Q16 = QKV16; void* K16 = QKV16 + hsz; void* V16 = QKV16 + 2 * hsz;
-  void* O16 = B<void>(h, "O16");
-  void* H16 = B<void>(h, "H16");
+  void* O16 = ws.O16;
+  void* H16 = ws.H16;
   wm_status st;
   if (ln1_ready) *ln1_ready = false;
+  WmLnArgs ln{};   // norm1 / norm2 of the M rows of X into A16
+  ln.x = X; ln.ld_in = D; ln.y = A16; ln.ld_out = D; ln.D = D; ln.eps = eps; ln.groups = 1; ln.rows_per_group = M; ln.dtype = dt;
   if (!ln1_done) {
-    st = layernorm(c, X, D, A16, D, F(h, p + "norm1.weight"), F(h, p + "norm1.bias"), D, eps, 1, M, 0, 0, 0, 0, 0, dt);
+    ln.w = w.norm1.w; ln.b = w.norm1.b;
+    st = layernorm(c, ln);
     if (st) return st;
   }
   // the residual GEMMs carry the LayerNorm that follows them when the launch allows it (gemm.hip epilogue_resid_ln)
-  auto fuse_args = [&](WmGemmArgs& ex, const float* w, const float* b) {
-    ex.ln_out = A16; ex.ln_ld = D; ex.ln_w = w; ex.ln_b = b; ex.ln_eps = eps;
-    ex.ln_stats = B<float>(h, "LN_STATS");
-    int* sync = B<int>(h, "LN_SYNC");
+  auto fuse_args = [&](WmGemmArgs& ex, const Norm& n) {
+    ex.ln_out = A16; ex.ln_ld = D; ex.ln_w = n.w; ex.ln_b = n.b; ex.ln_eps = eps;
+    ex.ln_stats = ws.LN_STATS;
+    int* sync = ws.LN_SYNC;
     ex.ln_sync = sync; ex.ln_fallback = sync + ((size_t)d.Mx / 16 + 2) * 2;
   };
   {  // QKV projection with q/k-norm + RoPE + head-major relayout fused into the epilogue (attention.py:50-56)
@@ -1026,14 +1258,11 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
     memset(&ex, 0, sizeof(ex));
     WmQkvArgs& a = ex.qkv;
     a.q = Q16; a.k = K16; a.v = V16;
-    if (qk_norm) {
-      a.qn_w = F(h, p + "attn.q_norm.weight"); a.qn_b = F(h, p + "attn.q_norm.bias");
-      a.kn_w = F(h, p + "attn.k_norm.weight"); a.kn_b = F(h, p + "attn.k_norm.bias");
-    }
-    if (rope) { a.rope_cos = B<float>(h, "rope_cos"); a.rope_sin = B<float>(h, "rope_sin"); }
+    a.qn_w = w.q_norm.w; a.qn_b = w.q_norm.b; a.kn_w = w.k_norm.w; a.kn_b = w.k_norm.b;   // (null in the DINO blocks)
+    if (rope) { a.rope_cos = ws.rope_cos; a.rope_sin = ws.rope_sin; }
     a.M = M; a.H = heads; a.head_stride = M; a.tokens_per_view = tokens_per_view; a.patch_start = patch_start; a.grid_w = d.gw;
     a.q_scale = 0.125f * 1.4426950408889634f; a.dtype = dt;  // 1/sqrt(64) * log2(e): the attention kernel works in base 2
-    st = gemm(c, dt, WM_EPI_QKV, A16, D, W16(h, p + "attn.qkv.weight"), D, nullptr, 0, F(h, p + "attn.qkv.bias"), nullptr, M, 3 * D, D, &ex);
+    st = gemm(c, dt, WM_EPI_QKV, A16, D, w.qkv.w, D, nullptr, 0, w.qkv.b, nullptr, M, 3 * D, D, &ex);
     if (st) return st;
   }
   {
@@ -1047,12 +1276,12 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
     // compared bit for bit, is on record.  The second queue is safe here: between fork and join the compute queue runs only
     // the attention kernels, which contain no packed-fp32 instruction (the hazard described at the DPT heads below needs one;
     // tests/test_kernel_resources_cpu.py disassembles them)
-    a.part_o = B<float>(h, "ATT_PO"); a.part_ml = B<float>(h, "ATT_ML"); a.max_splits = WM_ATTN_MAX_SPLITS;
-    a.unit_flags = B<int>(h, "ATT_FLAGS");
+    a.part_o = ws.ATT_PO; a.part_ml = ws.ATT_ML; a.max_splits = WM_ATTN_MAX_SPLITS;
+    a.unit_flags = ws.ATT_FLAGS;
     const size_t hint_n = wm_attention_max_blocks((int)d.Mx, d.P < d.Td ? d.P : d.Td, d.heads);
     const int site = c.attn_site++;
-    int* const hint0 = B<int>(h, "ATT_HINT") + (size_t)site * 3 * hint_n;
-    int* const stat0 = B<int>(h, "ATT_STAT") + (size_t)site * 3;
+    int* const hint0 = ws.ATT_HINT + (size_t)site * 3 * hint_n;
+    int* const stat0 = ws.ATT_STAT + (size_t)site * 3;
     a.unit_hint = hint0; a.unit_stat = stat0;
     bool general_only = false;
     if (site * 3 < h->att_stat_n) {
@@ -1088,7 +1317,7 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
         LCHK(c, hipEventCreateWithFlags(&h->cfork, hipEventDisableTiming));
         LCHK(c, hipEventCreateWithFlags(&h->cjoin, hipEventDisableTiming));
       }
-      char* KVG = B<char>(h, "KVG");
+      char* KVG = ws.KVG;
       const int rank = h->comm.rank, world = d.world;
       LCHK(c, hipEventRecord(h->cfork, c.s));
       // slice counts: minimise rounds x tiles per block over the resident slots, per launch (uniform slices only)
@@ -1100,7 +1329,7 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
         WmAttnArgs g = a;
         g.force_partial = 1; g.seq_len = M; g.kv_head_stride = M;
         if (chunks <= 1) { g.K = K16; g.V = V16; g.kv_chunks = 1; }
-        else { g.K = B<char>(h, "KVG"); g.V = g.K; g.kv_chunks = chunks; g.kv_rows_per_chunk = M; g.kv_chunk_stride = (long long)(2 * hsz / 2); }
+        else { g.K = ws.KVG; g.V = g.K; g.kv_chunks = chunks; g.kv_rows_per_chunk = M; g.kv_chunk_stride = (long long)(2 * hsz / 2); }
         int unit_rows = 256, per_cu = 2;
         wm_attention_geometry(g, &unit_rows, &per_cu);
         const int ntiles = (chunks < 1 ? 1 : chunks) * ntpc;
@@ -1144,7 +1373,7 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
     } else {
       if (sharded) {
         // K and V are adjacent: one all-gather of [K|V] per layer -> [world][2][H][M][64]
-        char* KVG = B<char>(h, "KVG");
+        char* KVG = ws.KVG;
         st = comm_allgather(h, K16, KVG, 2 * hsz, c.s);
         if (st) return st;
         a.K = KVG; a.V = KVG + hsz; a.seq_len = M; a.kv_head_stride = M; a.kv_chunks = d.world;
@@ -1160,36 +1389,32 @@ wm_status backbone_block(Ctx& c, const std::string& p, float* X, int M, int seq_
   {
     WmGemmArgs ex;
     memset(&ex, 0, sizeof(ex));
-    fuse_args(ex, F(h, p + "norm2.weight"), F(h, p + "norm2.bias"));
+    fuse_args(ex, w.norm2);
     bool fused = false;
-    st = gemm(c, dt, WM_EPI_RESID, O16, D, W16(h, p + "attn.proj.weight"), D, X, D, F(h, p + "attn.proj.bias"), F(h, p + "ls1.gamma"), M, D, D, &ex, -1, &fused);
+    st = gemm(c, dt, WM_EPI_RESID, O16, D, w.proj.w, D, X, D, w.proj.b, w.ls1, M, D, D, &ex, -1, &fused);
     if (st) return st;
     if (!fused) {
-      st = layernorm(c, X, D, A16, D, F(h, p + "norm2.weight"), F(h, p + "norm2.bias"), D, eps, 1, M, 0, 0, 0, 0, 0, dt);
+      ln.w = w.norm2.w; ln.b = w.norm2.b;
+      st = layernorm(c, ln);
       if (st) return st;
     }
   }
   const int Hd = c.h->cfg.mlp_ratio * D;
-  st = gemm(c, dt, WM_EPI_GELU_T16, A16, D, W16(h, p + "mlp.fc1.weight"), D, H16, Hd, F(h, p + "mlp.fc1.bias"), nullptr, M, Hd, D);
+  st = gemm(c, dt, WM_EPI_GELU_T16, A16, D, w.fc1.w, D, H16, Hd, w.fc1.b, nullptr, M, Hd, D);
   if (st) return st;
   WmGemmArgs ex;
   memset(&ex, 0, sizeof(ex));
   ex.C2 = tap_half; ex.ldc2 = 2 * D;
   bool fused = false;
-  if (!next_norm1.empty()) fuse_args(ex, F(h, next_norm1 + "norm1.weight"), F(h, next_norm1 + "norm1.bias"));
-  st = gemm(c, dt, WM_EPI_RESID, H16, Hd, W16(h, p + "mlp.fc2.weight"), Hd, X, D, F(h, p + "mlp.fc2.bias"), F(h, p + "ls2.gamma"), M, D, Hd, &ex, -1, &fused);
+  if (next_norm1) fuse_args(ex, *next_norm1);
+  st = gemm(c, dt, WM_EPI_RESID, H16, Hd, w.fc2.w, Hd, X, D, w.fc2.b, w.ls2, M, D, Hd, &ex, -1, &fused);
   if (ln1_ready) *ln1_ready = fused;
   return st;
 }
 
-wm_status linear32(Ctx& c, const float* X, int ldx, const std::string& name, float* Y, int ldy, int M, int pre, int post,
+wm_status linear32(Ctx& c, const float* X, int ldx, const Lin32& w, float* Y, int ldy, int M, int pre, int post,
                    const float* gamma = nullptr, int accumulate = 0) {
-  const Weight* w = W(c.h, name + ".weight");
-  if (!w || !w->f32) return fail(c.h, WM_ERR_STATE, "missing fp32 weight " + name);
-  const int N = (int)w->shape[0];
-  int K = 1;
-  for (size_t i = 1; i < w->shape.size(); ++i) K *= (int)w->shape[i];
-  LCHK(c, wm_launch_linear_f32(X, w->f32, F(c.h, name + ".bias"), Y, M, N, K, ldx, ldy, pre, post, gamma, accumulate, c.s));
+  LCHK(c, wm_launch_linear_f32(X, w.w, w.b, Y, M, w.N, w.K, ldx, ldy, pre, post, gamma, accumulate, c.s));
   return WM_OK;
 }
 
@@ -1198,51 +1423,58 @@ wm_status camera_head(Ctx& c, float* out_params) {
   wm_handle* h = c.h;
   const Dims& d = c.d;
   const wm_config& cf = h->cfg;
+  const Model& m = h->m;
+  const Workspace& ws = h->ws;
   const int D2 = 2 * d.D, S = d.nt;
-  const std::string ch = "cam_head.";
-  float* tok = B<float>(h, "cam_tok");
+  float* tok = ws.cam_tok;
   wm_status st;
   // token_norm on tap3[:, :, 0]
-  float* tok_local = d.world > 1 ? B<float>(h, "cam_tok_local") : tok;
-  st = layernorm(c, B<float>(h, "tap3"), D2, tok_local, D2, F(h, ch + "token_norm.weight"), F(h, ch + "token_norm.bias"), D2, 1e-5f,
-                 d.n, 1, d.P, 0, 1, 0, 1, 0);
+  float* tok_local = d.world > 1 ? ws.cam_tok_local : tok;
+  WmLnArgs ln{};
+  ln.x = ws.tap[3]; ln.ld_in = D2; ln.y = tok_local; ln.ld_out = D2; ln.w = m.cam_token_norm.w; ln.b = m.cam_token_norm.b; ln.D = D2; ln.eps = 1e-5f;
+  ln.groups = d.n; ln.rows_per_group = 1; ln.in_group = d.P; ln.out_group = 1; ln.out_f32 = 1;
+  st = layernorm(c, ln);
   if (st) return st;
   if (d.world > 1) {
     st = comm_allgather(h, tok_local, tok, (size_t)d.n * D2 * 4, c.s);
     if (st) return st;
   }
-  float *e = B<float>(h, "cam_e"), *mod = B<float>(h, "cam_mod"), *hh = B<float>(h, "cam_h"), *a = B<float>(h, "cam_a");
-  float *qkv = B<float>(h, "cam_qkv"), *o = B<float>(h, "cam_o"), *f = B<float>(h, "cam_f");
-  float *pred = B<float>(h, "cam_pred"), *delta = B<float>(h, "cam_delta"), *init = B<float>(h, "cam_init");
+  float *e = ws.cam_e, *mod = ws.cam_mod, *hh = ws.cam_h, *a = ws.cam_a;
+  float *qkv = ws.cam_qkv, *o = ws.cam_o, *f = ws.cam_f;
+  float *pred = ws.cam_pred, *delta = ws.cam_delta, *init = ws.cam_init;
   LCHK(c, hipMemsetAsync(pred, 0, (size_t)S * 12 * 4, c.s));
   LCHK(c, hipMemsetAsync(delta, 0, (size_t)S * 12 * 4, c.s));
+  ln = WmLnArgs{};   // the trunk's norms: the S rows of hh into a, fp32
+  ln.x = hh; ln.ld_in = D2; ln.y = a; ln.ld_out = D2; ln.D = D2; ln.eps = 1e-5f; ln.groups = 1; ln.rows_per_group = S; ln.out_f32 = 1;
   for (int step = 0; step < cf.cam_steps; ++step) {
-    st = linear32(c, step == 0 ? init : pred, 12, ch + "param_embed", e, D2, S, 0, 0);
+    st = linear32(c, step == 0 ? init : pred, 12, m.cam_param_embed, e, D2, S, 0, 0);
     if (st) return st;
-    st = linear32(c, e, D2, ch + "adapt_norm_gen.1", mod, 3 * D2, S, 1, 0);
+    st = linear32(c, e, D2, m.cam_adapt, mod, 3 * D2, S, 1, 0);
     if (st) return st;
     LCHK(c, wm_launch_adaln(tok, mod, hh, S, D2, 1e-6f, c.s));
-    for (int b = 0; b < cf.cam_trunk_depth; ++b) {
-      const std::string p = ch + "refine_net." + std::to_string(b) + ".";
-      st = layernorm(c, hh, D2, a, D2, F(h, p + "norm1.weight"), F(h, p + "norm1.bias"), D2, 1e-5f, 1, S, 0, 0, 0, 0, 1, 0);
+    for (const CamBlockW& w : m.cam) {
+      ln.w = w.norm1.w; ln.b = w.norm1.b;
+      st = layernorm(c, ln);
       if (st) return st;
-      st = linear32(c, a, D2, p + "attn.qkv", qkv, 3 * D2, S, 0, 0);
+      st = linear32(c, a, D2, w.qkv, qkv, 3 * D2, S, 0, 0);
       if (st) return st;
       LCHK(c, wm_launch_small_attention(qkv, o, S, cf.cam_heads, D2 / cf.cam_heads, c.s));
-      st = linear32(c, o, D2, p + "attn.proj", hh, D2, S, 0, 0, F(h, p + "ls1.gamma"), 1);
+      st = linear32(c, o, D2, w.proj, hh, D2, S, 0, 0, w.ls1, 1);
       if (st) return st;
-      st = layernorm(c, hh, D2, a, D2, F(h, p + "norm2.weight"), F(h, p + "norm2.bias"), D2, 1e-5f, 1, S, 0, 0, 0, 0, 1, 0);
+      ln.w = w.norm2.w; ln.b = w.norm2.b;
+      st = layernorm(c, ln);
       if (st) return st;
-      st = linear32(c, a, D2, p + "mlp.fc1", f, 4 * D2, S, 0, 2);
+      st = linear32(c, a, D2, w.fc1, f, 4 * D2, S, 0, 2);
       if (st) return st;
-      st = linear32(c, f, 4 * D2, p + "mlp.fc2", hh, D2, S, 0, 0, F(h, p + "ls2.gamma"), 1);
+      st = linear32(c, f, 4 * D2, w.fc2, hh, D2, S, 0, 0, w.ls2, 1);
       if (st) return st;
     }
-    st = layernorm(c, hh, D2, a, D2, F(h, ch + "out_norm.weight"), F(h, ch + "out_norm.bias"), D2, 1e-5f, 1, S, 0, 0, 0, 0, 1, 0);
+    ln.w = m.cam_out_norm.w; ln.b = m.cam_out_norm.b;
+    st = layernorm(c, ln);
     if (st) return st;
-    st = linear32(c, a, D2, ch + "param_predictor.fc1", f, D2 / 2, S, 0, 2);
+    st = linear32(c, a, D2, m.cam_pred_fc1, f, D2 / 2, S, 0, 2);
     if (st) return st;
-    st = linear32(c, f, D2 / 2, ch + "param_predictor.fc2", delta, 12, S, 0, 0);
+    st = linear32(c, f, D2 / 2, m.cam_pred_fc2, delta, 12, S, 0, 0);
     if (st) return st;
     LCHK(c, wm_launch_cam_update(pred, delta, out_params, S, step == 0, c.s));
   }
@@ -1396,7 +1628,10 @@ static hipError_t build_tapfold(int dt, int nh, int oc, int K, int Kp, const flo
 // dst[k] [n hw][oc], 16-bit (out16) or fp32
 wm_status tap_front_one(Ctx& c, const float* tap, void* xhat, const void* w16, const float* bias, const float* pos, int nh, int oc, int out16,
                         void* const* dst, int n, int hw, int P, int psi, int D2) {
-  wm_status st = layernorm(c, tap, D2, xhat, D2, nullptr, nullptr, D2, 1e-5f, n, hw, P, psi, hw, 0, 0, c.hdt);
+  WmLnArgs ln{};   // no affine: it is folded into the projection
+  ln.x = tap; ln.ld_in = D2; ln.y = xhat; ln.ld_out = D2; ln.D = D2; ln.eps = 1e-5f;
+  ln.groups = n; ln.rows_per_group = hw; ln.in_group = P; ln.in_off = psi; ln.out_group = hw; ln.dtype = c.hdt;
+  wm_status st = layernorm(c, ln);
   if (st) return st;
   WmGemmArgs ex;
   memset(&ex, 0, sizeof(ex));
@@ -1406,28 +1641,28 @@ wm_status tap_front_one(Ctx& c, const float* tap, void* xhat, const void* w16, c
   return gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, xhat, D2, w16, ru(D2, 64), nullptr, oc, bias, nullptr, n * hw, nh * oc, D2, &ex);
 }
 
-// where head `slot` finds the projection of tap i for the views from v0 on (the shared front's outputs; all n views of the rank)
-void* tap_front_dst(wm_handle* h, const Dims& d, int slot, int i, int v0) {
+// where head slot `hb` finds the projection of tap i for the views from v0 on (the shared front's outputs; all n views of the rank)
+void* tap_front_dst(const wm_handle* h, const Dims& d, const HeadBufs& hb, int i, int v0) {
   const int32_t* oc = h->cfg.dpt_out_channels;
-  static const char* const names[4] = {"dpt_P16_h", "dpt_P16b_h", "dpt_f2_h", "dpt_f3in_h"};
-  char* base = (char*)h->buf.at(std::string(names[i]) + std::to_string(slot));
-  return base + (size_t)v0 * d.hw * oc[i] * (i < 2 ? 2 : 4);
+  void* const base[4] = {hb.P16, hb.P16b, hb.f2, hb.f3in};
+  return (char*)base[i] + (size_t)v0 * d.hw * oc[i] * (i < 2 ? 2 : 4);
 }
 
 // the shared front of all heads of the group, every view chunk, on c.s (before the heads fork)
 wm_status tap_front(Ctx& c) {
   wm_handle* h = c.h;
   const Dims& d = c.d;
+  const Workspace& ws = h->ws;
   const TapFold& tf = h->tapfold;
-  const int D2 = 2 * d.D, nh = (int)tf.heads.size();
-  void* xhat = h->buf.at("dpt_T16_h0");
+  const int D2 = 2 * d.D, nh = tf.nh;
+  void* xhat = ws.hb[0].T16;
   for (int v0 = 0; v0 < d.n; v0 += d.chunk) {
     const int n = std::min(d.chunk, d.n - v0);
     for (int i = 0; i < 4; ++i) {
       void* dst[4] = {nullptr, nullptr, nullptr, nullptr};
-      for (int k = 0; k < nh; ++k) dst[k] = tap_front_dst(h, d, k, i, v0);
-      const float* tap = B<float>(h, ("tap" + std::to_string(i)).c_str()) + (size_t)v0 * d.P * D2;
-      wm_status st = tap_front_one(c, tap, xhat, tf.w16[i], tf.bias[i], B<float>(h, ("dpt_pos" + std::to_string(i)).c_str()), nh,
+      for (int k = 0; k < nh; ++k) dst[k] = tap_front_dst(h, d, ws.hb[k], i, v0);
+      const float* tap = ws.tap[i] + (size_t)v0 * d.P * D2;
+      wm_status st = tap_front_one(c, tap, xhat, tf.w16[i], tf.bias[i], ws.dpt_pos[i], nh,
                                    h->cfg.dpt_out_channels[i], i < 2 ? 1 : 0, dst, n, d.hw, d.P, d.psi, D2);
       if (st) return st;
     }
@@ -1447,37 +1682,37 @@ static hipError_t launch_tconv(const TconvPack& t, int dt, const void* tokens16,
   return wm_launch_tconv_border(out, t.bmiss, n, t.k * gh, t.k * gw, 256, s);
 }
 
-// up_hs > 0: x is [N][up_hs][up_ws][Cin] and the conv runs on its align_corners bilinear resize to (Hi, Wi)
-// (+ position tables), fused into the 3x3 halo kernel's input staging.
-wm_status conv(Ctx& c, const float* x, const std::string& wname, bool bias, const float* resid, bool resid_relu, const float* resid2,
-               float* y, int N, int Hi, int Wi, int ks, int stride, int pad, bool relu_in, int up_hs = 0, int up_ws = 0,
-               const float* up_addx = nullptr, const float* up_addy = nullptr, bool* out16 = nullptr, bool relu_out = false, bool in16 = false) {
-  const Weight* w = W(c.h, wname + ".weight");
-  if (!w || !w->w16) return fail(c.h, WM_ERR_STATE, "missing conv weight " + wname);
+// the geometry of a conv launch; the caller then sets, by field name, whatever else differs from zero (residuals, ReLUs, 16-bit forms, fused resize)
+WmConvArgs conv_args(const float* x, float* y, int N, int Hi, int Wi, int ksize, int stride, int pad) {
   WmConvArgs a;
   memset(&a, 0, sizeof(a));
-  a.up_hs = up_hs; a.up_ws = up_ws; a.up_addx = up_addx; a.up_addy = up_addy;
-  a.x = x; a.w = w->w16; a.bias = bias ? F(c.h, wname + ".bias") : nullptr; a.resid = resid; a.resid2 = resid2; a.y = y;
-  a.N = N; a.Hi = Hi; a.Wi = Wi; a.Cin = (int)w->shape[1]; a.Cout = (int)w->shape[0]; a.ksize = ks; a.stride = stride; a.pad = pad;
-  a.Ho = (Hi + 2 * pad - ks) / stride + 1; a.Wo = (Wi + 2 * pad - ks) / stride + 1;
-  a.relu_in = relu_in; a.resid_relu = resid_relu; a.relu_out = relu_out ? 1 : 0; a.in16 = in16 ? 1 : 0; a.dtype = c.hdt;
+  a.x = x; a.y = y; a.N = N; a.Hi = Hi; a.Wi = Wi; a.ksize = ksize; a.stride = stride; a.pad = pad;
+  return a;
+}
+
+// a.up_hs > 0: x is [N][up_hs][up_ws][Cin] and the conv runs on its align_corners bilinear resize to (Hi, Wi)
+// (+ position tables), fused into the 3x3 halo kernel's input staging.
+// The weight, bias, channel counts, output size and operand type are filled in here.
+wm_status conv(Ctx& c, const ConvW& w, WmConvArgs a, bool* out16 = nullptr) {
+  a.w = w.w16; a.bias = w.bias; a.Cin = w.cin; a.Cout = w.cout; a.dtype = c.hdt;
+  a.Ho = (a.Hi + 2 * a.pad - a.ksize) / a.stride + 1; a.Wo = (a.Wi + 2 * a.pad - a.ksize) / a.stride + 1;
   if (out16) {  // the caller can take y as a 16-bit tensor (its only consumer rounds it to the operand type anyway): granted when the kernel can
     *out16 = wm_conv3x3_out16_ok(a);
     a.out16 = *out16 ? 1 : 0;
   }
   // timing kinds by kernel instantiation: the F -> F 3x3 convs of the two large pyramid levels, output_conv1 with its fused
   // resize; everything else (small levels, 1x1, stride 2) under 3
-  const bool pyr = ks == 3 && stride == 1 && up_hs == 0 && a.Cin == a.Cout && a.Cin >= 128;
-  const int kind = up_hs > 0 ? 10 : pyr && Hi == 4 * c.d.gh ? 8 : pyr && Hi == 2 * c.d.gh ? 9 : 3;
+  const bool pyr = a.ksize == 3 && a.stride == 1 && a.up_hs == 0 && a.Cin == a.Cout && a.Cin >= 128;
+  const int kind = a.up_hs > 0 ? 10 : pyr && a.Hi == 4 * c.d.gh ? 8 : pyr && a.Hi == 2 * c.d.gh ? 9 : 3;
   ProfScope ps(c.h, kind, c.s);
-  if (wm_tune(WM_TUNE_CONV_GEMM, 0) == 1 && in16 && ks == 3 && stride == 1 && pad == 1 && up_hs == 0 && a.Cin % 64 == 0 && a.Cout % 8 == 0 &&
-      (long)N * Hi * Wi >= 4096) {
+  if (wm_tune(WM_TUNE_CONV_GEMM, 0) == 1 && a.in16 && a.ksize == 3 && a.stride == 1 && a.pad == 1 && a.up_hs == 0 && a.Cin % 64 == 0 && a.Cout % 8 == 0 &&
+      (long)a.N * a.Hi * a.Wi >= 4096) {
     // a 16-bit NHWC input: the conv IS the ping-pong GEMM over (pixels) x (tap, channel), the A pieces DMA-ed from the shifted pixels
     WmGemmArgs g;
     memset(&g, 0, sizeof(g));
-    g.A = x; g.W = w->w16; g.C = y; g.bias = a.bias; g.M = N * Hi * Wi; g.N = a.Cout; g.K = 9 * a.Cin; g.lda = a.Cin; g.ldw = 9 * a.Cin; g.ldc = a.Cout;
-    g.dtype = c.hdt; g.epi = WM_EPI_CONV; g.cv_h = Hi; g.cv_w = Wi; g.cv_cin = a.Cin; g.cv_zero = B<uint16_t>(c.h, "ZERO256");
-    g.cv_resid = resid; g.cv_resid2 = resid2; g.cv_resid_relu = resid_relu ? 1 : 0; g.out16 = a.out16; g.relu = a.relu_out;
+    g.A = a.x; g.W = a.w; g.C = a.y; g.bias = a.bias; g.M = a.N * a.Hi * a.Wi; g.N = a.Cout; g.K = 9 * a.Cin; g.lda = a.Cin; g.ldw = 9 * a.Cin; g.ldc = a.Cout;
+    g.dtype = c.hdt; g.epi = WM_EPI_CONV; g.cv_h = a.Hi; g.cv_w = a.Wi; g.cv_cin = a.Cin; g.cv_zero = c.h->ws.ZERO256;
+    g.cv_resid = a.resid; g.cv_resid2 = a.resid2; g.cv_resid_relu = a.resid_relu ? 1 : 0; g.out16 = a.out16; g.relu = a.relu_out;
     LCHK(c, wm_launch_gemm(g, c.s));
     return WM_OK;
   }
@@ -1485,106 +1720,109 @@ wm_status conv(Ctx& c, const float* x, const std::string& wname, bool bias, cons
   return WM_OK;
 }
 
-// ResidualConvUnit (dense_head.py:435-455): y = conv2(relu(conv1(relu x))) + relu(x) (+ extra)
+// ResidualConvUnit (dense_head.py:435-455): y = conv2(relu(conv1(relu x))) + relu(x) (+ extra); w: the unit's conv1, conv2
 // y16: when non-null the caller can take y as a 16-bit tensor; *y16 tells whether it got one
 // conv1's output has ONE consumer, conv2's input staging, which applies ReLU and rounds to the operand type: where the kernel can, conv1
 // writes exactly that — relu(conv1) as a 16-bit tensor — and conv2 stages it unconverted (bit-identical values; a quarter of the
 // bytes written, a quarter read: 268 MB less traffic per RCU at 148^2 x 8 views).  Tuning rcu_mid16 = 0: the fp32 intermediate (A/B).
-wm_status rcu(Ctx& c, const std::string& p, const float* x, const float* extra, float* tmp, float* y, int N, int Hh, int Ww, bool* y16 = nullptr) {
+wm_status rcu(Ctx& c, const ConvW (&w)[2], const float* x, const float* extra, float* tmp, float* y, int N, int Hh, int Ww, bool* y16 = nullptr) {
   const bool want = wm_tune(WM_TUNE_RCU_MID16, 1) != 0;
   bool mid16 = false;
-  wm_status st = conv(c, x, p + "conv1", true, nullptr, false, nullptr, tmp, N, Hh, Ww, 3, 1, 1, true, 0, 0, nullptr, nullptr, want ? &mid16 : nullptr, want);
+  WmConvArgs a1 = conv_args(x, tmp, N, Hh, Ww, 3, 1, 1);
+  a1.relu_in = 1; a1.relu_out = want ? 1 : 0;
+  wm_status st = conv(c, w[0], a1, want ? &mid16 : nullptr);
   if (st) return st;
   // (relu_out was requested together with out16; if the kernel could not grant out16 the fp32 tmp holds relu(conv1), and relu is idempotent)
-  return conv(c, tmp, p + "conv2", true, x, true, extra, y, N, Hh, Ww, 3, 1, 1, !mid16, 0, 0, nullptr, nullptr, y16, false, mid16);
+  WmConvArgs a2 = conv_args(tmp, y, N, Hh, Ww, 3, 1, 1);
+  a2.resid = x; a2.resid_relu = 1; a2.resid2 = extra; a2.relu_in = mid16 ? 0 : 1; a2.in16 = mid16 ? 1 : 0;
+  return conv(c, w[1], a2, y16);
 }
 
 // FeatureFusionBlock.out_conv (1x1, dense_head.py:496) on x2 [N*H*W][F]: a plain GEMM when x2 came as a 16-bit tensor (the ping-pong
 // kernel, fp32 NHWC out), the generic conv kernel on the fp32 tensor otherwise
 // y16: the output as a 16-bit tensor of the operand type (its only consumer is a GEMM: the tap GEMM of upconv.hip); needs x2_is_16
-wm_status out_conv(Ctx& c, const std::string& name, const float* x2, bool x2_is_16, float* y, int N, int Hh, int Ww, int F_, bool y16 = false) {
-  if (!x2_is_16) return y16 ? fail(c.h, WM_ERR_STATE, "out_conv: 16-bit output needs the 16-bit input") : conv(c, x2, name, true, nullptr, false, nullptr, y, N, Hh, Ww, 1, 1, 0, false);
-  const Weight* w = W(c.h, name + ".weight");
-  if (!w || !w->w16 || (int)w->shape[0] != F_ || (int)w->shape[1] != F_) return fail(c.h, WM_ERR_STATE, "missing conv weight " + name);
-  return gemm(c, c.hdt, y16 ? WM_EPI_T16 : WM_EPI_F32, x2, F_, w->w16, F_, y, F_, F(c.h, name + ".bias"), nullptr, N * Hh * Ww, F_, F_, nullptr, 3);
+wm_status out_conv(Ctx& c, const ConvW& w, const float* x2, bool x2_is_16, float* y, int N, int Hh, int Ww, int F_, bool y16 = false) {
+  if (!x2_is_16) return y16 ? fail(c.h, WM_ERR_STATE, "out_conv: 16-bit output needs the 16-bit input") : conv(c, w, conv_args(x2, y, N, Hh, Ww, 1, 1, 0));
+  return gemm(c, c.hdt, y16 ? WM_EPI_T16 : WM_EPI_F32, x2, F_, w.w16, F_, y, F_, w.bias, nullptr, N * Hh * Ww, F_, F_, nullptr, 3);
 }
 
-// DPTHead (dense_head.py:107-295) for views [v0, v0+n) of this rank
-wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, bool is_gs, float* out_attr, float* out_conf,
+// DPTHead (dense_head.py:107-295) for views [v0, v0+n) of this rank: head `id` (its weights) in workspace slot `slot` (its buffers)
+wm_status dpt_head(Ctx& c, int id, int F_, int out_dim, int act, float* out_attr, float* out_conf,
                    const float* img, const wm_outputs* out, int first_view, int slot, bool front_done = false) {
   // front_done: the shared front (tap_front) has already normalised and projected the four taps of every view for this head's slot
-  const std::string sx = "_h" + std::to_string(slot);
-  auto HB = [&](const char* n) { return (float*)c.h->buf.at(std::string(n) + sx); };
   wm_handle* h = c.h;
   const Dims& d = c.d;
   const wm_config& cf = h->cfg;
+  const HeadW& w = h->m.head[id];
+  const Workspace& ws = h->ws;
+  const HeadBufs& hb = ws.hb[slot];
+  const bool is_gs = id == HD_GS;
   const int D2 = 2 * d.D, hw = d.hw, gh = d.gh, gw = d.gw;
   const int32_t* oc = cf.dpt_out_channels;
-  const std::string sc = p + "scratch.";
-  float* S0 = HB("dpt_s0"); float* S1 = HB("dpt_s1"); float* S2 = HB("dpt_s2"); float* S3 = HB("dpt_s3");
+  float* S0 = hb.s[0]; float* S1 = hb.s[1]; float* S2 = hb.s[2]; float* S3 = hb.s[3];
   wm_status st;
   for (int v0 = 0; v0 < d.n; v0 += d.chunk) {
     const int n = std::min(d.chunk, d.n - v0);
-    float* feats[4] = {HB("dpt_f0"), HB("dpt_f1"), front_done ? (float*)tap_front_dst(h, d, slot, 2, v0) : HB("dpt_f2"), HB("dpt_f3")};
+    float* feats[4] = {hb.f0, hb.f1, front_done ? (float*)tap_front_dst(h, d, hb, 2, v0) : hb.f2, hb.f3};
     bool tconv_done[4] = {false, false, false, false};
     for (int i = 0; i < 4; ++i) {
-      const float* tap = B<float>(h, ("tap" + std::to_string(i)).c_str()) + (size_t)v0 * d.P * D2;
-      void* T16 = HB("dpt_T16");
+      const float* tap = ws.tap[i] + (size_t)v0 * d.P * D2;
+      void* T16 = hb.T16;
       if (!front_done) {
-        st = layernorm(c, tap, D2, T16, D2, F(h, p + "norm.weight"), F(h, p + "norm.bias"), D2, 1e-5f, n, hw, d.P, d.psi, hw, 0, 0, c.hdt);
+        WmLnArgs ln{};
+        ln.x = tap; ln.ld_in = D2; ln.y = T16; ln.ld_out = D2; ln.w = w.norm.w; ln.b = w.norm.b; ln.D = D2; ln.eps = 1e-5f;
+        ln.groups = n; ln.rows_per_group = hw; ln.in_group = d.P; ln.in_off = d.psi; ln.out_group = hw; ln.dtype = c.hdt;
+        st = layernorm(c, ln);
         if (st) return st;
       }
-      const std::string pj = p + "projects." + std::to_string(i);
       WmGemmArgs ex;
       memset(&ex, 0, sizeof(ex));
-      ex.rows_per_group = hw; ex.out_group = hw; ex.out_off = 0; ex.add = B<float>(h, ("dpt_pos" + std::to_string(i)).c_str());
+      ex.rows_per_group = hw; ex.out_group = hw; ex.out_off = 0; ex.add = ws.dpt_pos[i];
       if (i < 2) {  // feeds a k==stride ConvTranspose (GEMM): 16-bit output
         ex.out16 = 1;
-        void* P16 = front_done ? tap_front_dst(h, d, slot, i, v0) : (void*)HB("dpt_P16");
+        void* P16 = front_done ? tap_front_dst(h, d, hb, i, v0) : hb.P16;
         if (!front_done) {
-          st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, W16(h, pj + ".weight"), D2, P16, oc[i], F(h, pj + ".bias"), nullptr, n * hw, oc[i], D2, &ex);
+          st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, w.proj[i].w, D2, P16, oc[i], w.proj[i].b, nullptr, n * hw, oc[i], D2, &ex);
           if (st) return st;
         }
-        auto tc = h->tconv.find(p + std::to_string(i));
-        tconv_done[i] = wm_tune(WM_TUNE_TCONV, 1) != 0 && !is_gs && F_ == 256 && tc != h->tconv.end() && tc->second.w16 != nullptr;
+        tconv_done[i] = wm_tune(WM_TUNE_TCONV, 1) != 0 && !is_gs && F_ == 256 && w.tconv[i] != nullptr;
         if (tconv_done[i]) {   // ConvTranspose and layer{i+1}_rn as one GEMM at the token resolution, straight into rn[i]
           ProfScope ps(h, i == 0 ? 8 : 3, c.s);
-          LCHK(c, launch_tconv(tc->second, c.hdt, P16, HB(i == 0 ? "dpt_rn1" : "dpt_rn2"), n, gh, gw, B<uint16_t>(h, "ZERO256"), c.s));
+          LCHK(c, launch_tconv(*w.tconv[i], c.hdt, P16, hb.rn[i], n, gh, gw, ws.ZERO256, c.s));
           continue;
         }
         const int k = i == 0 ? 4 : 2;
-        const std::string rs = p + "resize_layers." + std::to_string(i);
         WmGemmArgs ct;
         memset(&ct, 0, sizeof(ct));
         ct.ct_k = k; ct.ct_cout = oc[i]; ct.ct_gh = gh; ct.ct_gw = gw;
-        st = gemm(c, c.hdt, WM_EPI_CONVT, P16, oc[i], W16(h, rs + ".weight"), oc[i], feats[i], 0, F(h, rs + ".bias"), nullptr, n * hw, k * k * oc[i], oc[i], &ct);
+        st = gemm(c, c.hdt, WM_EPI_CONVT, P16, oc[i], w.resize[i].w, oc[i], feats[i], 0, w.resize[i].b, nullptr, n * hw, k * k * oc[i], oc[i], &ct);
         if (st) return st;
       } else {
-        float* dst = i == 2 ? feats[2] : front_done ? (float*)tap_front_dst(h, d, slot, 3, v0) : HB("dpt_f3in");
+        float* dst = i == 2 ? feats[2] : front_done ? (float*)tap_front_dst(h, d, hb, 3, v0) : hb.f3in;
         if (!front_done) {
-          st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, W16(h, pj + ".weight"), D2, dst, oc[i], F(h, pj + ".bias"), nullptr, n * hw, oc[i], D2, &ex);
+          st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, T16, D2, w.proj[i].w, D2, dst, oc[i], w.proj[i].b, nullptr, n * hw, oc[i], D2, &ex);
           if (st) return st;
         }
         if (i == 3) {
-          st = conv(c, dst, p + "resize_layers.3", true, nullptr, false, nullptr, feats[3], n, gh, gw, 3, 2, 1, false);
+          st = conv(c, w.resize3, conv_args(dst, feats[3], n, gh, gw, 3, 2, 1));
           if (st) return st;
         }
       }
     }
     const int Hs[4] = {4 * gh, 2 * gh, gh, d.gh2}, Ws[4] = {4 * gw, 2 * gw, gw, d.gw2};
-    float* rn[4] = {HB("dpt_rn1"), HB("dpt_rn2"), HB("dpt_rn3"), HB("dpt_rn4")};
+    float* const* rn = hb.rn;
     for (int i = 0; i < 4; ++i) {
       if (tconv_done[i]) continue;
-      st = conv(c, feats[i], sc + "layer" + std::to_string(i + 1) + "_rn", false, nullptr, false, nullptr, rn[i], n, Hs[i], Ws[i], 3, 1, 1, false);
+      st = conv(c, w.rn[i], conv_args(feats[i], rn[i], n, Hs[i], Ws[i], 3, 1, 1));
       if (st) return st;
     }
     // refinenet4: RCU2(rn4) -> resize to level 3 -> out_conv
     bool x16 = false;
-    st = rcu(c, sc + "refinenet4.resConfUnit2.", rn[3], nullptr, S0, S1, n, Hs[3], Ws[3], &x16);
+    st = rcu(c, w.rcu[3][1], rn[3], nullptr, S0, S1, n, Hs[3], Ws[3], &x16);
     if (st) return st;
     // out_conv (1x1) and the align_corners bilinear resize are both linear and the interpolation weights sum
     // to 1, so out_conv(resize(x)) == resize(out_conv(x)): run the 1x1 at the LOW resolution (4x fewer FLOPs)
-    st = out_conv(c, sc + "refinenet4.out_conv", S1, x16, S0, n, Hs[3], Ws[3], F_);
+    st = out_conv(c, w.out_conv[3], S1, x16, S0, n, Hs[3], Ws[3], F_);
     if (st) return st;
     LCHK(c, wm_launch_bilinear(S0, S2, n, Hs[3], Ws[3], Hs[2], Ws[2], F_, nullptr, nullptr, c.s));
     float* cur = S2;  // output of the previous fusion block at level L
@@ -1593,31 +1831,26 @@ wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, b
     const bool fuse_up1 = fuse_on && F_ % 64 == 0 && 4 * Hs[0] * Ws[0] >= 256;
     const bool fuse_up2 = fuse_on && !is_gs && (F_ / 2) % 64 == 0;
     // output_conv1 on the resized tensor as nine 1x1 products at the LOW resolution + a bilinear gather (upconv.hip): a quarter of the MFMA work
-    const Weight* w_oc1 = W(h, sc + "output_conv1.weight");
-    const bool gather_on = wm_tune(WM_TUNE_UP1_GATHER, 1) != 0 && c.hdt == WM_DT_F16 && w_oc1 && w_oc1->tap_major && F_ % 64 == 0 &&
-                           (int)w_oc1->shape[1] == F_ && ((int)w_oc1->shape[0] == 128 || (int)w_oc1->shape[0] == 64 || (int)w_oc1->shape[0] == 32) &&
-                           (unsigned long long)n * Hs[0] * Ws[0] * 9ull * (unsigned long long)w_oc1->shape[0] * 2ull < (1ull << 32);   // the gather's 32-bit offsets
+    const int Co1 = w.oc1.cout;
+    const bool gather_on = wm_tune(WM_TUNE_UP1_GATHER, 1) != 0 && c.hdt == WM_DT_F16 && w.oc1_tap && F_ % 64 == 0 &&
+                           w.oc1.cin == F_ && (Co1 == 128 || Co1 == 64 || Co1 == 32) &&
+                           (unsigned long long)n * Hs[0] * Ws[0] * 9ull * (unsigned long long)Co1 * 2ull < (1ull << 32);   // the gather's 32-bit offsets
     bool up1_gather = false;
-    const Up1Comp* comp = nullptr;
-    {
-      auto it = h->up1comp.find(p);
-      if (gather_on && wm_tune(WM_TUNE_UP1_COMP, 1) != 0 && it != h->up1comp.end() && it->second.w16 && it->second.co == (int)w_oc1->shape[0]) comp = &it->second;
-    }
+    const Up1Comp* comp = gather_on && wm_tune(WM_TUNE_UP1_COMP, 1) != 0 ? w.comp : nullptr;
     for (int L = 2; L >= 0; --L) {  // refinenet3 (level 2), refinenet2 (level 1), refinenet1 (level 0)
-      const std::string rp = sc + "refinenet" + std::to_string(L + 1) + ".";
       float* others[3];
       int k = 0;
       for (float* b : {S0, S1, S2, S3}) if (b != cur) others[k++] = b;
       // x = cur + RCU1(rn[L])
-      st = rcu(c, rp + "resConfUnit1.", rn[L], cur, others[0], others[1], n, Hs[L], Ws[L]);
+      st = rcu(c, w.rcu[L][0], rn[L], cur, others[0], others[1], n, Hs[L], Ws[L]);
       if (st) return st;
       // x = RCU2(x)
-      st = rcu(c, rp + "resConfUnit2.", others[1], nullptr, others[0], others[2], n, Hs[L], Ws[L], &x16);
+      st = rcu(c, w.rcu[L][1], others[1], nullptr, others[0], others[2], n, Hs[L], Ws[L], &x16);
       if (st) return st;
       const int Ho = L > 0 ? Hs[L - 1] : 2 * Hs[0], Wo = L > 0 ? Ws[L - 1] : 2 * Ws[0];
       up1_gather = L == 0 && gather_on && x16;
       if (up1_gather && comp != nullptr) { cur = others[2]; break; }   // out_conv lives inside the tap matrices: the tap GEMM reads x2 itself
-      st = out_conv(c, rp + "out_conv", others[2], x16, others[0], n, Hs[L], Ws[L], F_, up1_gather);
+      st = out_conv(c, w.out_conv[L], others[2], x16, others[0], n, Hs[L], Ws[L], F_, up1_gather);
       if (st) return st;
       if (L == 0 && (fuse_up1 || up1_gather)) { cur = others[0]; break; }  // the last resize is fused into output_conv1 (its input staging, or the tap form)
       LCHK(c, wm_launch_bilinear(others[0], others[1], n, Hs[L], Ws[L], Ho, Wo, F_, nullptr, nullptr, c.s));
@@ -1630,69 +1863,71 @@ wm_status dpt_head(Ctx& c, const std::string& p, int F_, int out_dim, int act, b
       for (float* b : {S0, S1, S2, S3}) if (b != cur) others[k++] = b;
     }
     if (up1_gather) {
-      const int Co = (int)w_oc1->shape[0];
-      const size_t numel = (size_t)Co * 9 * F_;
       void* Y1 = others[1];
-      if (comp) st = gemm(c, c.hdt, WM_EPI_T16, cur, F_, comp->w16, F_, Y1, 9 * Co, comp->bias, nullptr, n * Hs[0] * Ws[0], 9 * Co, F_, nullptr, 10);
-      else st = gemm(c, c.hdt, WM_EPI_T16, cur, F_, (const uint16_t*)w_oc1->w16 + numel, F_, Y1, 9 * Co, nullptr, nullptr, n * Hs[0] * Ws[0], 9 * Co, F_, nullptr, 10);
+      if (comp) st = gemm(c, c.hdt, WM_EPI_T16, cur, F_, comp->w16, F_, Y1, 9 * Co1, comp->bias, nullptr, n * Hs[0] * Ws[0], 9 * Co1, F_, nullptr, 10);
+      else st = gemm(c, c.hdt, WM_EPI_T16, cur, F_, w.oc1_tap, F_, Y1, 9 * Co1, nullptr, nullptr, n * Hs[0] * Ws[0], 9 * Co1, F_, nullptr, 10);
       if (!st) {
         ProfScope ps(h, 10, c.s);
-        LCHK(c, wm_launch_upconv_gather(Y1, F(h, sc + "output_conv1.bias"), others[0], n, Hs[0], Ws[0], H8, W8, Co, c.s));
+        LCHK(c, wm_launch_upconv_gather(Y1, w.oc1.bias, others[0], n, Hs[0], Ws[0], H8, W8, Co1, c.s));
       }
-    } else if (fuse_up1) st = conv(c, cur, sc + "output_conv1", true, nullptr, false, nullptr, others[0], n, H8, W8, 3, 1, 1, false, Hs[0], Ws[0]);
-    else st = conv(c, cur, sc + "output_conv1", true, nullptr, false, nullptr, others[0], n, H8, W8, 3, 1, 1, false);
+    } else {
+      WmConvArgs a = conv_args(cur, others[0], n, H8, W8, 3, 1, 1);
+      if (fuse_up1) { a.up_hs = Hs[0]; a.up_ws = Ws[0]; }
+      st = conv(c, w.oc1, a);
+    }
     if (st) return st;
     const int Ho = gh * cf.patch_size, Wo = gw * cf.patch_size;
     float* fused = others[1];
-    const float* posx = B<float>(h, is_gs ? "gs_posx" : "dpt_posx");
-    const float* posy = B<float>(h, is_gs ? "gs_posy" : "dpt_posy");
+    const float* posx = ws.posx[is_gs ? 1 : 0];
+    const float* posy = ws.posy[is_gs ? 1 : 0];
     // output_conv2[0] un-fused (measured: 16-bit LDS-tiled resize 260 us + DMA-fed 32-channel conv 255 us vs 600-630 us for the
     // fused-resize kernel at 8 views, tools/bench_up_conv_n32.py): resize into `fused` as 16-bit, conv reads it by LDS-DMA
     bool tail_done = false;
-    const Weight* w_oc2 = W(h, sc + "output_conv2.0.weight");
-    const bool up2_unfused = !is_gs && (F_ / 2) % 64 == 0 && F_ / 2 <= 128 && w_oc2 && w_oc2->shape[0] == 32 && w_oc2->w16 != nullptr;
+    const bool up2_unfused = !is_gs && (F_ / 2) % 64 == 0 && F_ / 2 <= 128 && w.oc2_0.cout == 32;
     if (up2_unfused) {
       LCHK(c, wm_launch_bilinear16(others[0], fused, n, H8, W8, Ho, Wo, F_ / 2, posx, posy, c.hdt, c.s));
       WmConvN32Args a;
       memset(&a, 0, sizeof(a));
-      a.x = (const uint16_t*)fused; a.w = (const uint16_t*)w_oc2->w16; a.bias = F(h, sc + "output_conv2.0.bias"); a.y = others[2];
-      a.zero = B<uint16_t>(h, "ZERO256"); a.N = n; a.H = Ho; a.W = Wo; a.Cin = F_ / 2; a.relu_out = 0; a.dtype = c.hdt;
+      a.x = (const uint16_t*)fused; a.w = (const uint16_t*)w.oc2_0.w16; a.bias = w.oc2_0.bias; a.y = others[2];
+      a.zero = ws.ZERO256; a.N = n; a.H = Ho; a.W = Wo; a.Cin = F_ / 2; a.relu_out = 0; a.dtype = c.hdt;
       // ... with the head's tail (ReLU, 1x1 conv 32 -> C, activations) in its epilogue: the 32-channel tensor is never stored
-      a.tail_w = F(h, sc + "output_conv2.2.weight"); a.tail_b = F(h, sc + "output_conv2.2.bias"); a.tail_C = out_dim; a.tail_act = act;
+      a.tail_w = w.oc2_2.w; a.tail_b = w.oc2_2.b; a.tail_C = out_dim; a.tail_act = act;
       a.tail_attr = out_attr + (size_t)v0 * Ho * Wo * (out_dim - 1); a.tail_conf = out_conf + (size_t)v0 * Ho * Wo;
       ProfScope ps(h, 11, c.s);
       LCHK(c, wm_launch_conv3x3_n32_in16(a, c.s));
       tail_done = true;
     } else if (fuse_up2) {  // (the GS branch also needs the resized tensor itself: input_merger accumulates into it)
-      st = conv(c, others[0], sc + "output_conv2.0", true, nullptr, false, nullptr, others[2], n, Ho, Wo, 3, 1, 1, false, H8, W8, posx, posy);
+      WmConvArgs a = conv_args(others[0], others[2], n, Ho, Wo, 3, 1, 1);
+      a.up_hs = H8; a.up_ws = W8; a.up_addx = posx; a.up_addy = posy;
+      st = conv(c, w.oc2_0, a);
     } else {
       LCHK(c, wm_launch_bilinear(others[0], fused, n, H8, W8, Ho, Wo, F_ / 2, posx, posy, c.s));
-      st = conv(c, fused, sc + "output_conv2.0", true, nullptr, false, nullptr, others[2], n, Ho, Wo, 3, 1, 1, false);
+      st = conv(c, w.oc2_0, conv_args(fused, others[2], n, Ho, Wo, 3, 1, 1));
     }
     if (st) return st;
     const size_t npix = (size_t)n * Ho * Wo, voff = (size_t)v0 * Ho * Wo;
     if (!tail_done)
-      LCHK(c, wm_launch_dpt_tail(others[2], F(h, sc + "output_conv2.2.weight"), F(h, sc + "output_conv2.2.bias"),
-                                 out_attr + voff * (out_dim - 1), out_conf + voff, npix, out_dim, act, c.s));
+      LCHK(c, wm_launch_dpt_tail(others[2], w.oc2_2.w, w.oc2_2.b, out_attr + voff * (out_dim - 1), out_conf + voff, npix, out_dim, act, c.s));
     if (is_gs && out->splat_means) {
       // dense_head.py:232-244: fused += ReLU(conv7x7(img)); then GaussianSplatRenderer.gs_head
       // (rasterization.py:149-153): conv3x3 (no bias) -> ReLU -> conv1x1 -> 12 raw parameters per pixel
       const float* img_c = img + (size_t)v0 * 3 * Ho * Wo;
-      void* col = B<void>(h, "gs_im2col");
+      void* col = ws.gs_im2col;
       LCHK(c, wm_launch_im2col7(img_c, col, n, Ho, Wo, 192, c.hdt, c.s));
       WmGemmArgs ex;
       memset(&ex, 0, sizeof(ex));
       ex.rows_per_group = (int)npix; ex.accumulate = 1; ex.relu = 1;
-      st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, col, 192, W16(h, p + "input_merger.0.weight"), 192, fused, F_ / 2,
-                F(h, p + "input_merger.0.bias"), nullptr, (int)npix, F_ / 2, 192, &ex);
+      st = gemm(c, c.hdt, WM_EPI_ROWMAP_ADD, col, 192, w.merger.w, 192, fused, F_ / 2, w.merger.b, nullptr, (int)npix, F_ / 2, 192, &ex);
       if (st) return st;
       float* X = others[0];   // [n][H][W][gs_dim]
       float* gp = others[2];  // [n*H*W][12] (y32 is dead after the tail)
-      st = conv(c, fused, "gs_renderer.gs_head.0", false, nullptr, false, nullptr, X, n, Ho, Wo, 3, 1, 1, false);
+      st = conv(c, w.gs0, conv_args(fused, X, n, Ho, Wo, 3, 1, 1));
       if (st) return st;
-      st = conv(c, X, "gs_renderer.gs_head.2", true, nullptr, false, nullptr, gp, n, Ho, Wo, 1, 1, 0, true);
+      WmConvArgs a = conv_args(X, gp, n, Ho, Wo, 1, 1, 0);
+      a.relu_in = 1;
+      st = conv(c, w.gs2, a);
       if (st) return st;
-      LCHK(c, wm_launch_gs_splat(gp, img_c, out_attr + voff, B<float>(h, "cam_params") + (size_t)(first_view + v0) * 9,
+      LCHK(c, wm_launch_gs_splat(gp, img_c, out_attr + voff, ws.cam_params + (size_t)(first_view + v0) * 9,
                                  out->splat_means + voff * 3, out->splat_quats + voff * 4, out->splat_scales + voff * 3,
                                  out->splat_opacities + voff, out->splat_sh + voff * 3, out->splat_weights + voff, n, Ho, Wo, c.s));
     }
@@ -1717,84 +1952,85 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
   wm_status st = WM_OK;
   for (int k = 0; k < wm_handle::NKIND; ++k) h->ev_used[k] = 0;
   ProfScope whole(h, 4, s);
-  HIPCHK(h, hipMemsetAsync(B<char>(h, "ZERO256"), 0, 256, s));
+  const Model& m = h->m;
+  const Workspace& ws = h->ws;
+  HIPCHK(h, hipMemsetAsync(ws.ZERO256, 0, 256, s));
   const int D = d.D;
-  const std::string v = "visual_geometry_transformer.", dn = v + "patch_embed.";
-  float* Xd = B<float>(h, "Xd");
-  float* Xv = B<float>(h, "Xv");
-  void* A16 = B<void>(h, "A16");
+  float* Xd = ws.Xd;
+  float* Xv = ws.Xv;
+  void* A16 = ws.A16;
 
   // ---- a3/a4: normalise + patchify + DINOv2 encoder (vision_transformer.py:209-266)
   LCHK(c, wm_launch_im2col(img, A16, n, 3, H, W_, cf.patch_size, d.kpad_patch, 1, c.bdt, s));
   {
     WmGemmArgs ex;
     memset(&ex, 0, sizeof(ex));
-    ex.rows_per_group = d.hw; ex.out_group = d.Td; ex.out_off = 1 + d.R; ex.add = B<float>(h, "dino_pos") + D;
-    st = gemm(c, c.bdt, WM_EPI_ROWMAP_ADD, A16, d.kpad_patch, W16(h, dn + "patch_embed.proj.weight"), d.kpad_patch, Xd, D,
-              F(h, dn + "patch_embed.proj.bias"), nullptr, n * d.hw, D, d.kpad_patch, &ex);
+    ex.rows_per_group = d.hw; ex.out_group = d.Td; ex.out_off = 1 + d.R; ex.add = ws.dino_pos + D;
+    st = gemm(c, c.bdt, WM_EPI_ROWMAP_ADD, A16, d.kpad_patch, m.patch_proj.w, d.kpad_patch, Xd, D, m.patch_proj.b, nullptr, n * d.hw, D, d.kpad_patch, &ex);
     if (st) return st;
   }
-  LCHK(c, wm_launch_dino_tokens(nullptr, F(h, dn + "cls_token"), F(h, dn + "register_tokens"), B<float>(h, "dino_pos"), Xd, n, d.hw, d.R, D, s));
+  LCHK(c, wm_launch_dino_tokens(nullptr, m.cls_token, m.register_tokens, ws.dino_pos, Xd, n, d.hw, d.R, D, s));
   {
     bool ln1 = false;
     for (int i = 0; i < cf.dino_depth; ++i) {
-      const std::string nxt = i + 1 < cf.dino_depth ? dn + "blocks." + std::to_string(i + 1) + "." : std::string();
-      st = backbone_block(c, dn + "blocks." + std::to_string(i) + ".", Xd, d.Md, d.Td, cf.dino_heads, 1e-6f, false, false, d.Td, 0, false, nullptr, ln1, nxt, &ln1);
+      const Norm* nxt = i + 1 < cf.dino_depth ? &m.dino[i + 1].norm1 : nullptr;
+      st = backbone_block(c, m.dino[i], Xd, d.Md, d.Td, cf.dino_heads, 1e-6f, false, d.Td, 0, false, nullptr, ln1, nxt, &ln1);
       if (st) return st;
     }
   }
   // final LN, patch tokens only, straight into the multi-view token buffer
-  st = layernorm(c, Xd, D, Xv, D, F(h, dn + "norm.weight"), F(h, dn + "norm.bias"), D, 1e-6f, n, d.hw, d.Td, 1 + d.R, d.P, d.psi, 1, 0);
-  if (st) return st;
+  {
+    WmLnArgs ln{};
+    ln.x = Xd; ln.ld_in = D; ln.y = Xv; ln.ld_out = D; ln.w = m.dino_norm.w; ln.b = m.dino_norm.b; ln.D = D; ln.eps = 1e-6f;
+    ln.groups = n; ln.rows_per_group = d.hw; ln.in_group = d.Td; ln.in_off = 1 + d.R; ln.out_group = d.P; ln.out_off = d.psi; ln.out_f32 = 1;
+    st = layernorm(c, ln);
+    if (st) return st;
+  }
 
   // ---- a5: special + prior tokens (visual_transformer.py:285-295,343-371)
   const float* pose_tok = nullptr; const float* ray_tok = nullptr;
   if (cf.enable_cond) {
-    float* pin = B<float>(h, "pr_in"); float* ph = B<float>(h, "pr_h");
+    float* pin = ws.pr_in; float* ph = ws.pr_h;
     if (flags && flags[0] == 1 && pose7) {
       LCHK(c, hipMemcpy2DAsync(pin, 8 * 4, pose7, 7 * 4, 7 * 4, n, hipMemcpyDeviceToDevice, s));
-      st = linear32(c, pin, 8, v + "pose_embed.0", ph, D, n, 0, 1);
+      st = linear32(c, pin, 8, m.pose_embed[0], ph, D, n, 0, 1);
       if (st) return st;
-      st = linear32(c, ph, D, v + "pose_embed.2", B<float>(h, "pose_tok"), D, n, 0, 0);
+      st = linear32(c, ph, D, m.pose_embed[1], ws.pose_tok, D, n, 0, 0);
       if (st) return st;
-      pose_tok = B<float>(h, "pose_tok");
+      pose_tok = ws.pose_tok;
     }
     if (flags && flags[2] == 1 && ray4) {
-      st = linear32(c, ray4, 4, v + "ray_embed.0", ph, D, n, 0, 1);
+      st = linear32(c, ray4, 4, m.ray_embed[0], ph, D, n, 0, 1);
       if (st) return st;
-      st = linear32(c, ph, D, v + "ray_embed.2", B<float>(h, "ray_tok"), D, n, 0, 0);
+      st = linear32(c, ph, D, m.ray_embed[1], ws.ray_tok, D, n, 0, 0);
       if (st) return st;
-      ray_tok = B<float>(h, "ray_tok");
+      ray_tok = ws.ray_tok;
     }
     if (flags && flags[1] == 1 && depth) {  // PatchEmbed_Mlp (patch_embed.py:79-93): unshuffle -> fc1 -> GELU -> fc2, added to patches
       LCHK(c, wm_launch_im2col(depth, A16, n, 1, H, W_, cf.patch_size, d.kpad_depth, 0, c.bdt, s));
-      void* H16 = B<void>(h, "H16");
-      st = gemm(c, c.bdt, WM_EPI_GELU_T16, A16, d.kpad_depth, W16(h, v + "depth_embed.proj.2.fc1.weight"), d.kpad_depth, H16, 4 * D,
-                F(h, v + "depth_embed.proj.2.fc1.bias"), nullptr, n * d.hw, 4 * D, d.kpad_depth);
+      void* H16 = ws.H16;
+      st = gemm(c, c.bdt, WM_EPI_GELU_T16, A16, d.kpad_depth, m.depth_fc1.w, d.kpad_depth, H16, 4 * D, m.depth_fc1.b, nullptr, n * d.hw, 4 * D, d.kpad_depth);
       if (st) return st;
       WmGemmArgs ex;
       memset(&ex, 0, sizeof(ex));
       ex.rows_per_group = d.hw; ex.out_group = d.P; ex.out_off = d.psi; ex.accumulate = 1;
-      st = gemm(c, c.bdt, WM_EPI_ROWMAP_ADD, H16, 4 * D, W16(h, v + "depth_embed.proj.2.fc2.weight"), 4 * D, Xv, D,
-                F(h, v + "depth_embed.proj.2.fc2.bias"), nullptr, n * d.hw, D, 4 * D, &ex);
+      st = gemm(c, c.bdt, WM_EPI_ROWMAP_ADD, H16, 4 * D, m.depth_fc2.w, 4 * D, Xv, D, m.depth_fc2.b, nullptr, n * d.hw, D, 4 * D, &ex);
       if (st) return st;
     }
   }
-  LCHK(c, wm_launch_vgt_special(Xv, F(h, v + "cam_token"), F(h, v + "reg_token"), pose_tok, ray_tok, n, d.P, d.R, D, cf.enable_cond, first_view, s));
+  LCHK(c, wm_launch_vgt_special(Xv, m.cam_token, m.reg_token, pose_tok, ray_tok, n, d.P, d.R, D, cf.enable_cond, first_view, s));
 
   // ---- a7-a10: 24 x (frame block, global block) + taps (visual_transformer.py:309-339)
   int tap_i = 0;
   bool vgt_ln1 = false;   // A16 already holds the coming block's norm1(X): the previous block's fc2 epilogue wrote it
   for (int i = 0; i < cf.depth; ++i) {
     const bool is_tap = tap_i < 4 && i == cf.intermediate_idxs[tap_i];
-    float* tap = is_tap ? B<float>(h, ("tap" + std::to_string(tap_i)).c_str()) : nullptr;
+    float* tap = is_tap ? ws.tap[tap_i] : nullptr;
     // (frame and global blocks alternate on the same token buffer: each block's fc2 epilogue computes the next block's norm1)
-    const std::string gname = v + "global_blocks." + std::to_string(i) + ".";
-    const std::string fnext = i + 1 < cf.depth ? v + "frame_blocks." + std::to_string(i + 1) + "." : std::string();
-    st = backbone_block(c, v + "frame_blocks." + std::to_string(i) + ".", Xv, d.Mv, d.P, cf.num_heads, 1e-5f, true, true, d.P, d.psi, false, tap,
-                        vgt_ln1, gname, &vgt_ln1);
+    const Norm* fnext = i + 1 < cf.depth ? &m.frame[i + 1].norm1 : nullptr;
+    st = backbone_block(c, m.frame[i], Xv, d.Mv, d.P, cf.num_heads, 1e-5f, true, d.P, d.psi, false, tap, vgt_ln1, &m.global[i].norm1, &vgt_ln1);
     if (st) return st;
-    st = backbone_block(c, gname, Xv, d.Mv, d.Mv, cf.num_heads, 1e-5f, true, true, d.P, d.psi, true, tap ? tap + D : nullptr, vgt_ln1, fnext, &vgt_ln1);
+    st = backbone_block(c, m.global[i], Xv, d.Mv, d.Mv, cf.num_heads, 1e-5f, true, d.P, d.psi, true, tap ? tap + D : nullptr, vgt_ln1, fnext, &vgt_ln1);
     if (st) return st;
     if (is_tap) {
       if (out->taps[tap_i]) LCHK(c, hipMemcpyAsync(out->taps[tap_i], tap, (size_t)d.Mv * 2 * D * 4, hipMemcpyDeviceToDevice, s));
@@ -1803,7 +2039,7 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
   }
 
   // fallback statistics of the fast attention kernels -> pinned host mirror (read by the NEXT forwards' launch policy; no synchronisation)
-  if (h->att_stat_host) LCHK(c, hipMemcpyAsync(h->att_stat_host, B<int>(h, "ATT_STAT"), (size_t)h->att_stat_n * 4, hipMemcpyDeviceToHost, s));
+  if (h->att_stat_host) LCHK(c, hipMemcpyAsync(h->att_stat_host, ws.ATT_STAT, (size_t)h->att_stat_n * 4, hipMemcpyDeviceToHost, s));
 
   // The camera head and the DPT heads are independent of each other: each runs on one of the handle's own queues, forked from and
   // joined back to the caller's stream (-1.15 ms per forward at 8 x 518^2, -5 ms at 32 views: the HBM-bound camera head and the under-filled small DPT
@@ -1833,25 +2069,25 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
       LCHK(c, hipStreamWaitEvent(cc.s, h->hfork, 0));
       cam_async = true;
     }
-    st = camera_head(cc, B<float>(h, "cam_params"));
+    st = camera_head(cc, ws.cam_params);
     if (st) return st;
-    LCHK(c, hipMemcpyAsync(out->camera_params, B<float>(h, "cam_params"), (size_t)nt * 9 * 4, hipMemcpyDeviceToDevice, cc.s));
+    LCHK(c, hipMemcpyAsync(out->camera_params, ws.cam_params, (size_t)nt * 9 * 4, hipMemcpyDeviceToDevice, cc.s));
     if (out->camera_poses && out->camera_intrs)
-      LCHK(c, wm_launch_cam_matrices(B<float>(h, "cam_params"), out->camera_poses, out->camera_intrs, nt, H, W_, cc.s));
+      LCHK(c, wm_launch_cam_matrices(ws.cam_params, out->camera_poses, out->camera_intrs, nt, H, W_, cc.s));
     if (cam_async) LCHK(c, hipEventRecord(h->camjoin, cc.s));
   }
   // ---- a13: DPT heads (worldmirror.py:74-98): independent of each other; one per queue unless tuning heads_concurrent = 0 (see above).
   {
-    struct HeadJob { const char* p; int F; int od; int act; bool gs; float* attr; float* conf; };
+    struct HeadJob { int id; int F; int od; int act; float* attr; float* conf; };   // id: which head (HeadId); its index in jobs is its workspace slot
     std::vector<HeadJob> jobs;
-    if (cf.enable_depth && out->depth && out->depth_conf) jobs.push_back({"depth_head.", cf.dpt_features, 2, WM_ACT_EXP, false, out->depth, out->depth_conf});
-    if (cf.enable_pts && out->pts3d && out->pts3d_conf) jobs.push_back({"pts_head.", cf.dpt_features, 4, WM_ACT_INV_LOG, false, out->pts3d, out->pts3d_conf});
-    if (cf.enable_norm && out->normals && out->normals_conf) jobs.push_back({"norm_head.", cf.dpt_features, 4, WM_ACT_NORM, false, out->normals, out->normals_conf});
+    if (cf.enable_depth && out->depth && out->depth_conf) jobs.push_back({HD_DEPTH, cf.dpt_features, 2, WM_ACT_EXP, out->depth, out->depth_conf});
+    if (cf.enable_pts && out->pts3d && out->pts3d_conf) jobs.push_back({HD_PTS, cf.dpt_features, 4, WM_ACT_INV_LOG, out->pts3d, out->pts3d_conf});
+    if (cf.enable_norm && out->normals && out->normals_conf) jobs.push_back({HD_NORM, cf.dpt_features, 4, WM_ACT_NORM, out->normals, out->normals_conf});
     if (cf.enable_gs && out->gs_depth && out->gs_depth_conf) {
       if (out->splat_means && !(out->splat_quats && out->splat_scales && out->splat_opacities && out->splat_sh && out->splat_weights))
         return fail(h, WM_ERR_INVALID, "splat outputs must be given together");
       if (out->splat_means && !(cf.enable_cam && out->camera_params)) return fail(h, WM_ERR_INVALID, "splats need the camera head");
-      jobs.push_back({"gs_head.", cf.gs_dim, 2, WM_ACT_EXP, true, out->gs_depth, out->gs_depth_conf});
+      jobs.push_back({HD_GS, cf.gs_dim, 2, WM_ACT_EXP, out->gs_depth, out->gs_depth_conf});
     }
     // Round 4: the LAST head runs on the caller's stream itself and only the others fork.  HIP multiplexes streams onto four hardware
     // queues: with every head on a stream of its own (three heads + the camera head + the caller's idle stream) two DPT heads shared
@@ -1861,8 +2097,8 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
     // The heads' front — LayerNorm of each tap and its 1x1 projection — once for all heads on the caller's stream (tuning tap_shared = 0: every
     // head normalises and projects for itself).  Taken when the folded weights exist (wm_reserve: two or more heads, in range) and the call
     // runs exactly the group's heads, whose order numbers the workspace slots.
-    bool front = wm_tune(WM_TUNE_TAP_SHARED, 1) != 0 && h->tapfold.valid && h->tapfold.heads.size() == jobs.size();
-    for (size_t k = 0; front && k < jobs.size(); ++k) front = h->tapfold.heads[k] == jobs[k].p;
+    bool front = wm_tune(WM_TUNE_TAP_SHARED, 1) != 0 && h->tapfold.valid && (size_t)h->tapfold.nh == jobs.size();
+    for (size_t k = 0; front && k < jobs.size(); ++k) front = h->tapfold.heads[k] == jobs[k].id;
     if (front) {
       st = tap_front(c);
       if (st) return st;
@@ -1875,8 +2111,8 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
     auto run_head = [&](size_t k, hipStream_t hs) -> wm_status {
       Ctx hc = c;
       hc.s = hs;
-      if (jobs[k].gs && cam_async) LCHK(c, hipStreamWaitEvent(hs, h->camjoin, 0));  // the splats are unprojected with the predicted cameras
-      return dpt_head(hc, jobs[k].p, jobs[k].F, jobs[k].od, jobs[k].act, jobs[k].gs, jobs[k].attr, jobs[k].conf, img, out, first_view, (int)k, front);
+      if (jobs[k].id == HD_GS && cam_async) LCHK(c, hipStreamWaitEvent(hs, h->camjoin, 0));  // the splats are unprojected with the predicted cameras
+      return dpt_head(hc, jobs[k].id, jobs[k].F, jobs[k].od, jobs[k].act, jobs[k].attr, jobs[k].conf, img, out, first_view, (int)k, front);
     };
     const bool fork_heads = !serial && (jobs.size() > 1 || cam_async);
     for (size_t k = 0; k < jobs.size(); ++k) {
@@ -1926,8 +2162,7 @@ extern "C" wm_status wm_set_workspace(wm_handle* h, void* device_ptr, size_t byt
   h->arena = (char*)device_ptr;
   h->arena_bytes = device_ptr ? bytes : 0;
   h->arena_owned = device_ptr == nullptr;  // NULL hands the arena back to the library
-  h->plan_n = -1;
-  h->buf.clear();
+  h->plan_n = -1;   // (the bound workspace pointers go with the plan)
   return WM_OK;
 }
 
@@ -2061,7 +2296,10 @@ extern "C" wm_status wm_op_dpt_tap_front(int dtype, const float* tap, int n, int
     if (hipMemcpy(gw, norm_w[k], (size_t)D2 * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(gb, norm_b[k], (size_t)D2 * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(pb, proj_b[k], (size_t)oc * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(w16, r.data(), r.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
       return finish(WM_ERR_HIP);
-    wm_status st = layernorm(c, tap, D2, xhat, D2, gw, gb, D2, 1e-5f, n, hw, P, psi, hw, 0, 0, dtype);
+    WmLnArgs ln{};
+    ln.x = tap; ln.ld_in = D2; ln.y = xhat; ln.ld_out = D2; ln.w = gw; ln.b = gb; ln.D = D2; ln.eps = 1e-5f;
+    ln.groups = n; ln.rows_per_group = hw; ln.in_group = P; ln.in_off = psi; ln.out_group = hw; ln.dtype = dtype;
+    wm_status st = layernorm(c, ln);
     if (st) return finish(st);
     WmGemmArgs ex;
     memset(&ex, 0, sizeof(ex));

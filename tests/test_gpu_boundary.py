@@ -157,3 +157,98 @@ def test_batch_of_two_equals_two_forwards():
         assert ab[k].shape[0] == 2 and torch.equal(ab[k][0:1], a[k]) and torch.equal(ab[k][1:2], b[k]), k
     if "splats" in ab:
         assert len(ab["splats"]["means"]) == 2 and torch.equal(ab["splats"]["means"][1], b["splats"]["means"][0])
+
+
+# ---- the index spaces of the bound model: head identity vs workspace slot, shape vs plan, tensor vs handle
+_HEAD_FIELDS = {"depth": ("depth", "depth_conf", 1), "pts": ("pts3d", "pts3d_conf", 3), "norm": ("normals", "normals_conf", 3)}
+
+
+def _raw_forward(m, img, fields):
+    """wm_forward on the model's handle with only `fields` of wm_outputs set (the workspace must be reserved)."""
+    from hunyuanworld_mirror_amd import _lib
+    n, _, H, W = img.shape
+    shapes = {"camera_params": (1, n, 9)}
+    for attr, conf, ch in _HEAD_FIELDS.values():
+        shapes[attr], shapes[conf] = (1, n, H, W, ch), (1, n, H, W)
+    o, res = _lib.wm_outputs(), {}
+    for f in fields:
+        res[f] = torch.full(shapes[f], float("nan"), device="cuda")
+        setattr(o, f, res[f].data_ptr())
+    fl = (C.c_int32 * 3)(0, 0, 0)
+    st = _lib.lib().wm_forward(m._handle, _lib.ptr(img), n, H, W, None, None, None, fl, C.byref(o), None)
+    assert st == 0, m._err()
+    torch.cuda.synchronize()
+    return res
+
+
+def test_subset_of_heads_runs_at_slot_zero():
+    """A call that asks for one DPT head (plus the camera) runs that head in workspace slot 0, whichever head it is: with every head
+    on the direct tap front (tap_shared = 0) its outputs are bit for bit those of the call with all heads; with the default tuning the
+    full call takes the shared front and the subset call the direct one, so the subset stays within test_tiny_golden's tolerance."""
+    from hunyuanworld_mirror_amd import WorldMirror, _lib
+    cfg, views, flags, outs, z = load_golden("tiny_2v_70x70_noprior")
+    assert cfg.enable_depth and cfg.enable_pts and cfg.enable_norm
+    m = WorldMirror(arch=cfg).init_synthetic_weights().to("cuda:0")
+    L = _lib.lib()
+    img = torch.from_numpy(views["img"])[0].cuda().contiguous()
+    try:
+        assert L.wm_set_tuning(b"tap_shared", 0) == 0
+        full = {k: v.clone() for k, v in m(_views(views), flags).items()}
+        torch.cuda.synchronize()
+        for attr, conf, _ in _HEAD_FIELDS.values():
+            got = _raw_forward(m, img, ("camera_params", attr, conf))
+            assert torch.equal(got[attr], full[attr]), attr
+            assert torch.equal(got[conf], full[conf]), conf
+            assert torch.equal(got["camera_params"], full["camera_params"])
+    finally:
+        L.wm_set_tuning(b"tap_shared", -1)
+    for attr, conf, _ in _HEAD_FIELDS.values():
+        got = _raw_forward(m, img, ("camera_params", attr, conf))
+        for k in (attr, conf, "camera_params"):
+            e = rel_l2(got[k].cpu().numpy(), outs[k])
+            print(f"subset call, default tuning: {k} vs golden {e:.2e}")
+            assert e < 2e-2, (k, e)                         # GROSS of tests/test_gpu_e2e.py::test_tiny_golden
+
+
+def test_replan_on_a_live_handle():
+    """70 x 70, then 70 x 56 with other views and priors, then 70 x 70 again on ONE handle: every plan binds the workspace of its own
+    shape, so the third result is the first and the second is a fresh model's."""
+    from hunyuanworld_mirror_amd import WorldMirror
+    cfg, views_b, flags_b, _, _ = load_golden("tiny_3v_70x56_pose_ray")
+    cfg_a, views_a, flags_a, _, _ = load_golden("tiny_2v_70x70_noprior")
+    assert cfg_a.to_dict() == cfg.to_dict()
+    ta, tb = _views(views_a), _views(views_b)
+    keys = ("pts3d", "depth", "normals", "camera_params")
+    m = WorldMirror(arch=cfg).init_synthetic_weights().to("cuda:0")
+    first = {k: v.clone() for k, v in m(ta, flags_a).items()}
+    second = {k: v.clone() for k, v in m(tb, flags_b).items()}
+    third = m(ta, flags_a)
+    fresh = WorldMirror(arch=cfg).init_synthetic_weights().to("cuda:0")(tb, flags_b)
+    torch.cuda.synchronize()
+    for k in keys:
+        assert torch.equal(third[k], first[k]), k
+        assert torch.equal(second[k], fresh[k]), k
+
+
+@pytest.mark.parametrize("name", ["visual_geometry_transformer.frame_blocks.0.ls1.gamma", "pts_head.scratch.output_conv1.bias"])
+def test_one_tensor_reloaded_on_a_live_handle(name):
+    """load_state_dict of ONE tensor on a live handle (the other tensors keep their device copies): the next forward is the forward
+    of a fresh model built from the whole changed state."""
+    from hunyuanworld_mirror_amd import WorldMirror
+    from hunyuanworld_mirror_amd.weights import iter_params
+    cfg, views, flags, outs, z = load_golden("tiny_2v_70x70_noprior")
+    tv = _views(views)
+    state = dict(iter_params(cfg))
+    m = WorldMirror(arch=cfg).to("cuda:0").init_synthetic_weights()   # on the device first: the model keeps no host copy to re-upload
+    before = {k: v.clone() for k, v in m(tv, flags).items()}
+    state[name] = (state[name] * 2.0 + 0.05).astype(np.float32)
+    missing, unexpected = m.load_state_dict({name: state[name]})
+    assert not unexpected and m.missing_weights == 0
+    after = m(tv, flags)
+    fresh = WorldMirror(arch=cfg)
+    fresh.load_state_dict(state)
+    ref = fresh.to("cuda:0")(tv, flags)
+    torch.cuda.synchronize()
+    for k in ("pts3d", "depth", "normals", "camera_params"):
+        assert torch.equal(after[k], ref[k]), k
+    assert not torch.equal(after["pts3d"], before["pts3d"])
