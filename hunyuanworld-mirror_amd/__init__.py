@@ -14,3 +14,5 @@ from .pose import CameraOptModule  # noqa: F401
 from .exporter import export_splats, load_gaussian_ply, process_ply_to_splat, save_gs_ply, splats_from_ply  # noqa: F401
 from .colmap import colmap_points_from_depth, load_colmap, save_colmap, save_points_ply, save_scene_ply  # noqa: F401
 from .splat_init import create_splats_with_optimizers, knn, knn_scales, rgb_to_sh  # noqa: F401
+from .video import (GSEffects, depth_frames, interpolate_trajectory, quaternion_to_rotation_matrix, render_interpolated_frames,  # noqa: F401
+                    render_interpolated_video, rgb_frames, rotation_matrix_to_quaternion, slerp_quaternions, wobble_trajectory)

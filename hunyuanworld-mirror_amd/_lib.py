@@ -77,6 +77,7 @@ EXPORTS = [
     "wm_colmap_select_workspace_bytes", "wm_colmap_select", "wm_colmap_gather", "wm_colmap_pack_workspace_bytes", "wm_colmap_pack",
     "wm_pack_point_ply_workspace_bytes", "wm_pack_point_ply",
     "wm_knn_workspace_bytes", "wm_knn",
+    "wm_gs_effect_spread_workspace_bytes", "wm_gs_effect_spread", "wm_video_frames_workspace_bytes", "wm_video_frames", "wm_turbo_lut",
 ]
 
 _lib = None
@@ -243,6 +244,14 @@ def lib() -> C.CDLL:
     L.wm_knn_workspace_bytes.argtypes = [i64, i32]
     L.wm_knn_workspace_bytes.restype = C.c_size_t
     L.wm_knn.argtypes = [vp, i64, i32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.wm_gs_effect_spread_workspace_bytes.argtypes = [i64]
+    L.wm_gs_effect_spread_workspace_bytes.restype = C.c_size_t
+    L.wm_gs_effect_spread.argtypes = [vp, vp, vp, vp, vp, i64, f64, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.wm_video_frames_workspace_bytes.argtypes = [i32, i32, i32]
+    L.wm_video_frames_workspace_bytes.restype = C.c_size_t
+    L.wm_video_frames.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.wm_turbo_lut.argtypes = [vp]
+    L.wm_turbo_lut.restype = None
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
     L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t

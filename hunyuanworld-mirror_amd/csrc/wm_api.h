@@ -31,3 +31,17 @@ hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors,
 // No synchronisation.  1 <= K <= 16, K <= N < 2^31.
 size_t wm_knn_ws_bytes(long long N, int K);      // 0 for sizes the launcher refuses
 hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspace, float* dist, int* idx, int* nonfinite_flag, hipStream_t s);
+
+// ------------------------------------------------------------------ fly-through video (video.hip), entries in wm_api_scene.cpp
+// GSEffects.apply_effect, effect_type 2, on (means - shift) * inv_scale, scales * inv_scale and rgb or degree-0 SH colours; shift [3] on the
+// device or null.  stats (device, 2 doubles): the count of flag < 0.99 and the sum of flag.  No synchronisation.  N < 2^31.
+size_t wm_gs_effect_ws_bytes(long long N);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_gs_effect_spread(const float* means, const float* scales, const float* opacities, const float* colors, const float* random_vals,
+                                      long long N, double t_n, int ignore_scale, const float* shift, float inv_scale, int colors_are_sh0,
+                                      float* out_means, float* out_scales, float* out_opacities, float* out_colors, float* flag, double* stats,
+                                      void* workspace, hipStream_t s);
+// rgbs [F,H,W,3] -> rgb_out u8 and / or depths [F,H,W] -> depth_out [F,H,W,3] u8 (turbo) + near_far [F,2]; either input may be null
+size_t wm_video_frames_ws_bytes(int F, int H, int W);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_video_frames(const float* rgbs, const float* depths, int F, int H, int W, unsigned char* rgb_out, unsigned char* depth_out,
+                                  float* near_far, void* workspace, hipStream_t s);
+void wm_turbo_lut_bytes(unsigned char* out);      // host: the 256 x 3 table

@@ -1,6 +1,6 @@
 // Scene-level entries of the C ABI (include/wm_hip.h): the caller's steps on either side of the forward, each with its *_workspace_bytes.
 // In file order: splat pruning, the rasteriser, densification, MCMC, the photometric loss, the bilateral grid, the appearance module, the
-// depth loss and point projection, then image ingest and the point masks, the COLMAP hand-off and the nearest neighbours.  Each entry
+// depth loss and point projection, then image ingest and the point masks, the COLMAP hand-off, the nearest neighbours and the fly-through video.  Each entry
 // checks its arguments, fills its launcher's args struct, launches on the caller's stream and maps the hipError_t.
 #include <hip/hip_runtime.h>
 
@@ -604,4 +604,30 @@ extern "C" wm_status wm_knn(const float* points, int64_t N, int K, void* workspa
   const size_t need = wm_knn_ws_bytes(N, K);
   if (need == 0 || !points || !workspace || workspace_bytes < need || !dist || !nonfinite_flag) return WM_ERR_INVALID;
   return wm_status_of(wm_launch_knn(points, N, K, workspace, dist, idx, nonfinite_flag, (hipStream_t)stream));
+}
+
+// ---------------------------------------------------------------- fly-through video (video.hip)
+extern "C" size_t wm_gs_effect_spread_workspace_bytes(int64_t N) { return wm_gs_effect_ws_bytes(N); }
+// replaces src/utils/gs_effects.py:162-242 (apply_effect, effect_type 2) with src/utils/render_utils.py:230-234 around it (the shift and
+// scale of the pruned splats, SH2RGB / RGB2SH) and the two reductions of :228 and :281
+extern "C" wm_status wm_gs_effect_spread(const float* means, const float* scales, const float* opacities, const float* colors,
+                                         const float* random_vals, int64_t N, double t_n, int ignore_scale, const float* shift, float inv_scale,
+                                         int colors_are_sh0, float* out_means, float* out_scales, float* out_opacities, float* out_colors,
+                                         float* flag, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const size_t need = wm_gs_effect_ws_bytes(N);
+  if (need == 0 || !workspace || workspace_bytes < need || !stats || !(t_n == t_n)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_gs_effect_spread(means, scales, opacities, colors, random_vals, N, t_n, ignore_scale, shift, inv_scale, colors_are_sh0,
+                                                 out_means, out_scales, out_opacities, out_colors, flag, stats, workspace, (hipStream_t)stream));
+}
+extern "C" size_t wm_video_frames_workspace_bytes(int F, int H, int W) { return wm_video_frames_ws_bytes(F, H, W); }
+// replaces src/utils/render_utils.py:326-357 (depth_vis per frame with src/utils/color_map.py:11-29, and _make_video's clamp * 255 -> uint8)
+extern "C" wm_status wm_video_frames(const float* rgbs, const float* depths, int F, int H, int W, unsigned char* rgb_out, unsigned char* depth_out,
+                                     float* near_far, void* workspace, size_t workspace_bytes, void* stream) {
+  const size_t need = wm_video_frames_ws_bytes(F, H, W);
+  if (need == 0 || (!rgbs && !depths)) return WM_ERR_INVALID;
+  if (depths && (!workspace || workspace_bytes < need)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_video_frames(rgbs, depths, F, H, W, rgb_out, depth_out, near_far, workspace, (hipStream_t)stream));
+}
+extern "C" void wm_turbo_lut(unsigned char out[768]) {
+  if (out) wm_turbo_lut_bytes(out);
 }

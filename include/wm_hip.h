@@ -861,6 +861,43 @@ size_t wm_knn_workspace_bytes(int64_t N, int K);
 wm_status wm_knn(const float* points, int64_t N, int K, void* workspace, size_t workspace_bytes, float* dist, int32_t* idx,
                  int32_t* nonfinite_flag, void* stream);
 
+/* ---- fly-through video around the rasteriser (csrc/video.hip): what src/utils/render_utils.py:196-368 render_interpolated_video runs per frame
+ * beside rasterize_batches.
+ *
+ * wm_gs_effect_spread: GSEffects.apply_effect with effect_type 2 (src/utils/gs_effects.py:162-242) in one pass, with the driver's composition
+ * of render_utils.py:230-234 folded in.  means / scales / colors [N,3], opacities / random_vals [N], all contiguous fp32 on the device.
+ * Positions enter as (means - shift) * inv_scale and scales as scales * inv_scale (shift: 3 floats ON THE DEVICE, or NULL for none; inv_scale 1
+ * for none); colors_are_sh0 != 0: colors are degree-0 SH, converted by sh * C0 + 0.5 on the way in and (rgb - 0.5) / C0 on the way out
+ * (C0 = 0.28209479177387814).  t_n is the reference's normalized_t = t - start_time; its host scalars (s = smoothstep of t_n - 3.2 times 10,
+ * t_n - 3.1416) are taken in fp64 as Python takes them and then used in fp32 as the tensor operations use them.  Outputs: out_means,
+ * out_scales, out_colors [N,3], out_opacities [N] and flag [N] = the reference's smoothstep_val; with ignore_scale the scale mix and the
+ * random mask (random_vals < 0.8 flag, which zeroes means, scales and opacities) are skipped.  The noise term of gs_effects.py:211-218 is not
+ * evaluated: the reference multiplies it by 0.0, so it shows only for non-finite positions, which are out of contract.
+ * stats (device, 2 doubles, written by the call): [0] the number of flag < 0.99 (render_utils.py:228), [1] the sum of flag in fp64
+ * (render_utils.py:281 takes its mean), both by a fixed-order two-stage reduction: the same input gives the same bits.  No synchronisation.
+ * Not built: the trainer-parametrised output of render_utils.py:236-241 (log scales, logit opacities).
+ * WM_ERR_INVALID, before anything is launched: N < 0, N >= 2^31, a NaN t_n, a null pointer other than shift, a too small workspace. */
+size_t wm_gs_effect_spread_workspace_bytes(int64_t N);
+wm_status wm_gs_effect_spread(const float* means, const float* scales, const float* opacities, const float* colors, const float* random_vals,
+                              int64_t N, double t_n, int ignore_scale, const float* shift, float inv_scale, int colors_are_sh0, float* out_means,
+                              float* out_scales, float* out_opacities, float* out_colors, float* flag, double* stats, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* wm_video_frames: the frames in bytes.  rgbs [F,H,W,3] fp32 (or NULL) -> rgb_out [F,H,W,3] u8 = uint8 of clamp to [0, 1] times 255, the fp32
+ * product truncated (_make_video, render_utils.py:355-357).  depths [F,H,W] fp32 (or NULL) -> depth_out [F,H,W,3] u8 and near_far [F,2] fp32:
+ * depth_vis of render_utils.py:326-335 per frame, near = log of torch.quantile of the pixels d > 0 at 0.01 (the number 0.0 where no pixel is
+ * valid), far = log of torch.quantile of every pixel at 0.99, both exact order statistics with torch's linear interpolation (rank = q (n - 1)
+ * as an fp32 product, lerp with the weight < 0.5 switch; the log taken in fp64 and rounded once), then per pixel
+ * x = 1 - (log(max(d, 1e-9)) - near) / (far - near + 1e-9) in fp32, clipped to [0, 1], row min(int(256 x), 255) of matplotlib's turbo table
+ * (src/utils/color_map.py:11-29), each table byte being uint8 of the fp32 row value times 255.  Degenerate frames follow that arithmetic (all
+ * zero: near 0, far -inf, every pixel the last row).  NaN depths are out of contract.  One histogram pass per radix digit covers all frames;
+ * the masked subset is selected in place.  Deterministic; no synchronisation.  F <= 65535, H W < 2^31.
+ * workspace: the _workspace_bytes value for (F, H, W), read only with depths; 0 for sizes the call refuses.
+ * wm_turbo_lut: host only, no device work: the 256 x 3 table bytes, rows r g b. */
+size_t wm_video_frames_workspace_bytes(int F, int H, int W);
+wm_status wm_video_frames(const float* rgbs, const float* depths, int F, int H, int W, unsigned char* rgb_out, unsigned char* depth_out,
+                          float* near_far, void* workspace, size_t workspace_bytes, void* stream);
+void wm_turbo_lut(unsigned char out[768]);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
