@@ -78,6 +78,8 @@ EXPORTS = [
     "wm_pack_point_ply_workspace_bytes", "wm_pack_point_ply",
     "wm_knn_workspace_bytes", "wm_knn",
     "wm_gs_effect_spread_workspace_bytes", "wm_gs_effect_spread", "wm_video_frames_workspace_bytes", "wm_video_frames", "wm_turbo_lut",
+    "wm_image_mesh_workspace_bytes", "wm_image_mesh_count", "wm_image_mesh_pack", "wm_glb_pack_points_workspace_bytes", "wm_glb_pack_points",
+    "wm_masked_percentile_neighbours_workspace_bytes", "wm_masked_percentile_neighbours",
 ]
 
 _lib = None
@@ -252,6 +254,16 @@ def lib() -> C.CDLL:
     L.wm_video_frames.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
     L.wm_turbo_lut.argtypes = [vp]
     L.wm_turbo_lut.restype = None
+    L.wm_image_mesh_workspace_bytes.argtypes = [i32, i32, i32]
+    L.wm_image_mesh_workspace_bytes.restype = C.c_size_t
+    L.wm_image_mesh_count.argtypes = [vp, i32, i32, i32, vp, C.c_size_t, i64p, i64p, vp]
+    L.wm_image_mesh_pack.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, C.c_size_t, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.wm_glb_pack_points_workspace_bytes.argtypes = [i64]
+    L.wm_glb_pack_points_workspace_bytes.restype = C.c_size_t
+    L.wm_glb_pack_points.argtypes = [vp, vp, vp, i64, vp, C.c_size_t, vp, C.c_size_t, i64p, vp, vp]
+    L.wm_masked_percentile_neighbours_workspace_bytes.argtypes = [i64, i32]
+    L.wm_masked_percentile_neighbours_workspace_bytes.restype = C.c_size_t
+    L.wm_masked_percentile_neighbours.argtypes = [vp, vp, i64, C.POINTER(f64), i32, vp, C.c_size_t, vp, vp, vp]
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
     L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t

@@ -45,3 +45,22 @@ size_t wm_video_frames_ws_bytes(int F, int H, int W);      // 0 for sizes the la
 hipError_t wm_launch_video_frames(const float* rgbs, const float* depths, int F, int H, int W, unsigned char* rgb_out, unsigned char* depth_out,
                                   float* near_far, void* workspace, hipStream_t s);
 void wm_turbo_lut_bytes(unsigned char* out);      // host: the 256 x 3 table
+
+// ------------------------------------------------------------------ GLB scene hand-off (glb.hip), entries in wm_api_scene.cpp
+// count: the vertices and valid quads of every view's image mesh (mask [S,H,W] bytes or null = all); leaves its scans in the workspace, synchronises
+// the stream once and writes n_vertices[S + 1], n_quads[S + 1] (host; the totals last).  pack: reads those scans and writes the views' vertices
+// (positions, RGBA, normals when given) and faces, concatenated, and bounds [S,6].  Sizes: S H W < 2^31.
+size_t wm_image_mesh_ws_bytes(int S, int H, int W);      // 0 for sizes the launchers refuse
+hipError_t wm_launch_image_mesh_count(const unsigned char* mask, int S, int H, int W, void* workspace, long long* n_vertices, long long* n_quads,
+                                      hipStream_t s);
+hipError_t wm_launch_image_mesh_pack(const float* points, const float* colors, const float* normals, const unsigned char* mask, int S, int H, int W,
+                                     void* workspace, long long total_v, long long total_q, float* positions, unsigned char* rgba, float* normals_out,
+                                     int* faces, float* bounds, hipStream_t s);
+// the masked rows of points / colors [N,3] in order: out[0, 12 n) positions, out[12 n, 16 n) RGBA; bounds [6]; synchronises once for *n_kept
+size_t wm_glb_points_ws_bytes(long long N);
+hipError_t wm_launch_glb_points(const float* points, const float* colors, const unsigned char* mask, long long N, void* workspace, void* out,
+                                long long* n_kept, float* bounds, hipStream_t s);
+// out [3][nq][2] (device): per column and quantile the order statistics of rank floor((n - 1) q) and the next; *count_out (device) = n
+size_t wm_percentile_neighbours_ws_bytes(long long N, int nq);
+hipError_t wm_launch_percentile_neighbours(const float* points, const unsigned char* mask, long long N, const double* q, int nq, void* workspace,
+                                           float* out, long long* count_out, hipStream_t s);

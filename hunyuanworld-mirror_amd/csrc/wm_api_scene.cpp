@@ -631,3 +631,47 @@ extern "C" wm_status wm_video_frames(const float* rgbs, const float* depths, int
 extern "C" void wm_turbo_lut(unsigned char out[768]) {
   if (out) wm_turbo_lut_bytes(out);
 }
+
+// ---------------------------------------------------------------- GLB scene hand-off (glb.hip)
+extern "C" size_t wm_image_mesh_workspace_bytes(int S, int H, int W) { return wm_image_mesh_ws_bytes(S, H, W); }
+// replaces the mask part of src/utils/visual_util.py:168-179 (valid_quads and np.unique's count) for every view
+extern "C" wm_status wm_image_mesh_count(const unsigned char* mask, int S, int H, int W, void* workspace, size_t workspace_bytes,
+                                         int64_t* n_vertices, int64_t* n_quads, void* stream) {
+  const size_t need = wm_image_mesh_ws_bytes(S, H, W);
+  if (need == 0 || !workspace || workspace_bytes < need || !n_vertices || !n_quads) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_image_mesh_count(mask, S, H, W, workspace, (long long*)n_vertices, (long long*)n_quads, (hipStream_t)stream));
+}
+// replaces visual_util.py:172-190 (the kept faces, the triangles, np.unique's remap and the gathers) and the uint8 colours of :378 / :428
+extern "C" wm_status wm_image_mesh_pack(const float* points, const float* colors, const float* normals, const unsigned char* mask, int S, int H,
+                                        int W, const void* workspace, size_t workspace_bytes, int64_t total_vertices, int64_t total_quads,
+                                        float* positions, unsigned char* rgba, float* normals_out, int32_t* faces, float* bounds, void* stream) {
+  const size_t need = wm_image_mesh_ws_bytes(S, H, W);
+  if (need == 0 || !workspace || workspace_bytes < need || !points || !colors || !bounds) return WM_ERR_INVALID;
+  if (total_vertices < 0 || total_quads < 0) return WM_ERR_INVALID;
+  if (total_vertices > 0 && (!positions || !rgba || (normals && !normals_out))) return WM_ERR_INVALID;
+  if (total_quads > 0 && !faces) return WM_ERR_INVALID;
+  if (((size_t)positions & 3) || ((size_t)normals_out & 3) || ((size_t)faces & 3)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_image_mesh_pack(points, colors, normals, mask, S, H, W, (void*)workspace, total_vertices, total_quads, positions,
+                                                rgba, normals_out, faces, bounds, (hipStream_t)stream));
+}
+extern "C" size_t wm_glb_pack_points_workspace_bytes(int64_t N) { return wm_glb_points_ws_bytes(N); }
+// replaces visual_util.py:274-298 (the uint8 colours and the boolean indexing of the flattened points)
+extern "C" wm_status wm_glb_pack_points(const float* points, const float* colors, const unsigned char* mask, int64_t N, void* workspace,
+                                        size_t workspace_bytes, void* out, size_t out_bytes, int64_t* n_kept, float* bounds, void* stream) {
+  const size_t need = wm_glb_points_ws_bytes(N);
+  if (need == 0 || !workspace || workspace_bytes < need || !points || !colors || !out || !n_kept || !bounds) return WM_ERR_INVALID;
+  if (out_bytes < (size_t)N * 16 || ((size_t)out & 3)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_glb_points(points, colors, mask, N, workspace, out, (long long*)n_kept, bounds, (hipStream_t)stream));
+}
+extern "C" size_t wm_masked_percentile_neighbours_workspace_bytes(int64_t N, int n_quantiles) {
+  return wm_percentile_neighbours_ws_bytes(N, n_quantiles);
+}
+// replaces the selection inside np.percentile of visual_util.py:307-308 (a partition of the filtered points per axis)
+extern "C" wm_status wm_masked_percentile_neighbours(const float* points, const unsigned char* mask, int64_t N, const double* quantiles,
+                                                     int n_quantiles, void* workspace, size_t workspace_bytes, float* out, int64_t* count_out,
+                                                     void* stream) {
+  const size_t need = wm_percentile_neighbours_ws_bytes(N, n_quantiles);
+  if (need == 0 || !workspace || workspace_bytes < need || !quantiles || !out || !count_out || (N > 0 && !points)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_percentile_neighbours(points, mask, N, quantiles, n_quantiles, workspace, out, (long long*)count_out,
+                                                      (hipStream_t)stream));
+}

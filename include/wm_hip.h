@@ -898,6 +898,41 @@ wm_status wm_video_frames(const float* rgbs, const float* depths, int F, int H, 
                           float* near_far, void* workspace, size_t workspace_bytes, void* stream);
 void wm_turbo_lut(unsigned char out[768]);
 
+/* ---- GLB scene hand-off (csrc/glb.hip): the 3-D view of the demo, convert_predictions_to_glb_scene of src/utils/visual_util.py:208-469 with
+ * create_image_mesh (:109-205), in the layout of a glTF 2.0 BIN chunk.  All arrays contiguous on the device unless marked host.
+ * image mesh.  mask [S,H,W] bytes (non-zero = in; NULL = every pixel).  A quad at pixel p = y W + x is valid when p, p + W, p + W + 1 and
+ *   p + 1 are all in; a pixel is a vertex when it is a corner of a valid quad.  Vertices come in ascending pixel index (np.unique's order),
+ *   faces in raster order of the quads, (a, b, c), (a, c, d) for the quad (p, p + W, p + W + 1, p + 1), indices local to the view.
+ *   The count entry leaves its scans in the workspace, synchronises the stream ONCE and writes n_vertices[S + 1] and n_quads[S + 1] (host:
+ *   per view, the total last).  The pack entry, given the same mask and the untouched workspace, writes the views one after another:
+ *   positions [V,3] fp32 (bit copies of points [S,H,W,3]), rgba [V,4] u8 = trunc of the reference's three fp32 roundings
+ *   fl(fl(fl(x 255) / 255) 255) of colors [S,H,W,3] with alpha 255, normals_out [V,3] (copies of normals [S,H,W,3]; both NULL for none),
+ *   faces [2 Q,3] int32, and bounds [S,6] fp32 = min xyz, max xyz of each view's vertices (+inf, -inf for a view without any).
+ *   No atomics and no floating-point accumulation: positions come from prefix sums.  Non-finite positions are out of contract for bounds.
+ *   workspace: the _workspace_bytes value for (S, H, W): 4 bytes per pixel + about 32 per 512 pixels; 0 for S, H or W < 1 or S H W >= 2^31.
+ * point cloud (visual_util.py:274-298).  The rows i of points / colors [N,3] with mask[i] != 0 (NULL: all), in order: out[0, 12 n) positions,
+ *   out[12 n, 16 n) RGBA = trunc(fl(x 255)), alpha 255; out_bytes >= 16 N, 4-byte aligned; bounds [6].  Synchronises once and writes *n_kept
+ *   (host) = n.  workspace: the _workspace_bytes value for N; 0 for N < 1 or N >= 2^31.
+ * percentile neighbours (np.percentile's selection, visual_util.py:307-308).  For column c of points [N,3] and quantile j (quantiles: host,
+ *   1 .. 4 values in [0, 1]) out[(c n_quantiles + j) 2 + u], u = 0, 1: the order statistics of rank floor((n - 1) q_j) + u (clipped to n - 1)
+ *   among the n rows with mask[i] != 0, exact, by radix selection (integer histogram adds are its only atomics); *count_out (device) = n;
+ *   with n = 0 out is not written.  -0 orders below +0; NaN is out of contract.  No synchronisation.
+ *   workspace: the _workspace_bytes value; 0 for N < 0, 3 N >= 2^31 or n_quantiles outside 1 .. 4.
+ * WM_ERR_INVALID, before anything is launched: a null pointer where none is allowed, sizes the size calls refuse, a too small workspace or
+ *   output buffer, a misaligned output. */
+size_t wm_image_mesh_workspace_bytes(int S, int H, int W);
+wm_status wm_image_mesh_count(const unsigned char* mask, int S, int H, int W, void* workspace, size_t workspace_bytes, int64_t* n_vertices,
+                              int64_t* n_quads, void* stream);
+wm_status wm_image_mesh_pack(const float* points, const float* colors, const float* normals, const unsigned char* mask, int S, int H, int W,
+                             const void* workspace, size_t workspace_bytes, int64_t total_vertices, int64_t total_quads, float* positions,
+                             unsigned char* rgba, float* normals_out, int32_t* faces, float* bounds, void* stream);
+size_t wm_glb_pack_points_workspace_bytes(int64_t N);
+wm_status wm_glb_pack_points(const float* points, const float* colors, const unsigned char* mask, int64_t N, void* workspace,
+                             size_t workspace_bytes, void* out, size_t out_bytes, int64_t* n_kept, float* bounds, void* stream);
+size_t wm_masked_percentile_neighbours_workspace_bytes(int64_t N, int n_quantiles);
+wm_status wm_masked_percentile_neighbours(const float* points, const unsigned char* mask, int64_t N, const double* quantiles, int n_quantiles,
+                                          void* workspace, size_t workspace_bytes, float* out, int64_t* count_out, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
