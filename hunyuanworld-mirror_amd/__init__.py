@@ -16,4 +16,6 @@ from .colmap import colmap_points_from_depth, load_colmap, save_colmap, save_poi
 from .splat_init import create_splats_with_optimizers, knn, knn_scales, rgb_to_sh  # noqa: F401
 from .video import (GSEffects, depth_frames, interpolate_trajectory, quaternion_to_rotation_matrix, render_interpolated_frames,  # noqa: F401
                     render_interpolated_video, rgb_frames, rotation_matrix_to_quaternion, slerp_quaternions, wobble_trajectory)
+from .metrics import (Evaluator, PeakSignalNoiseRatio, StructuralSimilarityIndexMeasure, color_correct, eval_metrics, psnr,  # noqa: F401
+                      ssim)
 from .glb import (GLBScene, convert_predictions_to_glb_scene, image_mesh, load_glb, save_camera_params)  # noqa: F401

@@ -80,6 +80,7 @@ EXPORTS = [
     "wm_gs_effect_spread_workspace_bytes", "wm_gs_effect_spread", "wm_video_frames_workspace_bytes", "wm_video_frames", "wm_turbo_lut",
     "wm_image_mesh_workspace_bytes", "wm_image_mesh_count", "wm_image_mesh_pack", "wm_glb_pack_points_workspace_bytes", "wm_glb_pack_points",
     "wm_masked_percentile_neighbours_workspace_bytes", "wm_masked_percentile_neighbours",
+    "wm_eval_frame_workspace_bytes", "wm_eval_frame", "wm_color_correct_workspace_bytes", "wm_color_correct",
 ]
 
 _lib = None
@@ -264,6 +265,12 @@ def lib() -> C.CDLL:
     L.wm_masked_percentile_neighbours_workspace_bytes.argtypes = [i64, i32]
     L.wm_masked_percentile_neighbours_workspace_bytes.restype = C.c_size_t
     L.wm_masked_percentile_neighbours.argtypes = [vp, vp, i64, C.POINTER(f64), i32, vp, C.c_size_t, vp, vp, vp]
+    L.wm_eval_frame_workspace_bytes.argtypes = [i32, i32, i32]
+    L.wm_eval_frame_workspace_bytes.restype = C.c_size_t
+    L.wm_eval_frame.argtypes = [vp, i64p, vp, i64p, i32, i32, i32, i32, f64, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.wm_color_correct_workspace_bytes.argtypes = [i32, i64]
+    L.wm_color_correct_workspace_bytes.restype = C.c_size_t
+    L.wm_color_correct.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, C.c_size_t, vp]
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
     L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t

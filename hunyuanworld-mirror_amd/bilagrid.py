@@ -9,8 +9,9 @@ csrc/bilagrid.hip).  The three names the trainer imports from examples/lib_bilag
 
 What differs from lib_bilagrid.py, on purpose: the sliced [..., 3, 4] matrices are never materialised, so the dict ``slice`` returns has
 no "rgb_affine_mats"; ``BilateralGrid.forward`` (which returns those matrices) and 2-D inputs (one grid index per sample) raise
-NotImplementedError; ``color_correct`` (an evaluation-time least-squares fit) and the CP-decomposed 4-D grid (``BilateralGridCP4D``,
-``slice4d``: they need tensorly) are not part of this library.  No CPU fallback: tensors must live on a HIP device."""
+NotImplementedError; the CP-decomposed 4-D grid (``BilateralGridCP4D``, ``slice4d``: they need tensorly) is not part of this library.
+``color_correct``, the evaluation-time colour fit, lives in metrics.py (``wm_color_correct``) and is re-exported here under the name
+lib_bilagrid gives it.  No CPU fallback: tensors must live on a HIP device."""
 from __future__ import annotations
 
 import torch
@@ -18,6 +19,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import check, ptr, stream
+from .metrics import color_correct  # noqa: F401
 
 MAX_CELLS = 4096      # include/wm_hip.h: L * Hg * Wg the grid gradient keeps in registers
 MAX_AXIS = 1024

@@ -64,3 +64,15 @@ hipError_t wm_launch_glb_points(const float* points, const float* colors, const 
 size_t wm_percentile_neighbours_ws_bytes(long long N, int nq);
 hipError_t wm_launch_percentile_neighbours(const float* points, const unsigned char* mask, long long N, const double* q, int nq, void* workspace,
                                            float* out, long long* count_out, hipStream_t s);
+
+// ------------------------------------------------------------------ trainer evaluation (evalmetrics.hip), entries in wm_api_scene.cpp
+// colors / pixels [B,H,W,3] by element strides (B, H, W, C); clamped [B,H,W,3], canvas [B,H,2W,3] u8, psnr_all, psnr_each [B]: each may be null.
+// No synchronisation.  Sizes: B <= 65535, 6 H W < 2^31.
+size_t wm_eval_frame_ws_bytes(int B, int H, int W);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_eval_frame(const float* colors, const long long* cs, const float* pixels, const long long* ps, int B, int H, int W, int clamp,
+                                double data_range, float* clamped, unsigned char* canvas, float* psnr_all, float* psnr_each, void* workspace,
+                                hipStream_t s);
+// img, ref, out: contiguous [nsys][P][3]; out must not overlap img.  No synchronisation.  nsys <= 65535, P < 2^31.
+size_t wm_color_correct_ws_bytes(int nsys, long long P);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_color_correct(const float* img, const float* ref, int nsys, long long P, int num_iters, double eps, float* out, void* workspace,
+                                   hipStream_t s);

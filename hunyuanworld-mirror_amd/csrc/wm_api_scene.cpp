@@ -1,6 +1,6 @@
 // Scene-level entries of the C ABI (include/wm_hip.h): the caller's steps on either side of the forward, each with its *_workspace_bytes.
 // In file order: splat pruning, the rasteriser, densification, MCMC, the photometric loss, the bilateral grid, the appearance module, the
-// depth loss and point projection, then image ingest and the point masks, the COLMAP hand-off, the nearest neighbours and the fly-through video.  Each entry
+// depth loss and point projection, then image ingest and the point masks, the COLMAP hand-off, the nearest neighbours, the fly-through video, the GLB scene and the trainer evaluation.  Each entry
 // checks its arguments, fills its launcher's args struct, launches on the caller's stream and maps the hipError_t.
 #include <hip/hip_runtime.h>
 
@@ -674,4 +674,29 @@ extern "C" wm_status wm_masked_percentile_neighbours(const float* points, const 
   if (need == 0 || !workspace || workspace_bytes < need || !quantiles || !out || !count_out || (N > 0 && !points)) return WM_ERR_INVALID;
   return wm_status_of(wm_launch_percentile_neighbours(points, mask, N, quantiles, n_quantiles, workspace, out, (long long*)count_out,
                                                       (hipStream_t)stream));
+}
+extern "C" size_t wm_eval_frame_workspace_bytes(int B, int H, int W) { return wm_eval_frame_ws_bytes(B, H, W); }
+// replaces simple_trainer_worldmirror.py:1040-1054: the clamp, the canvas bytes and the PSNR of one batch of renders
+extern "C" wm_status wm_eval_frame(const float* colors, const int64_t* color_strides, const float* pixels, const int64_t* pixel_strides, int B, int H,
+                                   int W, int clamp_colors, double data_range, float* clamped_out, unsigned char* canvas_out, float* psnr_out,
+                                   float* psnr_per_image, void* workspace, size_t workspace_bytes, void* stream) {
+  const size_t need = wm_eval_frame_ws_bytes(B, H, W);
+  if (need == 0 || !workspace || workspace_bytes < need || !colors || !pixels || !color_strides || !pixel_strides) return WM_ERR_INVALID;
+  if (!(data_range > 0.0) || (canvas_out && !clamp_colors)) return WM_ERR_INVALID;   // the canvas shows the clamped render
+  if (((size_t)workspace & 7) || ((size_t)clamped_out & 3)) return WM_ERR_INVALID;
+  long long cs[4], ps[4];
+  for (int i = 0; i < 4; ++i) { cs[i] = color_strides[i]; ps[i] = pixel_strides[i]; }
+  return wm_status_of(wm_launch_eval_frame(colors, cs, pixels, ps, B, H, W, clamp_colors, data_range, clamped_out, canvas_out, psnr_out,
+                                           psnr_per_image, workspace, (hipStream_t)stream));
+}
+extern "C" size_t wm_color_correct_workspace_bytes(int n_systems, int64_t n_pixels) { return wm_color_correct_ws_bytes(n_systems, n_pixels); }
+// replaces lib_bilagrid.py:56-126 (color_correct): per iteration one accumulation pass and one solve, no [P,10] matrix, no host round trip
+extern "C" wm_status wm_color_correct(const float* img, const float* ref, int n_systems, int64_t n_pixels, int num_iters, double eps, float* out,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  const size_t need = wm_color_correct_ws_bytes(n_systems, n_pixels);
+  if (need == 0 || !workspace || workspace_bytes < need || ((size_t)workspace & 7) || !img || !ref || !out) return WM_ERR_INVALID;
+  if (num_iters < 0 || !(eps > 0.0) || !(eps < 0.5)) return WM_ERR_INVALID;
+  const size_t bytes = (size_t)n_systems * (size_t)n_pixels * 3 * sizeof(float);
+  if ((const char*)out < (const char*)img + bytes && (const char*)img < (const char*)out + bytes) return WM_ERR_INVALID;   // mask0 reads img throughout
+  return wm_status_of(wm_launch_color_correct(img, ref, n_systems, n_pixels, num_iters, eps, out, workspace, (hipStream_t)stream));
 }

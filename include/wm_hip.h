@@ -933,6 +933,39 @@ size_t wm_masked_percentile_neighbours_workspace_bytes(int64_t N, int n_quantile
 wm_status wm_masked_percentile_neighbours(const float* points, const unsigned char* mask, int64_t N, const double* quantiles, int n_quantiles,
                                           void* workspace, size_t workspace_bytes, float* out, int64_t* count_out, void* stream);
 
+/* ---- Trainer evaluation (csrc/evalmetrics.hip): Runner.eval of gsplat's simple_trainer_worldmirror.py:1005-1091 and color_correct of
+ * examples/lib_bilagrid.py:56-126.  Both entries are asynchronous on stream and never synchronise the host.  Every sum is fp64 in a fixed
+ * order (a lane in index order, a block by a fixed tree or one lane per sum, the blocks' partials in block order): no floating-point atomics,
+ * results are bitwise reproducible.
+ * eval frame (:1040-1054).  colors, pixels: fp32 [B,H,W,3] addressed by ELEMENT strides (sB, sH, sW, sC) (host arrays, read during the call), so
+ *   channels 0:3 of an RGB+ED [B,H,W,4] render and the permuted view of a [B,3,H,W] tensor are read in place.  c = clamp(colors, 0, 1) when
+ *   clamp_colors (NaN stays NaN), else colors.  clamped_out [B,H,W,3] fp32 contiguous = c.  canvas_out uint8 [B,H,2W,3]: pixels on the left,
+ *   c on the right, each byte the fp32 product v * 255.0f truncated toward zero ((canvas * 255).astype(np.uint8); values outside [0, 1] are
+ *   out of contract and saturate); it needs clamp_colors.  *psnr_out = 10 log10(data_range^2 / mse) over all B H W 3 values and
+ *   psnr_per_image[b] the same over image b, fp32 device values formed in fp64 from differences and squares taken in fp64 of the fp32 inputs;
+ *   +inf for mse == 0.  A per-image value does not depend on B.  Any of the four outputs may be NULL.
+ *   workspace: the _workspace_bytes value (8 bytes per 1024 pixels of each image), 8-byte aligned; 0 for B, H or W < 1, B > 65535 or
+ *   6 H W >= 2^31.
+ * colour correction.  img, ref, out: contiguous fp32 [n_systems][n_pixels][3]; each system is fitted on its own (n_systems = 1: the
+ *   reference's reshape([-1, 3])).  The reference's algorithm, masks, num_iters and eps; per iteration one pass forms the 10 features of the
+ *   current image (rr rg rb gg gb bb r g b 1) and adds, per channel c under mask0_c & unclipped(cur_c) & unclipped(ref_c), the 55 unique
+ *   Gram entries and the 10 right-hand sides (products in fp64 of the fp32 values); the blocks' partial sums are added in block order, and one wave per system solves the three 10 x 10
+ *   normal equations: cyclic Jacobi eigendecomposition, then the MINIMUM-NORM least-squares solution over the eigenvalues above 1e-10 of
+ *   the largest (a channel with an empty mask gets w = 0).  The next pass applies the warp in fp64, clips to [0, 1], rounds the image to
+ *   fp32 (once per iteration, as the fp32 reference does) and accumulates again; the last pass only applies.  is_unclipped compares in fp32
+ *   against (float)eps and (float)(1 - eps).  num_iters = 0 copies img to out.  out must not overlap img (mask0 is re-read from img).
+ *   workspace: the _workspace_bytes value (1560 bytes per 512 pixels of each system + 1800 per system), 8-byte aligned; 0 for
+ *   n_systems outside 1 .. 65535 or n_pixels outside 1 .. 2^31 - 1.
+ * WM_ERR_INVALID, before anything is launched: a null input or workspace, sizes the size calls refuse, a too small or misaligned workspace,
+ *   data_range <= 0, a canvas without clamp_colors, num_iters < 0, eps outside (0, 0.5), out overlapping img. */
+size_t wm_eval_frame_workspace_bytes(int B, int H, int W);
+wm_status wm_eval_frame(const float* colors, const int64_t* color_strides, const float* pixels, const int64_t* pixel_strides, int B, int H,
+                        int W, int clamp_colors, double data_range, float* clamped_out, unsigned char* canvas_out, float* psnr_out,
+                        float* psnr_per_image, void* workspace, size_t workspace_bytes, void* stream);
+size_t wm_color_correct_workspace_bytes(int n_systems, int64_t n_pixels);
+wm_status wm_color_correct(const float* img, const float* ref, int n_systems, int64_t n_pixels, int num_iters, double eps, float* out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
