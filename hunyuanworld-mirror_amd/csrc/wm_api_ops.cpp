@@ -1,11 +1,12 @@
 // Operator-level entries of the C ABI (include/wm_hip.h: wm_op_*), for tests and tools: each checks its pointers, fills one launcher's args
-// struct, launches on the caller's stream and maps the hipError_t.  wm_op_tconv and wm_op_dpt_tap_front run the forward's own building
-// blocks and live beside them in wm_model.cpp.
+// struct, launches on the caller's stream and maps the hipError_t.  wm_op_tconv and wm_op_dpt_tap_front, at the end, run the forward's own
+// building blocks through the orchestrator's internal header (wm_model.h).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "wm_api.h"
+#include "wm_model.h"
 
 extern "C" wm_status wm_op_gemm(int dtype, int epi, const void* A, const void* Wp, void* C, const float* bias, const float* gamma,
                                 int M, int N, int K, void* stream) {
@@ -325,4 +326,78 @@ extern "C" wm_status wm_op_up_conv_n32_tail(int dtype, const float* x, const voi
   a.N = N; a.H = Hi; a.W = Wi; a.Cin = Cin; a.relu_out = 0; a.dtype = dtype;
   a.tail_w = tail_w; a.tail_b = tail_b; a.tail_C = tail_C; a.tail_act = tail_act; a.tail_attr = attr; a.tail_conf = conf;
   return wm_status_of(wm_launch_conv3x3_n32_in16(a, s));
+}
+
+// ====================================================================================== the forward's own building blocks
+using namespace wm_host;
+
+// Conv2d(Cm, 256, 3, padding=1, bias=False)(ConvTranspose2d(Cin, Cm, k, stride=k)(tokens)) composed at the token resolution (build_tconv):
+// tokens16 [N][gh][gw][Cin] 16-bit device; wct [Cin][Cm][k][k], bct [Cm], wrn [256][Cm][3][3]: HOST fp32 in torch's layouts; out fp32 [N][k gh][k gw][256]
+extern "C" wm_status wm_op_tconv(int dtype, const void* tokens16, const float* wct, const float* bct, const float* wrn, float* out, int N, int gh, int gw,
+                                 int k, int Cin, int Cm, const void* zero16, void* stream) {
+  if (!tokens16 || !wct || !bct || !wrn || !out || !zero16) return WM_ERR_INVALID;
+  TconvPack t;
+  hipStream_t s = (hipStream_t)stream;
+  if (build_tconv(dtype, k, Cin, Cm, 256, wct, bct, wrn, t, s) != hipSuccess) return WM_ERR_HIP;
+  const hipError_t e = launch_tconv(t, dtype, tokens16, out, N, gh, gw, zero16, s);
+  (void)hipStreamSynchronize(s);
+  free_tconv(t);
+  return e == hipSuccess ? WM_OK : WM_ERR_HIP;
+}
+// The DPT heads' tap front for one tap (dense_head.py:53,204-208), both forms the forward has: shared = 0 every head normalises the tap with its
+// own affine and projects it; shared = 1 one LayerNorm without affine and one GEMM over the heads' folded weights (build_tapfold), unless a folded
+// weight leaves the operand type's range — then the direct form runs (*ran_shared tells).  Host fp32 weights, device tap / pos / outputs.
+extern "C" wm_status wm_op_dpt_tap_front(int dtype, const float* tap, int n, int P, int psi, int hw, int D2, int nheads, int oc,
+                                         const float* const* norm_w, const float* const* norm_b, const float* const* proj_w,
+                                         const float* const* proj_b, const float* pos, int out16, int shared, void* const* out, int* ran_shared,
+                                         void* stream) {
+  if (!tap || !norm_w || !norm_b || !proj_w || !proj_b || !out || n <= 0 || hw <= 0 || psi < 0 || P < psi + hw || D2 <= 0 || D2 % 64 || nheads < 1 ||
+      nheads > 4 || oc <= 0 || (oc & 3) || (dtype != WM_DT_BF16 && dtype != WM_DT_F16))
+    return WM_ERR_INVALID;
+  for (int k = 0; k < nheads; ++k)
+    if (!norm_w[k] || !norm_b[k] || !proj_w[k] || !proj_b[k] || !out[k]) return WM_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  wm_handle tmp;
+  Ctx c{&tmp, Dims(), s, dtype, dtype};
+  if (ran_shared) *ran_shared = 0;
+  std::vector<void*> dev;
+  auto dalloc = [&](size_t bytes) -> void* { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) return nullptr; dev.push_back(q); return q; };
+  auto finish = [&](wm_status st) {
+    (void)hipStreamSynchronize(s);
+    for (void* q : dev) (void)hipFree(q);
+    return st;
+  };
+  void* xhat = dalloc((size_t)n * hw * D2 * 2);
+  if (!xhat) return finish(WM_ERR_HIP);
+  if (shared) {
+    void* w16 = nullptr; float* bias = nullptr; bool in_range = false;
+    if (build_tapfold(dtype, nheads, oc, D2, D2, proj_w, proj_b, norm_w, norm_b, &w16, &bias, &in_range) != hipSuccess) return finish(WM_ERR_HIP);
+    if (in_range) {
+      dev.push_back(w16); dev.push_back(bias);
+      if (ran_shared) *ran_shared = 1;
+      return finish(tap_front_one(c, tap, xhat, w16, bias, pos, nheads, oc, out16, out, n, hw, P, psi, D2));
+    }
+  }
+  for (int k = 0; k < nheads; ++k) {   // the direct form, as dpt_head runs it
+    float* gw = (float*)dalloc((size_t)D2 * 4); float* gb = (float*)dalloc((size_t)D2 * 4); float* pb = (float*)dalloc((size_t)oc * 4);
+    void* w16 = dalloc((size_t)oc * D2 * 2);
+    if (!gw || !gb || !pb || !w16) return finish(WM_ERR_HIP);
+    std::vector<uint16_t> r((size_t)oc * D2);
+    for (size_t i = 0; i < r.size(); ++i) r[i] = h_to16(proj_w[k][i], dtype);
+    if (hipMemcpy(gw, norm_w[k], (size_t)D2 * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(gb, norm_b[k], (size_t)D2 * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(pb, proj_b[k], (size_t)oc * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(w16, r.data(), r.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
+      return finish(WM_ERR_HIP);
+    WmLnArgs ln{};
+    ln.x = tap; ln.ld_in = D2; ln.y = xhat; ln.ld_out = D2; ln.w = gw; ln.b = gb; ln.D = D2; ln.eps = 1e-5f;
+    ln.groups = n; ln.rows_per_group = hw; ln.in_group = P; ln.in_off = psi; ln.out_group = hw; ln.dtype = dtype;
+    wm_status st = layernorm(c, ln);
+    if (st) return finish(st);
+    WmGemmArgs ex;
+    memset(&ex, 0, sizeof(ex));
+    ex.rows_per_group = hw; ex.out_group = hw; ex.out_off = 0; ex.add = pos; ex.out16 = out16;
+    st = gemm(c, dtype, WM_EPI_ROWMAP_ADD, xhat, D2, w16, D2, out[k], oc, pb, nullptr, n * hw, oc, D2, &ex);
+    if (st) return finish(st);
+    if (hipStreamSynchronize(s) != hipSuccess) return finish(WM_ERR_HIP);   // xhat is reused by the next head
+  }
+  return finish(WM_OK);
 }

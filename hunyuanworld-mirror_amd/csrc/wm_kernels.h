@@ -1,4 +1,4 @@
-// Internal launcher interface between the host side (the orchestrator wm_model.cpp, the entry files wm_api_ops.cpp and wm_api_scene.cpp)
+// Internal launcher interface between the host side (the orchestrator behind wm_model.h, the entry files wm_api_ops.cpp and wm_api_scene.cpp)
 // and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -122,7 +122,7 @@ struct WmAttnArgs {
   // the general kernel, launches ONLY the general kernel there for the next WM_ATTN_HINT_TTL calls: two partly filled launches
   // (fast kernel on the units in range, general kernel on the rest) cost up to 1.25 x the general kernel alone.
   int* unit_stat;
-  // Key range processed piecewise (sharded forward with the K/V all-gather overlapped, wm_model.cpp): with force_partial every
+  // Key range processed piecewise (sharded forward with the K/V all-gather overlapped, wm_backbone.cpp): with force_partial every
   // unit — split or not — writes an unnormalised partial into slot part_slot0 + split (kv_splits = the explicit, uniform slice
   // count of THIS launch, >= 1), nothing is combined; wm_launch_attention_combine then finishes all units over all slots.
   int force_partial, part_slot0;
@@ -468,6 +468,6 @@ hipError_t wm_launch_prune_gs(const float* means, const float* quats, const floa
 #define WM_TUNE_ENUM(name_, key_) WM_TUNE_##name_,
 enum { WM_TUNE_KEYS(WM_TUNE_ENUM) WM_TUNE_COUNT };
 #undef WM_TUNE_ENUM
-extern int wm_tuning[WM_TUNE_COUNT];   // one definition, beside wm_set_tuning in wm_model.cpp; the launchers and wm_api_ops.cpp read it too
+extern int wm_tuning[WM_TUNE_COUNT];   // one definition, beside wm_set_tuning in wm_weights.cpp; the launchers and wm_api_ops.cpp read it too
 inline int wm_tune(int key, int dflt) { return wm_tuning[key] < 0 ? dflt : wm_tuning[key]; }
 

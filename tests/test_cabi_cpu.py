@@ -106,6 +106,35 @@ def test_shipped_library_reads_no_wm_environment_switch(L):
             assert name not in text, (f, name)
 
 
+def test_orchestrator_internals_are_not_exported(L):
+    """The orchestrator's translation units share their types and functions through csrc/wm_model.h, in the namespace wm_host with hidden
+    visibility: none of it may reach the library's dynamic symbol table, which holds the C ABI (the entries wm_host_to_16 and
+    wm_host_resample_pos are C names, not members of the namespace)."""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    if nm is None and os.path.exists("/opt/rocm/llvm/bin/llvm-nm"):
+        nm = "/opt/rocm/llvm/bin/llvm-nm"
+    if nm is None:
+        pytest.skip("neither nm nor llvm-nm on this machine")
+    out = subprocess.run([nm, "-D", "--defined-only", "-C", LIB], check=True, capture_output=True, text=True).stdout
+    assert "wm_set_tuning" in out, "the symbol listing does not show the C ABI either"
+    leaked = [l for l in out.splitlines() if "wm_host::" in l]
+    assert not leaked, leaked
+    raw = subprocess.run([nm, "-D", "--defined-only", LIB], check=True, capture_output=True, text=True).stdout
+    assert not [l for l in raw.splitlines() if "7wm_host" in l], "mangled names of the namespace"
+
+
+def test_forward_files_create_no_queue():
+    """The forward records, waits and launches: the sources that hold the forward path create no stream and no event (wm_reserve and the
+    communicator-init entries do) and allocate nothing."""
+    src = os.path.join(ROOT, "hunyuanworld-mirror_amd", "csrc")
+    for f in ("wm_model.cpp", "wm_backbone.cpp", "wm_heads.cpp"):
+        text = open(os.path.join(src, f)).read()
+        for call in ("hipStreamCreate", "hipEventCreateWithFlags", "hipMalloc", "hipHostMalloc"):
+            assert call not in text, (f, call)
+
+
 # the key strings of wm_set_tuning before the table became a single list (wm_model.cpp of that commit): tests, tools and bench.py
 # call them by these spellings
 TUNING_KEYS_BEFORE_TABLE = ["gemm_cfg", "gemm_pp", "gemm_mfma16", "attn_qb", "op_ldpad", "attn_splits", "conv_fuse_up", "conv_narrow", "conv_bn",

@@ -1013,7 +1013,7 @@ def test_up_conv_n32_unfused(dev, N, Hs, Ws, Hi, Wi, Cin):
 @pytest.mark.parametrize("N,gh,gw,k,Cin", [(2, 16, 16, 4, 256), (3, 10, 7, 2, 512), (1, 37, 37, 4, 256), (8, 37, 37, 2, 512), (1, 1, 5, 4, 64), (2, 3, 1, 2, 128)])
 def test_token_conv_composition(dev, dt, N, gh, gw, k, Cin):
     """wm_op_tconv: Conv2d(3x3, pad 1, no bias) o ConvTranspose2d(kernel = stride = k) as ONE block-sparse GEMM at the token resolution
-    (per output phase the combined matrices of the <= 2 x 2 neighbour tokens its taps land in; gemm.hip WM_EPI_CONV tc_k, wm_model.cpp
+    (per output phase the combined matrices of the <= 2 x 2 neighbour tokens its taps land in; gemm.hip WM_EPI_CONV tc_k, wm_compose.cpp
     build_tconv) — against fp32 torch conv2d(conv_transpose2d(tokens)) on the same 16-bit tokens: interior, the image border (zero
     padding of the 3x3 sees neither neighbour tokens nor the ConvTranspose bias there), single-row / single-column token grids, both k."""
     g = torch.Generator().manual_seed(N * 7 + gh + k + Cin + dt)
