@@ -5,7 +5,9 @@ CPU: oracle/raster_ref.py against outputs of the reference's own gsplat torch im
 written by oracle/gen_golden_raster.py): covariances, projection, radii, conics, SH colours, tile-intersection lists.
 The compositing stage has no runnable reference here (PARITY UNPINNED for that stage, see the oracle's header): it is a
 restatement of gsplat's CUDA kernel, checked by a second tiling-free formulation and by closed-form cases.
-GPU: libwm_hip.so (wm_rasterize_splats) against the oracle."""
+GPU: libwm_hip.so (wm_rasterize_splats) against the oracle.
+The scenes here run the 2-pixel-per-lane compositing kernel only; all three kernels, and the list-walk edges (list lengths, saturation
+exits, image edges), are compared per pixel with the fp64 restatement in tests/test_raster_composite_gpu.py."""
 import os
 
 import numpy as np
