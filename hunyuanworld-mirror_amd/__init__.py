@@ -19,3 +19,4 @@ from .video import (GSEffects, depth_frames, interpolate_trajectory, quaternion_
 from .metrics import (Evaluator, PeakSignalNoiseRatio, StructuralSimilarityIndexMeasure, color_correct, eval_metrics, psnr,  # noqa: F401
                       ssim)
 from .glb import (GLBScene, convert_predictions_to_glb_scene, image_mesh, load_glb, save_camera_params)  # noqa: F401
+from .nvs import apply_confidence_filter, calculate_in_frustum_mask, calculate_unprojected_mask  # noqa: F401

@@ -81,6 +81,7 @@ EXPORTS = [
     "wm_image_mesh_workspace_bytes", "wm_image_mesh_count", "wm_image_mesh_pack", "wm_glb_pack_points_workspace_bytes", "wm_glb_pack_points",
     "wm_masked_percentile_neighbours_workspace_bytes", "wm_masked_percentile_neighbours",
     "wm_eval_frame_workspace_bytes", "wm_eval_frame", "wm_color_correct_workspace_bytes", "wm_color_correct",
+    "wm_confidence_mask_count", "wm_in_frustum_mask",
 ]
 
 _lib = None
@@ -146,6 +147,8 @@ def lib() -> C.CDLL:
     L.wm_confidence_mask_workspace_bytes.argtypes = [C.c_size_t]
     L.wm_confidence_mask_workspace_bytes.restype = C.c_size_t
     L.wm_confidence_mask.argtypes = [vp, C.c_size_t, C.c_double, vp, vp, C.c_size_t, vp]
+    L.wm_confidence_mask_count.argtypes = [vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, vp]
+    L.wm_in_frustum_mask.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]
     L.wm_depth_edge.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, i32, f32, vp, vp]
     L.wm_normals_edge.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, vp, vp]
     L.wm_point_filter_mask_workspace_bytes.argtypes = [i32, i32, i32]

@@ -1,6 +1,6 @@
 // Scene-level entries of the C ABI (include/wm_hip.h): the caller's steps on either side of the forward, each with its *_workspace_bytes.
 // In file order: splat pruning, the rasteriser, densification, MCMC, the photometric loss, the bilateral grid, the appearance module, the
-// depth loss and point projection, then image ingest and the point masks, the COLMAP hand-off, the nearest neighbours, the fly-through video, the GLB scene and the trainer evaluation.  Each entry
+// depth loss and point projection, then image ingest and the point masks (with the novel-view path's select and validity mask), the COLMAP hand-off, the nearest neighbours, the fly-through video, the GLB scene and the trainer evaluation.  Each entry
 // checks its arguments, fills its launcher's args struct, launches on the caller's stream and maps the hipError_t.
 #include <hip/hip_runtime.h>
 
@@ -520,6 +520,22 @@ extern "C" wm_status wm_confidence_mask(const float* conf, size_t n, double conf
   size_t K = keep < 1.0 ? 1 : (size_t)keep;
   if (K > n) K = n;
   return wm_launch_confidence_mask(conf, n, (unsigned int)K, mask, workspace, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
+}
+// the select of wm_confidence_mask with the count given: GaussianSplatRenderer.apply_confidence_filter (rasterization.py:248-299) caps its
+// count with max_gaussians, which no percentage expresses
+extern "C" wm_status wm_confidence_mask_count(const float* conf, size_t n, size_t k, unsigned char* mask, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  if (!conf || !mask || !workspace || workspace_bytes < wm_confidence_mask_workspace(n)) return WM_ERR_INVALID;
+  if (n < 1 || k < 1 || k > n || n >= ((size_t)1 << 32)) return WM_ERR_INVALID;
+  return wm_launch_confidence_mask(conf, n, (unsigned int)k, mask, workspace, (hipStream_t)stream) == hipSuccess ? WM_OK : WM_ERR_HIP;
+}
+// replaces calculate_in_frustum_mask (src/models/utils/frustum.py:26-89) behind the two matrix inverses, which the caller takes once
+extern "C" wm_status wm_in_frustum_mask(const float* depth_1, const float* depth_2, const float* kinv_1, const float* rel, const float* k_2, int B,
+                                        int V1, int V2, int H, int W, unsigned char* mask, void* stream) {
+  if (!depth_1 || !depth_2 || !kinv_1 || !rel || !k_2 || !mask || B < 1 || V1 < 1 || V2 < 1 || H < 1 || W < 1) return WM_ERR_INVALID;
+  if ((long long)B * V1 * H * W >= (1LL << 31) || (long long)B * V2 * H * W >= (1LL << 31) || (long long)B * V1 * V2 >= (1LL << 24))
+    return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_in_frustum_mask(depth_1, depth_2, kinv_1, rel, k_2, B, V1, V2, H, W, mask, (hipStream_t)stream));
 }
 extern "C" wm_status wm_depth_edge(const float* depth, const unsigned char* mask, int S, int H, int W, int k, int has_atol, float atol,
                                    int has_rtol, float rtol, unsigned char* out, void* stream) {

@@ -187,6 +187,10 @@ hipError_t wm_launch_resample_v_tensor(const unsigned char* tmp, float* out, int
                                        const int* bounds, const int* kk, int ksize, hipStream_t s);
 size_t wm_confidence_mask_workspace(size_t n);
 hipError_t wm_launch_confidence_mask(const float* conf, size_t n, unsigned int K, unsigned char* mask, void* workspace, hipStream_t s);
+// target-view validity mask of the novel-view protocol (frustum.hip): depth_1 [B][V1][H][W], depth_2 [B][V2][H][W], kinv_1 [B][V1][3][3],
+// rel [B][V1][V2][3][4], k_2 [B][V2][3][3] -> mask [B][V1][H][W] u8
+hipError_t wm_launch_in_frustum_mask(const float* depth_1, const float* depth_2, const float* kinv_1, const float* rel, const float* k_2, int B,
+                                     int V1, int V2, int H, int W, unsigned char* mask, hipStream_t s);
 // point-cloud filter masks (pointmask.hip): depth_edge / normals_edge over S views of H x W (k = 3, 5, 7), and app.py's fused
 // per-view quantile + edge composition (out_de / out_ne optional: the two edge masks of the composition)
 hipError_t wm_launch_depth_edge(const float* depth, const unsigned char* mask, int S, int H, int W, int k, int has_atol, float atol,

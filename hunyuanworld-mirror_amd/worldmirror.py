@@ -157,15 +157,35 @@ def prune_gs(splats: Dict[str, torch.Tensor], voxel_size: float = 0.002) -> Dict
 class _GSRenderer:
     """``model.gs_renderer`` as the callers use it (infer.py:264 -> render_interpolated_video, src/utils/render_utils.py:121):
     the object carrying ``.rasterizer`` (rasterization.py:133).  The splat head itself runs inside ``wm_forward``; the
-    forward pass does not rasterise (the reference discards that result, rasterization.py:243-246)."""
+    forward pass does not rasterise (the reference discards that result, rasterization.py:243-246): ``render`` does, on request."""
 
     def __init__(self):
         from .rasterization import Rasterizer
         self.rasterizer = Rasterizer()
         self.enable_prune, self.voxel_size, self.sh_degree = True, 0.002, 0
+        self.enable_conf_filter, self.conf_threshold_percent, self.max_gaussians = False, 30.0, 5_000_000   # rasterization.py:107-109
 
     def prune_gs(self, splats, voxel_size: float = 0.002):  # rasterization.py:301 (render_utils.py:206 calls it on the renderer)
         return prune_gs(splats, voxel_size)
+
+    def apply_confidence_filter(self, splats, conf):  # rasterization.py:248-299
+        from .nvs import apply_confidence_filter
+        if not self.enable_conf_filter or conf is None:
+            return splats
+        return apply_confidence_filter(splats, conf, self.conf_threshold_percent, self.max_gaussians)
+
+    def finish_splats(self, raw, depth_conf, S: int):
+        """rasterization.py:211-216: the confidence filter on depth_conf[:, :S] (the reference forgets that cut: INTEGRATION.md), then prune_gs"""
+        splats = raw
+        if self.enable_conf_filter and depth_conf is not None:
+            splats = self.apply_confidence_filter(splats, depth_conf[:, :S])
+        if self.enable_prune:
+            splats = self.prune_gs(splats, voxel_size=self.voxel_size)
+        return splats
+
+    def render(self, images, predictions, views=None, context_predictions=None, chunk_size: int = 4):  # rasterization.py:166-246
+        from .nvs import render
+        return render(self, images, predictions, views, context_predictions, chunk_size)
 
 
 class WorldMirror:
@@ -386,6 +406,12 @@ class WorldMirror:
     def forward(self, views: Dict[str, torch.Tensor], cond_flags: List[int] = [0, 0, 0]):
         if self._handle is None:
             raise RuntimeError("call .to('cuda') first: the forward pass runs in libwm_hip.so on the GPU")
+        # novel-view protocol (rasterization.py:181, 412): views["context_nums"] = S builds the splats from the first S views only
+        if "context_nums" in views and views["img"].dim() == 5:
+            from .nvs import check_context_nums
+            check_context_nums(views["context_nums"], int(views["img"].shape[1]), allow_all=True)
+        if self._comm and self._comm[1] > 1 and ("context_nums" in views or self.gs_renderer.enable_conf_filter):
+            raise NotImplementedError("context_nums and the confidence filter are not built for a view-sharded handle")
         B = int(views["img"].shape[0]) if views["img"].dim() == 5 else 1
         if B == 1:
             return self._forward_one(views, cond_flags, 0)
@@ -476,14 +502,20 @@ class WorldMirror:
             raw = {"means": raw["means"].reshape(1, M, 3), "quats": raw["quats"].reshape(1, M, 4),
                    "scales": raw["scales"].reshape(1, M, 3), "opacities": raw["opacities"].reshape(1, M),
                    "sh": raw["sh"].reshape(1, M, 1, 3), "weights": raw["weights"].reshape(1, M)}
+            n_ctx = int(views.get("context_nums", S))   # checked in forward(); only an unsharded handle (n == S) gets here with the key
+            if n_ctx < S:   # the context views' rows (rasterization.py:412): views of the forward's tensors, not copies
+                raw = {k: v[:, :n_ctx * H * W] for k, v in raw.items()}
             res["splats_raw"] = raw
+            src = raw
+            if self.gs_renderer.enable_conf_filter and "depth_conf" in res:   # rasterization.py:211-213, with the [:S] cut it forgets
+                src = self.gs_renderer.apply_confidence_filter(raw, res["depth_conf"][:, :n_ctx])
             if self.enable_prune:
                 # prune_gs merges voxels over ALL views (rasterization.py:301-387): the one cross-view step behind the forward.
                 # A sharded forward gathers the ranks' raw splats (global view order) and every rank merges the full set, so
                 # preds["splats"] is the reference's on every rank (not world separately merged sets)
-                res["splats"] = prune_gs(self._gather_splats(raw, world) if world > 1 else raw)
+                res["splats"] = prune_gs(self._gather_splats(src, world) if world > 1 else src)
             else:
-                res["splats"] = raw
+                res["splats"] = src
         self._keepalive = (img_l, pose_l, ray_l, depth_l)
         return res
 

@@ -285,6 +285,26 @@ wm_status wm_preprocess_image(const unsigned char* rgb, int H, int W, int mode, 
 size_t wm_confidence_mask_workspace_bytes(size_t n);
 wm_status wm_confidence_mask(const float* conf, size_t n, double conf_threshold_percent, unsigned char* mask, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* The same select with the count given instead of a percentage: mask[i] = 1 for the k highest confidences, 1 <= k <= n, all other rules
+ * (conf <= 1e-5 -> -inf, NaN above +inf, ties to the lowest indices) and the workspace as above.  It serves
+ * GaussianSplatRenderer.apply_confidence_filter (src/models/models/rasterization.py:248-299), whose count is capped by max_gaussians.
+ * WM_ERR_INVALID, before anything is launched: a NULL pointer, n < 1, k outside 1..n, n >= 2^32, a too small workspace. */
+wm_status wm_confidence_mask_count(const float* conf, size_t n, size_t k, unsigned char* mask, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+
+/* ---- novel-view path: the target-view validity mask (csrc/frustum.hip; reference: src/models/utils/frustum.py:26-89
+ * calculate_in_frustum_mask).  depth_1 [B][V1][H][W] (target views) and depth_2 [B][V2][H][W] (context views) contiguous fp32;
+ * kinv_1 [B][V1][3][3] = K1^-1; rel [B][V1][V2][3][4] = rows 0..2 of c2w_2[b][j]^-1 c2w_1[b][i]; k_2 [B][V2][3][3].  The caller takes the
+ * inverses once (the Python binding does, in fp64); the per-pixel arithmetic is fp32, the division by z one hardware reciprocal (1 ulp).
+ * mask [B][V1][H][W] u8:
+ *   mask = any_j(0 < px_j < W && 0 < py_j < H) && depth_1 > 1e-6 && any_j(isclose(z_j, sample_j, atol = 0.1, rtol = 1e-5))
+ * for (px_j, py_j, z_j) the pixel's point projected into context view j (divided by z without a z > 0 test, as the reference) and
+ * sample_j the bilinear, zero-padded sample of depth_2[b][j] at (px_j - 0.5, py_j - 0.5) (grid_sample, align_corners = False); a NaN on
+ * either side of the comparison gives false; the two any are independent.  One kernel, no workspace, no atomics: the same bits on
+ * every run.  Device pointers, stream-ordered.  WM_ERR_INVALID, before anything is launched: a NULL pointer, a size < 1,
+ * B V1 H W or B V2 H W >= 2^31, B V1 V2 >= 2^24. */
+wm_status wm_in_frustum_mask(const float* depth_1, const float* depth_2, const float* kinv_1, const float* rel, const float* k_2, int B,
+                             int V1, int V2, int H, int W, unsigned char* mask, void* stream);
 
 /* Point-cloud filter masks: the per-view mask app.py:172-206 (run_model) builds for every export.
  * All views are S x H x W, S*H*W < 2^31; k (window) is 3, 5 or 7; outputs are u8 0/1.  Bit-for-bit semantics of the
