@@ -20,3 +20,4 @@ from .metrics import (Evaluator, PeakSignalNoiseRatio, StructuralSimilarityIndex
                       ssim)
 from .glb import (GLBScene, convert_predictions_to_glb_scene, image_mesh, load_glb, save_camera_params)  # noqa: F401
 from .nvs import apply_confidence_filter, calculate_in_frustum_mask, calculate_unprojected_mask  # noqa: F401
+from .compression import PngCompression, kmeans_l1, sort_splats  # noqa: F401

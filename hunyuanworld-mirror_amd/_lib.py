@@ -82,6 +82,8 @@ EXPORTS = [
     "wm_masked_percentile_neighbours_workspace_bytes", "wm_masked_percentile_neighbours",
     "wm_eval_frame_workspace_bytes", "wm_eval_frame", "wm_color_correct_workspace_bytes", "wm_color_correct",
     "wm_confidence_mask_count", "wm_in_frustum_mask",
+    "wm_compress_minmax_workspace_bytes", "wm_compress_minmax", "wm_compress_quantise", "wm_compress_dequantise", "wm_gather_rows",
+    "wm_kmeans_l1_workspace_bytes", "wm_kmeans_l1", "wm_kmeans_l1_assign", "wm_grid_order_workspace_bytes", "wm_grid_order",
 ]
 
 _lib = None
@@ -274,6 +276,19 @@ def lib() -> C.CDLL:
     L.wm_color_correct_workspace_bytes.argtypes = [i32, i64]
     L.wm_color_correct_workspace_bytes.restype = C.c_size_t
     L.wm_color_correct.argtypes = [vp, vp, i32, i64, i32, f64, vp, vp, C.c_size_t, vp]
+    L.wm_compress_minmax_workspace_bytes.argtypes = [i64, i32]
+    L.wm_compress_minmax_workspace_bytes.restype = C.c_size_t
+    L.wm_compress_minmax.argtypes = [vp, i64, i32, vp, C.c_size_t, vp, vp, vp]
+    L.wm_compress_quantise.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp]
+    L.wm_compress_dequantise.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
+    L.wm_gather_rows.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i32), i32, vp, i64, vp]
+    L.wm_kmeans_l1_workspace_bytes.argtypes = [i64, i32, i32]
+    L.wm_kmeans_l1_workspace_bytes.restype = C.c_size_t
+    L.wm_kmeans_l1.argtypes = [vp, i64, i32, i32, vp, i32, f64, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+    L.wm_kmeans_l1_assign.argtypes = [vp, i64, i32, vp, i32, vp, vp, vp]
+    L.wm_grid_order_workspace_bytes.argtypes = [i32]
+    L.wm_grid_order_workspace_bytes.restype = C.c_size_t
+    L.wm_grid_order.argtypes = [vp, i32, vp, C.c_size_t, vp, vp, vp]
     L.wm_appearance_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.wm_appearance_backward_workspace_bytes.argtypes = [i32, i32]
     L.wm_appearance_backward_workspace_bytes.restype = C.c_size_t

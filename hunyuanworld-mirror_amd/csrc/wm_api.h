@@ -1,4 +1,4 @@
-// What the C-ABI entry files (wm_api_ops.cpp, wm_api_scene.cpp) share: the public header, the launcher interface and the status mapping.
+// What the C-ABI entry files (wm_api_ops.cpp, wm_api_scene.cpp, wm_api_compress.cpp) share: the public header, the launcher interface and the status mapping.
 #pragma once
 #include "../../include/wm_hip.h"
 #include "wm_kernels.h"
@@ -31,6 +31,28 @@ hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors,
 // No synchronisation.  1 <= K <= 16, K <= N < 2^31.
 size_t wm_knn_ws_bytes(long long N, int K);      // 0 for sizes the launcher refuses
 hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspace, float* dist, int* idx, int* nonfinite_flag, hipStream_t s);
+
+// ------------------------------------------------------------------ PNG compression of splats (compress.hip), entries in wm_api_compress.cpp
+// None of these synchronises.  mm [2 C]: C minima, then C maxima.  *nonfinite_flag (device) is set to 1 for a NaN or infinite value and
+// otherwise left as it is: the caller zeroes it once and reads it once.
+size_t wm_compress_minmax_ws_bytes(long long rows, int C);      // 0 for sizes the launcher refuses (C in 1..16)
+hipError_t wm_launch_compress_minmax(const float* x, long long rows, int C, void* workspace, float* mm, int* nonfinite_flag, hipStream_t s);
+// bits <= 8: one plane lo (hi null); bits 9..16: the low and the high bytes
+hipError_t wm_launch_compress_quantise(const float* x, long long rows, int C, const float* mm, int bits, unsigned char* lo, unsigned char* hi, hipStream_t s);
+hipError_t wm_launch_compress_dequantise(const unsigned char* lo, const unsigned char* hi, long long rows, int C, const float* mm, int bits, float* out,
+                                         hipStream_t s);
+// dst_f[r, :] = src_f[idx[r], :] for n_fields <= 16 fields of row_bytes[f] bytes per row (host arrays), rows < 2^31; idx values are the caller's to bound
+hipError_t wm_launch_gather_rows(const void* const* src, void* const* dst, const int* row_bytes, int n_fields, const int* idx, long long rows, hipStream_t s);
+// Lloyd under L1 distance (semantics: include/wm_hip.h).  D in {9, 24, 45}, 1 <= K <= 65536, K <= N <= 2^30.  info (device, 2 ints): the
+// iterations run, and 1 when an init row was outside 0 .. N-1 (row 0 was taken in its place).  labels_last may be null.
+size_t wm_kmeans_l1_ws_bytes(long long N, int D, int K);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_kmeans_l1(const float* x, long long N, int D, int K, const long long* init, int max_iter, double tol, void* workspace, int* labels,
+                               int* labels_last, float* centroids, double* errors, int* info, hipStream_t s);
+// one assignment on its own: labels [N] and dist [N] (the fp32 L1 distance to the chosen centroid) of x [N, D] against centroids [K, D]; N >= 1
+hipError_t wm_launch_kmeans_l1_assign(const float* x, long long N, int D, const float* centroids, int K, int* labels, float* dist, hipStream_t s);
+// perm [n^2]: the row of means [n^2, 3] that goes to every cell of the n x n grid.  1 <= n_side <= 46340.
+size_t wm_grid_order_ws_bytes(int n_side);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_grid_order(const float* means, int n_side, void* workspace, int* perm, int* nonfinite_flag, hipStream_t s);
 
 // ------------------------------------------------------------------ fly-through video (video.hip), entries in wm_api_scene.cpp
 // GSEffects.apply_effect, effect_type 2, on (means - shift) * inv_scale, scales * inv_scale and rgb or degree-0 SH colours; shift [3] on the

@@ -986,6 +986,53 @@ size_t wm_color_correct_workspace_bytes(int n_systems, int64_t n_pixels);
 wm_status wm_color_correct(const float* img, const float* ref, int n_systems, int64_t n_pixels, int num_iters, double eps, float* out,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG compression of trained splats (csrc/compress.hip): the device side of gsplat.compression.PngCompression
+ * (gsplat/compression/png_compression.py) as the trainer's run_compression calls it (simple_trainer_worldmirror.py:1293-1307).  All pointers
+ * are device pointers unless said otherwise; no entry synchronises; every entry returns WM_ERR_INVALID before anything is launched for a
+ * null pointer (other than the optional ones), a size it refuses or a too small workspace.
+ *
+ * wm_compress_minmax: mm [2 C] fp32 = the C per-channel minima, then the C maxima, of x [rows, C] (C in 1..16); NaN enters neither.
+ *   *nonfinite_flag (one int) is set to 1 when x holds a NaN or an infinity and is otherwise left as it is: the caller zeroes it before the
+ *   first call of a batch and reads it once after the last.  Two-level block reduction, no atomics, the same bits on every run.
+ * wm_compress_quantise: code = rint(((x - min) / (max - min)) * (2^bits - 1)) in fp32, every operation rounded on its own, the division
+ *   IEEE, rint half to even (numpy.round); a channel with max == min encodes as 0 (the reference divides 0 by 0).  bits <= 8: one byte
+ *   plane lo [rows, C], hi NULL; bits 9..16: the low bytes in lo and the high bytes in hi.
+ * wm_compress_dequantise: out = float(double(code) / (2^bits - 1) * double(float(max - min)) + double(min)), the reference's fp64 decoder,
+ *   every operation rounded on its own.  hi NULL exactly when bits <= 8.
+ * wm_gather_rows: dst_f[r, :] = src_f[idx[r], :] for r < rows and n_fields <= 16 fields in one launch.  src, dst (arrays of device pointers)
+ *   and row_bytes are HOST arrays of n_fields entries; idx [rows] int32 on the device, every value a row of each source (not checked).
+ *   A destination must not overlap a source.
+ * wm_kmeans_l1: Lloyd's algorithm under Manhattan distance on x [N, D] fp32, D in {9, 24, 45}, 1 <= K <= 65536, K <= N <= 2^30.
+ *   The initial centroids are the rows init [K] (int64).  Iteration t: (1) every row goes to the centroid of least L1 distance, the distance an
+ *   fp32 sum in the order d = 0 .. D-1, ties to the lowest index; (2) errors[t] = the mean assigned distance (fp64, fixed-order two-level
+ *   sum); (3) every centroid with members becomes the mean of its members (summed in row order in fp64, rounded once to fp32), a centroid
+ *   without members keeps its value.  The loop ends after max_iter iterations or after the first t > 0 with
+ *   |errors[t-1] - errors[t]| <= tol errors[t-1]; the rule is evaluated on the device and the later iterations' kernels return at once.
+ *   Then labels [N] int32 = one more assignment against the final centroids [K, D]; labels_last [N] (may be NULL) = the assignment of
+ *   the last iteration, whose member means the centroids are.  errors [max_iter] fp64, only the first info[0] written.  info [2] int32:
+ *   the iterations run, and 1 when an init row was outside 0 .. N-1 (row 0 was taken; the caller should refuse the result).
+ *   No float atomics anywhere: the same input and init give the same bits.  workspace: 20 N + 4 K bytes + the sort's scratch.
+ * wm_kmeans_l1_assign: step (1) on its own for x [N, D] (1 <= N <= 2^30) against a given table centroids [K, D]: labels [N] int32 and dist [N]
+ *   fp32, the L1 distance to the chosen centroid; the same arithmetic and tie rule, no workspace.
+ * wm_grid_order: perm [n_side^2] int32 = the row of means [n_side^2, 3] that goes to every cell (row-major) of the n_side x n_side grid:
+ *   the rows in the stable order of their 30-bit Morton codes (per-axis bounding box, 10 bits per axis) are laid along the cells in the
+ *   order of the cells' 2-D Morton codes.  Deterministic.  n_side in 1..46340.  nonfinite_flag as above.  workspace: 32 bytes per row + scratch. */
+size_t wm_compress_minmax_workspace_bytes(int64_t rows, int C);
+wm_status wm_compress_minmax(const float* x, int64_t rows, int C, void* workspace, size_t workspace_bytes, float* mm, int32_t* nonfinite_flag,
+                             void* stream);
+wm_status wm_compress_quantise(const float* x, int64_t rows, int C, const float* mm, int bits, unsigned char* lo, unsigned char* hi, void* stream);
+wm_status wm_compress_dequantise(const unsigned char* lo, const unsigned char* hi, int64_t rows, int C, const float* mm, int bits, float* out,
+                                 void* stream);
+wm_status wm_gather_rows(const void* const* src, void* const* dst, const int32_t* row_bytes, int n_fields, const int32_t* idx, int64_t rows,
+                         void* stream);
+size_t wm_kmeans_l1_workspace_bytes(int64_t N, int D, int K);
+wm_status wm_kmeans_l1(const float* x, int64_t N, int D, int K, const int64_t* init, int max_iter, double tol, void* workspace,
+                       size_t workspace_bytes, int32_t* labels, int32_t* labels_last, float* centroids, double* errors, int32_t* info, void* stream);
+wm_status wm_kmeans_l1_assign(const float* x, int64_t N, int D, const float* centroids, int K, int32_t* labels, float* dist, void* stream);
+size_t wm_grid_order_workspace_bytes(int n_side);
+wm_status wm_grid_order(const float* means, int n_side, void* workspace, size_t workspace_bytes, int32_t* perm, int32_t* nonfinite_flag,
+                        void* stream);
+
 /* Process-wide kernel-selection override for tests and A/B tools (no reference counterpart).  The keys are declared once, in
  * WM_TUNE_KEYS (csrc/wm_kernels.h); INTEGRATION.md lists each with its values and its default, in the same order.
  * value -1 restores the default.  Returns 0, or -1 for an unknown key. */
