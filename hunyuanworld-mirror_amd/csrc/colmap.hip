@@ -6,8 +6,9 @@
 // selection (wm_launch_colmap_select, wm_launch_colmap_gather)
 //   A pixel is a candidate when depth > eps (depth_to_world_coords_points' mask, elementwise.hip).  Candidates are ordered view-major and
 //   row-major inside a view.  Of the N_valid candidates the K = max(1, ceil(N_valid (100 - p) / 100)) highest confidences are kept (p <= 0:
-//   all of them), conf <= 1e-5 counting as -inf and ties at the K-th value going to the lowest candidate index: select.hip's rules, restated
-//   here because K depends on N_valid, which only the device knows.  Nothing of [S,H,W,3] is materialised and no index list is formed:
+//   all of them), conf <= 1e-5 counting as -inf (conf_key, scene_common.h) and ties at the K-th value going to the lowest candidate
+//   index: select.hip's rules, restated here because K depends on N_valid, which only the device knows.  Nothing of [S,H,W,3] is
+//   materialised and no index list is formed:
 //     count    per block, the number of candidates                                                  -> blk_off (as counts)
 //     setup    one block: N_valid, K, the select state
 //     hist / pick  4 x (8-bit histogram of the candidates' keys under the fixed prefix; walk the bins from the top): the K-th largest key
@@ -27,8 +28,8 @@
 //   come from the exclusive prefix of `counts` (the order is view-major), found by a search over the S + 1 offsets.
 #include <vector>
 
+#include "scene_common.h"
 #include "wm_api.h"
-#include "wm_common.h"
 
 namespace {
 
@@ -46,67 +47,19 @@ struct CmWs {
   size_t total;
 };
 
-size_t cm_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 unsigned cm_bpv(int H, int W) { return (unsigned)(((size_t)H * W + CM_CHUNK - 1) / CM_CHUNK); }
 
 CmWs cm_carve(char* base, int S, int H, int W) {
   CmWs w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += cm_align(b); return p; };
+  Carver c(base);
   const size_t nblk = (size_t)S * cm_bpv(H, W);
-  w.st = (CmState*)take(sizeof(CmState));
-  w.blk_gt = (unsigned int*)take((nblk + 1) * 4);
-  w.blk_eq = (unsigned int*)take((nblk + 1) * 4);
-  w.blk_off = (unsigned int*)take((nblk + 1) * 4);
-  w.res = (long long*)take(((size_t)S + 1) * 8);
-  w.total = o;
+  w.st = c.take<CmState>(1);
+  w.blk_gt = c.take<unsigned int>(nblk + 1);
+  w.blk_eq = c.take<unsigned int>(nblk + 1);
+  w.blk_off = c.take<unsigned int>(nblk + 1);
+  w.res = c.take<long long>((size_t)S + 1);
+  w.total = c.total();
   return w;
-}
-
-// select.hip's key (conf_key, kept identical): any NaN -> the one top key, conf <= 1e-5 -> -inf, then the order-preserving image of the float
-__device__ __forceinline__ unsigned int cm_key(float c) {
-  if (c != c) return 0xFFFFFFFFu;  // any NaN, either sign, any payload: the one top key, above +inf like torch.topk's NaN-largest
-  const float v = c <= 1e-5f ? -INFINITY : c;
-  const unsigned int u = __builtin_bit_cast(unsigned int, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone: larger float <=> larger key
-}
-
-// ordered rank of the lanes of a 256-thread block whose flag is set, and the number set; every lane calls it
-__device__ __forceinline__ unsigned int cm_block_rank(bool f, unsigned int* sW /* 4 */, unsigned int& total) {
-  const unsigned long long b = __ballot(f);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned int r = (unsigned int)__popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();      // sW may still be read from the call before
-  if (lane == 0) sW[w] = (unsigned int)__popcll(b);
-  __syncthreads();
-  unsigned int base = 0;
-  total = 0;
-#pragma unroll
-  for (int i = 0; i < CM_THREADS / 64; ++i) {
-    if (i < w) base += sW[i];
-    total += sW[i];
-  }
-  return base + r;
-}
-
-// in-place exclusive scan of v[0 .. n) by ONE 256-thread block; v[n] receives the total
-__device__ void cm_scan_in_place(unsigned int* v, unsigned int n, unsigned int* part /* 256, shared */) {
-  const unsigned int per = (n + CM_THREADS - 1) / CM_THREADS, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  unsigned int s = 0;
-  for (unsigned int i = lo; i < hi; ++i) s += v[i];
-  __syncthreads();
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int run = 0;
-    for (int i = 0; i < CM_THREADS; ++i) { const unsigned int t = part[i]; part[i] = run; run += t; }
-    v[n] = run;
-  }
-  __syncthreads();
-  unsigned int run = part[threadIdx.x];
-  for (unsigned int i = lo; i < hi; ++i) { const unsigned int t = v[i]; v[i] = run; run += t; }
-  __syncthreads();
 }
 
 struct CmPix { bool valid; unsigned int key; size_t idx; int p; };
@@ -119,7 +72,7 @@ __device__ __forceinline__ CmPix cm_pixel(const float* __restrict__ depth, const
   px.p = (int)p;
   px.idx = (size_t)v * hw + (size_t)p;
   px.valid = p < hw && depth[px.idx] > eps;      // NaN compares false
-  px.key = px.valid ? cm_key(conf[px.idx]) : 0u;
+  px.key = px.valid ? conf_key(conf[px.idx]) : 0u;
   return px;
 }
 
@@ -132,7 +85,7 @@ __global__ __launch_bounds__(CM_THREADS) void cm_valid_count_kernel(const float*
   for (int r = 0; r < CM_ROUNDS; ++r) {
     const long long p = (long long)c * CM_CHUNK + r * CM_THREADS + threadIdx.x;
     const bool ok = p < hw && depth[(size_t)v * hw + (size_t)p] > eps;
-    cm_block_rank(ok, sW, tot);
+    block_rank<CM_THREADS>(ok, sW, tot);
     cnt += tot;
   }
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cnt;
@@ -202,9 +155,9 @@ __global__ __launch_bounds__(CM_THREADS) void cm_count_kernel(const float* __res
 #pragma unroll
   for (int r = 0; r < CM_ROUNDS; ++r) {
     const CmPix px = cm_pixel(depth, conf, hw, bpv, eps, r);
-    cm_block_rank(px.valid && px.key > kth, sW, tot);
+    block_rank<CM_THREADS>(px.valid && px.key > kth, sW, tot);
     gt += tot;
-    cm_block_rank(px.valid && px.key == kth, sW, tot);
+    block_rank<CM_THREADS>(px.valid && px.key == kth, sW, tot);
     eq += tot;
   }
   if (threadIdx.x == 0) { blk_gt[blockIdx.x] = gt; blk_eq[blockIdx.x] = eq; }
@@ -217,13 +170,13 @@ __global__ __launch_bounds__(CM_THREADS) void cm_scan_kernel(const unsigned int*
   const unsigned int need = st->nvalid ? st->need_eq : 0u;
   const unsigned int per = (nblk + CM_THREADS - 1) / CM_THREADS, lo = threadIdx.x * per, hi = lo + per < nblk ? lo + per : nblk;
   for (unsigned int i = lo; i < hi; ++i) blk_off[i] = blk_eq[i];      // the tie counts themselves: the scan below overwrites blk_eq
-  cm_scan_in_place(blk_eq, nblk, part);
+  block_scan_in_place<CM_THREADS>(blk_eq, nblk, part);
   for (unsigned int i = lo; i < hi; ++i) {
     const unsigned int before = blk_eq[i], eq = blk_off[i];
     const unsigned int left = need > before ? need - before : 0u;
     blk_off[i] = blk_gt[i] + (left < eq ? left : eq);
   }
-  cm_scan_in_place(blk_off, nblk, part);
+  block_scan_in_place<CM_THREADS>(blk_off, nblk, part);
   for (int v = threadIdx.x; v <= S; v += CM_THREADS)
     res[v] = v < S ? (long long)blk_off[(size_t)(v + 1) * bpv] - (long long)blk_off[(size_t)v * bpv] : (long long)blk_off[nblk];
 }
@@ -243,10 +196,10 @@ __global__ __launch_bounds__(CM_THREADS) void cm_gather_kernel(const float* __re
   for (int r = 0; r < CM_ROUNDS; ++r) {
     const CmPix px = cm_pixel(depth, conf, hw, bpv, eps, r);
     const bool is_eq = px.valid && px.key == kth;
-    const unsigned int eq_rank = eq_run + cm_block_rank(is_eq, sW, tot);
+    const unsigned int eq_rank = eq_run + block_rank<CM_THREADS>(is_eq, sW, tot);
     eq_run += tot;
     const bool keep = px.valid && (px.key > kth || (is_eq && eq_rank < need));
-    const unsigned int pos = out_run + cm_block_rank(keep, sW, tot);
+    const unsigned int pos = out_run + block_rank<CM_THREADS>(keep, sW, tot);
     out_run += tot;
     if (keep && pos < n_kept) {
       const int y = px.p / W, x = px.p - y * W;
@@ -341,13 +294,11 @@ __global__ __launch_bounds__(CM_THREADS) void cm_pack_points2d_kernel(const int*
 }
 
 // ---- point-cloud PLY rows: 3 f32 | 3 u8
-__device__ __forceinline__ bool cm_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }      // false for NaN
-
 __device__ __forceinline__ bool cm_ply_keep(const float* __restrict__ points, const unsigned char* __restrict__ keep, int filter_finite, long long N) {
   const long long i = (long long)blockIdx.x * CM_THREADS + threadIdx.x;
   if (i >= N) return false;
   if (keep) return keep[i] != 0;
-  if (filter_finite) return cm_finite(points[3 * i]) && cm_finite(points[3 * i + 1]) && cm_finite(points[3 * i + 2]);
+  if (filter_finite) return finite_f32(points[3 * i]) && finite_f32(points[3 * i + 1]) && finite_f32(points[3 * i + 2]);
   return true;
 }
 
@@ -355,13 +306,13 @@ __global__ __launch_bounds__(CM_THREADS) void cm_ply_count_kernel(const float* _
                                                                   long long N, unsigned int* __restrict__ blk_cnt) {
   __shared__ unsigned int sW[CM_THREADS / 64];
   unsigned int tot;
-  cm_block_rank(cm_ply_keep(points, keep, filter_finite, N), sW, tot);
+  block_rank<CM_THREADS>(cm_ply_keep(points, keep, filter_finite, N), sW, tot);
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(CM_THREADS) void cm_scan1_kernel(unsigned int* blk, unsigned int nblk) {
   __shared__ unsigned int part[CM_THREADS];
-  cm_scan_in_place(blk, nblk, part);
+  block_scan_in_place<CM_THREADS>(blk, nblk, part);
 }
 
 __global__ __launch_bounds__(CM_THREADS) void cm_ply_scatter_kernel(const float* __restrict__ points, const unsigned char* __restrict__ keep, int filter_finite,
@@ -369,7 +320,7 @@ __global__ __launch_bounds__(CM_THREADS) void cm_ply_scatter_kernel(const float*
   __shared__ unsigned int sW[CM_THREADS / 64];
   unsigned int tot;
   const bool k = cm_ply_keep(points, keep, filter_finite, N);
-  const unsigned int pos = blk_off[blockIdx.x] + cm_block_rank(k, sW, tot);
+  const unsigned int pos = blk_off[blockIdx.x] + block_rank<CM_THREADS>(k, sW, tot);
   if (k) kept[pos] = (unsigned int)((long long)blockIdx.x * CM_THREADS + threadIdx.x);
 }
 
@@ -391,8 +342,6 @@ __global__ __launch_bounds__(CM_THREADS) void cm_pack_ply_kernel(const float* __
   const long long left = n - (long long)blockIdx.x * CM_THREADS;
   cm_flush<REC>(sRec, (int)(left < CM_THREADS ? left : CM_THREADS), out);
 }
-
-unsigned cm_blocks(long long n) { return (unsigned)((n + CM_THREADS - 1) / CM_THREADS); }
 
 bool cm_select_sizes_ok(int S, int H, int W) { return S >= 1 && H >= 1 && W >= 1 && (long long)S * H * W < (1LL << 31); }
 
@@ -422,9 +371,7 @@ hipError_t wm_launch_colmap_select(const float* depth, const float* conf, int S,
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   std::vector<long long> res((size_t)S + 1);
-  e = hipMemcpyAsync(res.data(), w.res, res.size() * 8, hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);      // the one synchronisation: the caller sizes its outputs by *n_kept
+  e = read_back(res.data(), w.res, res.size() * 8, s);      // the one synchronisation: the caller sizes its outputs by *n_kept
   if (e != hipSuccess) return e;
   for (int v = 0; v < S; ++v) counts[v] = res[v];
   *n_kept = res[S];
@@ -445,7 +392,7 @@ hipError_t wm_launch_colmap_gather(const float* depth, const float* conf, const 
 
 size_t wm_colmap_pack_ws_bytes(long long P, int S) {
   if (P < 0 || P >= (1LL << 31) || S < 1) return 0;
-  return cm_align(((size_t)S + 1) * 8);
+  return align256(((size_t)S + 1) * 8);
 }
 
 hipError_t wm_launch_colmap_pack(const float* points, const unsigned char* colors, const int* xyf, const long long* counts, int S, long long P,
@@ -455,18 +402,18 @@ hipError_t wm_launch_colmap_pack(const float* points, const unsigned char* color
   long long* offs = (long long*)workspace;
   if (points3d) {
     hipLaunchKernelGGL(cm_offsets_kernel, dim3(1), dim3(64), 0, s, counts, S, offs);
-    hipLaunchKernelGGL(cm_pack_points3d_kernel, dim3(cm_blocks(P)), dim3(CM_THREADS), 0, s, points, colors, (const long long*)offs, S, P,
+    hipLaunchKernelGGL(cm_pack_points3d_kernel, dim3(blocks_for(P, CM_THREADS)), dim3(CM_THREADS), 0, s, points, colors, (const long long*)offs, S, P,
                        (unsigned char*)points3d);
   }
   if (points2d)
-    hipLaunchKernelGGL(cm_pack_points2d_kernel, dim3(cm_blocks(3 * P)), dim3(CM_THREADS), 0, s, xyf, P, (unsigned long long*)points2d);
+    hipLaunchKernelGGL(cm_pack_points2d_kernel, dim3(blocks_for(3 * P, CM_THREADS)), dim3(CM_THREADS), 0, s, xyf, P, (unsigned long long*)points2d);
   return hipGetLastError();
 }
 
 size_t wm_point_ply_ws_bytes(long long N) {
   if (N < 0 || N >= (1LL << 31)) return 0;
   const size_t rows = (size_t)(N > 0 ? N : 1);
-  return cm_align(((size_t)cm_blocks((long long)rows) + 1) * 4) + cm_align(rows * 4);
+  return align256(((size_t)blocks_for((long long)rows, CM_THREADS) + 1) * 4) + align256(rows * 4);
 }
 
 hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors, const unsigned char* keep, int filter_finite, long long N,
@@ -474,21 +421,19 @@ hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors,
   if (N < 0 || N >= (1LL << 31)) return hipErrorInvalidValue;
   *n_kept = 0;
   if (N == 0) return hipSuccess;
-  const unsigned nblk = cm_blocks(N);
+  const unsigned nblk = blocks_for(N, CM_THREADS);
   const unsigned int* kept = nullptr;
   long long n = N;
   if (keep || filter_finite) {
     unsigned int* blk = (unsigned int*)workspace;
-    unsigned int* list = (unsigned int*)((char*)workspace + cm_align(((size_t)nblk + 1) * 4));
+    unsigned int* list = (unsigned int*)((char*)workspace + align256(((size_t)nblk + 1) * 4));
     hipLaunchKernelGGL(cm_ply_count_kernel, dim3(nblk), dim3(CM_THREADS), 0, s, points, keep, filter_finite, N, blk);
     hipLaunchKernelGGL(cm_scan1_kernel, dim3(1), dim3(CM_THREADS), 0, s, blk, nblk);
     hipLaunchKernelGGL(cm_ply_scatter_kernel, dim3(nblk), dim3(CM_THREADS), 0, s, points, keep, filter_finite, N, (const unsigned int*)blk, list);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     unsigned int total = 0;
-    e = hipMemcpyAsync(&total, blk + nblk, 4, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(s);
+    e = read_back(&total, blk + nblk, 4, s);
     if (e != hipSuccess) return e;
     if ((long long)total > N) return hipErrorUnknown;
     n = total;
@@ -496,6 +441,6 @@ hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors,
   }
   *n_kept = n;
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(cm_pack_ply_kernel, dim3(cm_blocks(n)), dim3(CM_THREADS), 0, s, points, colors, kept, n, (unsigned char*)out);
+  hipLaunchKernelGGL(cm_pack_ply_kernel, dim3(blocks_for(n, CM_THREADS)), dim3(CM_THREADS), 0, s, points, colors, kept, n, (unsigned char*)out);
   return hipGetLastError();
 }

@@ -27,12 +27,10 @@
 //   grid order    30-bit Morton codes of the means (per-axis bounding box, 10 bits per axis: floor((x - min) / (max - min) * 1024) held to
 //                 0 .. 1023, an axis of zero extent divides by 1), stable sort; 2-D Morton codes (row, col) of the n x n cells, same sort;
 //                 perm[cell of rank i] = row of rank i.
-#include <hipcub/hipcub.hpp>
-
 #include <climits>
 
+#include "scene_common.h"
 #include "wm_api.h"
-#include "wm_common.h"
 
 #pragma clang fp contract(off)
 
@@ -43,26 +41,12 @@ typedef unsigned char u8;
 constexpr int CP_THREADS = 256;
 constexpr int CP_WAVES = CP_THREADS / 64;
 constexpr int CP_MAX_BLOCKS = 1024;      // level-1 blocks of the two-level reductions
-constexpr float CP_FLT_MAX = 3.4028234663852886e38f;
-
-size_t cp_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ float cp_wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float cp_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 // ------------------------------------------------------------------ minmax
 // partials: per block 2 C + 1 floats (C mins, C maxs, 1.0 when a value was NaN or infinite).  Every lane of the block calls cp_block_out.
 __device__ __forceinline__ void cp_block_out(float lo, float hi, float* sLo, float* sHi, float* out_lo, float* out_hi) {
-  lo = cp_wave_min(lo);
-  hi = cp_wave_max(hi);
+  lo = wave_min(lo);
+  hi = wave_max(hi);
   const int tid = threadIdx.x;
   if ((tid & 63) == 0) { sLo[tid >> 6] = lo; sHi[tid >> 6] = hi; }
   __syncthreads();
@@ -86,7 +70,7 @@ __global__ __launch_bounds__(CP_THREADS) WM_NO_PACKED_FP32 void cp_minmax_kernel
     float lo = INFINITY, hi = -INFINITY;
     for (long long r = r0 + threadIdx.x; r < r1; r += CP_THREADS) {
       const float v = x[r * C + c];
-      if (!(fabsf(v) <= CP_FLT_MAX)) bad = 1.f;
+      if (!finite_f32(v)) bad = 1.f;
       lo = fminf(lo, v);
       hi = fmaxf(hi, v);
     }
@@ -276,22 +260,18 @@ struct KmWs { KmState* st; float* dist; int* labels; unsigned int* keys_sorted; 
 
 KmWs km_carve(char* base, size_t N, size_t K) {
   KmWs w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += cp_align(b); return p; };
-  w.st = (KmState*)take(sizeof(KmState));
-  w.dist = (float*)take(N * 4);
-  w.labels = (int*)take(N * 4);
-  w.keys_sorted = (unsigned int*)take(N * 4);
-  w.rows = (unsigned int*)take(N * 4);
-  w.rows_sorted = (unsigned int*)take(N * 4);
-  w.off = (int*)take((K + 1) * 4);
-  w.part = (double*)take(CP_MAX_BLOCKS * 8);
-  size_t tb = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const unsigned int*)nullptr, (unsigned int*)nullptr, (const unsigned int*)nullptr,
-                                           (unsigned int*)nullptr, (int)N, 0, 16);
-  w.cub_bytes = tb;
-  w.cub = take(tb ? tb : 4);
-  w.total = o;
+  Carver c(base);
+  w.st = c.take<KmState>(1);
+  w.dist = c.take<float>(N);
+  w.labels = c.take<int>(N);
+  w.keys_sorted = c.take<unsigned int>(N);
+  w.rows = c.take<unsigned int>(N);
+  w.rows_sorted = c.take<unsigned int>(N);
+  w.off = c.take<int>(K + 1);
+  w.part = c.take<double>(CP_MAX_BLOCKS);
+  w.cub_bytes = sort_pairs_copy_bytes<unsigned int, unsigned int>((int)N, 0, 16);
+  w.cub = c.take<char>(w.cub_bytes ? w.cub_bytes : 4);
+  w.total = c.total();
   return w;
 }
 
@@ -299,7 +279,7 @@ bool km_sizes_ok(long long N, int D, int K) { return (D == 9 || D == 24 || D == 
 
 template <int D>
 void km_assign(const float* x, int N, const float* cent, int K, int t, const KmState* st, int* labels, float* dist, hipStream_t s) {
-  hipLaunchKernelGGL(km_assign_kernel<D>, dim3((unsigned)((N + CP_THREADS - 1) / CP_THREADS)), dim3(CP_THREADS), 0, s, x, N, cent, K, t, st, labels, dist);
+  hipLaunchKernelGGL(km_assign_kernel<D>, dim3(blocks_for(N, CP_THREADS)), dim3(CP_THREADS), 0, s, x, N, cent, K, t, st, labels, dist);
 }
 void km_assign_any(int D, const float* x, int N, const float* cent, int K, int t, const KmState* st, int* labels, float* dist, hipStream_t s) {
   if (D == 9) km_assign<9>(x, N, cent, K, t, st, labels, dist, s);
@@ -308,23 +288,6 @@ void km_assign_any(int D, const float* x, int N, const float* cent, int K, int t
 }
 
 // ------------------------------------------------------------------ grid order
-__device__ __forceinline__ unsigned int cp_part1by2(unsigned int x) {      // 10 bits -> every third bit of 30
-  x &= 0x000003ffu;
-  x = (x ^ (x << 16)) & 0xff0000ffu;
-  x = (x ^ (x << 8)) & 0x0300f00fu;
-  x = (x ^ (x << 4)) & 0x030c30c3u;
-  x = (x ^ (x << 2)) & 0x09249249u;
-  return x;
-}
-__device__ __forceinline__ unsigned int cp_part1by1(unsigned int x) {      // 16 bits -> every second bit of 32
-  x &= 0x0000ffffu;
-  x = (x ^ (x << 8)) & 0x00ff00ffu;
-  x = (x ^ (x << 4)) & 0x0f0f0f0fu;
-  x = (x ^ (x << 2)) & 0x33333333u;
-  x = (x ^ (x << 1)) & 0x55555555u;
-  return x;
-}
-
 __global__ __launch_bounds__(CP_THREADS) WM_NO_PACKED_FP32 void cp_morton3_kernel(const float* __restrict__ means, long long N, const float* __restrict__ mm,
                                                                                   unsigned int* __restrict__ keys, unsigned int* __restrict__ vals) {
   const long long i = (long long)blockIdx.x * CP_THREADS + threadIdx.x;
@@ -338,7 +301,7 @@ __global__ __launch_bounds__(CP_THREADS) WM_NO_PACKED_FP32 void cp_morton3_kerne
     const float s = floorf(__fmul_rn(__fdiv_rn(__fsub_rn(means[3 * i + j], lo), len), 1024.f));
     q[j] = (unsigned int)fminf(fmaxf(s, 0.f), 1023.f);      // the maximum itself gives 1024; NaN -> 0
   }
-  keys[i] = (cp_part1by2(q[2]) << 2) | (cp_part1by2(q[1]) << 1) | cp_part1by2(q[0]);
+  keys[i] = (part1by2_10(q[2]) << 2) | (part1by2_10(q[1]) << 1) | part1by2_10(q[0]);
   vals[i] = (unsigned int)i;
 }
 
@@ -346,7 +309,7 @@ __global__ __launch_bounds__(CP_THREADS) void cp_morton2_kernel(int n, long long
   const long long c = (long long)blockIdx.x * CP_THREADS + threadIdx.x;
   if (c >= N) return;
   const unsigned int row = (unsigned int)(c / n), col = (unsigned int)(c - (long long)row * n);
-  keys[c] = (cp_part1by1(row) << 1) | cp_part1by1(col);
+  keys[c] = (part1by1_16(row) << 1) | part1by1_16(col);
   vals[c] = (unsigned int)c;
 }
 
@@ -366,21 +329,15 @@ struct GoWs { float* mm; float* partials; unsigned int* keys[2]; unsigned int* v
 
 GoWs go_carve(char* base, size_t N) {
   GoWs w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += cp_align(b); return p; };
-  w.mm = (float*)take(6 * 4);
-  w.partials = (float*)take(cp_minmax_partial_bytes(3));
-  for (int b = 0; b < 2; ++b) { w.keys[b] = (unsigned int*)take(N * 4); w.vals[b] = (unsigned int*)take(N * 4); }
-  for (int b = 0; b < 2; ++b) { w.ckeys[b] = (unsigned int*)take(N * 4); w.cvals[b] = (unsigned int*)take(N * 4); }
-  size_t tb = 0;
-  hipcub::DoubleBuffer<unsigned int> dk((unsigned int*)nullptr, (unsigned int*)nullptr), dv((unsigned int*)nullptr, (unsigned int*)nullptr);
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (int)N, 0, 32);
-  size_t tb30 = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb30, dk, dv, (int)N, 0, 30);
-  tb = tb > tb30 ? tb : tb30;
-  w.cub_bytes = tb;
-  w.cub = take(tb ? tb : 4);
-  w.total = o;
+  Carver c(base);
+  w.mm = c.take<float>(6);
+  w.partials = (float*)c.take<char>(cp_minmax_partial_bytes(3));
+  for (int b = 0; b < 2; ++b) { w.keys[b] = c.take<unsigned int>(N); w.vals[b] = c.take<unsigned int>(N); }
+  for (int b = 0; b < 2; ++b) { w.ckeys[b] = c.take<unsigned int>(N); w.cvals[b] = c.take<unsigned int>(N); }
+  const size_t tb32 = sort_pairs_bytes<unsigned int, unsigned int>((int)N, 0, 32), tb30 = sort_pairs_bytes<unsigned int, unsigned int>((int)N, 0, 30);
+  w.cub_bytes = tb32 > tb30 ? tb32 : tb30;
+  w.cub = c.take<char>(w.cub_bytes ? w.cub_bytes : 4);
+  w.total = c.total();
   return w;
 }
 
@@ -393,8 +350,6 @@ hipError_t cp_minmax(const float* x, long long rows, int C, float* partials, flo
   hipLaunchKernelGGL(cp_minmax_final_kernel, dim3(1), dim3(CP_THREADS), 0, s, (const float*)partials, (int)nb, C, mm, flag);
   return hipGetLastError();
 }
-
-unsigned cp_blocks(long long total) { return (unsigned)((total + CP_THREADS - 1) / CP_THREADS); }
 
 }  // namespace
 
@@ -411,14 +366,14 @@ hipError_t wm_launch_compress_minmax(const float* x, long long rows, int C, void
 hipError_t wm_launch_compress_quantise(const float* x, long long rows, int C, const float* mm, int bits, unsigned char* lo, unsigned char* hi, hipStream_t s) {
   if (rows < 1 || C < 1 || C > 16 || rows > (1LL << 40) / C || bits < 1 || bits > 16 || (bits > 8) != (hi != nullptr)) return hipErrorInvalidValue;
   const long long total = rows * C;
-  hipLaunchKernelGGL(cp_quantise_kernel, dim3(cp_blocks(total)), dim3(CP_THREADS), 0, s, x, total, C, mm, (float)((1 << bits) - 1), lo, hi);
+  hipLaunchKernelGGL(cp_quantise_kernel, dim3(blocks_for(total, CP_THREADS)), dim3(CP_THREADS), 0, s, x, total, C, mm, (float)((1 << bits) - 1), lo, hi);
   return hipGetLastError();
 }
 hipError_t wm_launch_compress_dequantise(const unsigned char* lo, const unsigned char* hi, long long rows, int C, const float* mm, int bits, float* out,
                                          hipStream_t s) {
   if (rows < 1 || C < 1 || C > 16 || rows > (1LL << 40) / C || bits < 1 || bits > 16 || (bits > 8) != (hi != nullptr)) return hipErrorInvalidValue;
   const long long total = rows * C;
-  hipLaunchKernelGGL(cp_dequantise_kernel, dim3(cp_blocks(total)), dim3(CP_THREADS), 0, s, lo, hi, total, C, mm, (double)((1 << bits) - 1), out);
+  hipLaunchKernelGGL(cp_dequantise_kernel, dim3(blocks_for(total, CP_THREADS)), dim3(CP_THREADS), 0, s, lo, hi, total, C, mm, (double)((1 << bits) - 1), out);
   return hipGetLastError();
 }
 
@@ -455,7 +410,7 @@ hipError_t wm_launch_kmeans_l1(const float* x, long long N, int D, int K, const 
   hipError_t e = hipMemsetAsync(w.st, 0, sizeof(KmState), s);
   if (e != hipSuccess) return e;
   const long long most = N > (long long)K * D ? N : (long long)K * D;
-  hipLaunchKernelGGL(km_init_kernel, dim3(cp_blocks(most)), dim3(CP_THREADS), 0, s, x, N, D, init, K, centroids, w.rows, w.st);
+  hipLaunchKernelGGL(km_init_kernel, dim3(blocks_for(most, CP_THREADS)), dim3(CP_THREADS), 0, s, x, N, D, init, K, centroids, w.rows, w.st);
   long long nb = (N + CP_THREADS - 1) / CP_THREADS;
   if (nb > CP_MAX_BLOCKS) nb = CP_MAX_BLOCKS;
   const long long per = (N + nb - 1) / nb;
@@ -466,11 +421,10 @@ hipError_t wm_launch_kmeans_l1(const float* x, long long N, int D, int K, const 
     hipLaunchKernelGGL(km_err2_kernel, dim3(1), dim3(CP_THREADS), 0, s, (const double*)w.part, (int)nb, N, t, tol, w.st, errors);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    size_t tb = w.cub_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, (const unsigned int*)last, w.keys_sorted, (const unsigned int*)w.rows, w.rows_sorted, n, 0, 16, s);
+    e = sort_pairs(w.cub, w.cub_bytes, (const unsigned int*)last, w.keys_sorted, (const unsigned int*)w.rows, w.rows_sorted, n, 0, 16, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(km_offsets_kernel, dim3(cp_blocks(K + 1)), dim3(CP_THREADS), 0, s, (const unsigned int*)w.keys_sorted, n, K, t, (const KmState*)w.st, w.off);
-    hipLaunchKernelGGL(km_update_kernel, dim3(cp_blocks((long long)K * D)), dim3(CP_THREADS), 0, s, x, D, K, (const unsigned int*)w.rows_sorted,
+    hipLaunchKernelGGL(km_offsets_kernel, dim3(blocks_for(K + 1, CP_THREADS)), dim3(CP_THREADS), 0, s, (const unsigned int*)w.keys_sorted, n, K, t, (const KmState*)w.st, w.off);
+    hipLaunchKernelGGL(km_update_kernel, dim3(blocks_for((long long)K * D, CP_THREADS)), dim3(CP_THREADS), 0, s, x, D, K, (const unsigned int*)w.rows_sorted,
                        (const int*)w.off, t, (const KmState*)w.st, centroids);
   }
   km_assign_any(D, x, n, centroids, K, -1, w.st, labels, w.dist, s);      // the returned labels belong to the returned centroids
@@ -496,18 +450,16 @@ hipError_t wm_launch_grid_order(const float* means, int n_side, void* workspace,
   const GoWs w = go_carve((char*)workspace, (size_t)N);
   hipError_t e = cp_minmax(means, N, 3, w.partials, w.mm, nonfinite_flag, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cp_morton3_kernel, dim3(cp_blocks(N)), dim3(CP_THREADS), 0, s, means, N, (const float*)w.mm, w.keys[0], w.vals[0]);
-  hipLaunchKernelGGL(cp_morton2_kernel, dim3(cp_blocks(N)), dim3(CP_THREADS), 0, s, n_side, N, w.ckeys[0], w.cvals[0]);
+  hipLaunchKernelGGL(cp_morton3_kernel, dim3(blocks_for(N, CP_THREADS)), dim3(CP_THREADS), 0, s, means, N, (const float*)w.mm, w.keys[0], w.vals[0]);
+  hipLaunchKernelGGL(cp_morton2_kernel, dim3(blocks_for(N, CP_THREADS)), dim3(CP_THREADS), 0, s, n_side, N, w.ckeys[0], w.cvals[0]);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipcub::DoubleBuffer<unsigned int> dk(w.keys[0], w.keys[1]), dv(w.vals[0], w.vals[1]);
-  size_t tb = w.cub_bytes;
-  e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, dk, dv, (int)N, 0, 30, s);      // stable: equal codes stay in row order
+  e = sort_pairs(w.cub, w.cub_bytes, dk, dv, (int)N, 0, 30, s);      // stable: equal codes stay in row order
   if (e != hipSuccess) return e;
   hipcub::DoubleBuffer<unsigned int> ck(w.ckeys[0], w.ckeys[1]), cv(w.cvals[0], w.cvals[1]);
-  tb = w.cub_bytes;
-  e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, ck, cv, (int)N, 0, 32, s);
+  e = sort_pairs(w.cub, w.cub_bytes, ck, cv, (int)N, 0, 32, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cp_place_kernel, dim3(cp_blocks(N)), dim3(CP_THREADS), 0, s, (const unsigned int*)dv.Current(), (const unsigned int*)cv.Current(), N, perm);
+  hipLaunchKernelGGL(cp_place_kernel, dim3(blocks_for(N, CP_THREADS)), dim3(CP_THREADS), 0, s, (const unsigned int*)dv.Current(), (const unsigned int*)cv.Current(), N, perm);
   return hipGetLastError();
 }

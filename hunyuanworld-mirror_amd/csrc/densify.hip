@@ -12,10 +12,8 @@
 //               the split Gaussians (the row of the noise it uses); the four counts are read back after one stream synchronisation.
 //   gather      one [N, R] tensor -> [n_out, R] by the plan: plain copy, Adam moments (new rows zero), means (split children move by
 //               R(q) (exp(s) * noise)), scales (split children log(exp(s) / 1.6)), revised opacities (arXiv:2404.06109).
-#include "wm_common.h"
+#include "scene_common.h"
 #include "wm_kernels.h"
-
-#include <hipcub/hipcub.hpp>
 
 namespace {
 
@@ -131,22 +129,17 @@ __global__ __launch_bounds__(256) void densify_gather_kernel(const float* __rest
   out[i] = v;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct PlanWs { Flags* flags; Flags* excl; int* counts; void* cub; size_t cub_bytes, total; };
 
 PlanWs carve(char* base, size_t N) {
   PlanWs w;
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += al256(b); return p; };
-  w.flags = (Flags*)take((N + 1) * sizeof(Flags));
-  w.excl = (Flags*)take((N + 1) * sizeof(Flags));
-  w.counts = (int*)take(4 * sizeof(int));
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveScan(nullptr, b, (Flags*)nullptr, (Flags*)nullptr, FlagsSum(), Flags{0u, 0u, 0u, 0u, 0u}, (int)(N + 1));
-  w.cub_bytes = b;
-  w.cub = take(b);
-  w.total = o;
+  Carver c(base);
+  w.flags = c.take<Flags>(N + 1);
+  w.excl = c.take<Flags>(N + 1);
+  w.counts = c.take<int>(4);
+  w.cub_bytes = exclusive_scan_bytes(FlagsSum(), Flags{0u, 0u, 0u, 0u, 0u}, (int)(N + 1));
+  w.cub = c.take<char>(w.cub_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -157,7 +150,7 @@ hipError_t wm_launch_densify_accumulate(const float* v_means2d, const int* radii
   if (N <= 0 || C <= 0 || width <= 0 || height <= 0) return hipErrorInvalidValue;
   // default.py:225-226: grads[..., 0] *= width / 2.0 * n_cameras, the factor rounded to fp32 once
   const float sx = (float)((double)width / 2.0 * (double)C), sy = (float)((double)height / 2.0 * (double)C);
-  hipLaunchKernelGGL(densify_accumulate_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, v_means2d, radii, N, C, sx, sy,
+  hipLaunchKernelGGL(densify_accumulate_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, s, v_means2d, radii, N, C, sx, sy,
                      (float)(width > height ? width : height), grad2d, count, radii_state);
   return hipGetLastError();
 }
@@ -169,14 +162,11 @@ hipError_t wm_launch_densify_plan(const WmDensifyPlanArgs& a, hipStream_t s) {
   if (a.use_scale2d && !a.radii_state) return hipErrorInvalidValue;
   PlanWs w = carve((char*)a.workspace, (size_t)a.N);
   if (w.total > a.workspace_bytes) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(densify_classify_kernel, dim3((unsigned)((a.N + 1 + 255) / 256)), dim3(256), 0, s, a, w.flags);
-  size_t tb = w.cub_bytes;
-  hipError_t e = hipcub::DeviceScan::ExclusiveScan(w.cub, tb, w.flags, w.excl, FlagsSum(), Flags{0u, 0u, 0u, 0u, 0u}, a.N + 1, s);
+  hipLaunchKernelGGL(densify_classify_kernel, dim3(blocks_for(a.N + 1, 256)), dim3(256), 0, s, a, w.flags);
+  hipError_t e = exclusive_scan(w.cub, w.cub_bytes, w.flags, w.excl, FlagsSum(), Flags{0u, 0u, 0u, 0u, 0u}, a.N + 1, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(densify_scatter_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, w.flags, w.excl, a.N, a.src, a.kind, a.rank, w.counts);
-  e = hipMemcpyAsync(a.counts, w.counts, 4 * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);
+  hipLaunchKernelGGL(densify_scatter_kernel, dim3(blocks_for(a.N, 256)), dim3(256), 0, s, w.flags, w.excl, a.N, a.src, a.kind, a.rank, w.counts);
+  e = read_back(a.counts, w.counts, 4 * sizeof(int), s);
   if (e != hipSuccess) return e;
   return hipGetLastError();
 }

@@ -23,20 +23,12 @@
 //   p_cam = R^T (p_world - t) with [R | t] = camtoworld[:3] (the RIGID inverse, taken here per camera: the call assumes R orthonormal,
 //   where the reference inverts a general 4 x 4), q = K p_cam, (x, y) = q.xy / q.z, depth = p_cam.z,
 //   valid = visible && 0 <= x < W && 0 <= y < H && depth > 0, decided on the fp64 values as the reference decides it in numpy.
-#include <hipcub/hipcub.hpp>
-
-#include "wm_common.h"
+#include "scene_common.h"
 #include "wm_kernels.h"
 
 namespace {
 
 constexpr int DL_THREADS = 256;
-
-__device__ __forceinline__ double dl_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 struct DlGeom {
   int C, H, W, M;
@@ -85,8 +77,8 @@ __global__ __launch_bounds__(DL_THREADS) WM_NO_PACKED_FP32 void depthloss_fwd_ke
   }
   if (WANT_BWD && e < rows) coef[e] = cf;
   // every thread reaches the barrier: no return above it
-  term = dl_wave_sum(term);
-  cnt = dl_wave_sum(cnt);
+  term = wave_sum(term);
+  cnt = wave_sum(cnt);
   const int tid = threadIdx.x;
   if ((tid & 63) == 0) { sRed[0][tid >> 6] = term; sRed[1][tid >> 6] = cnt; }
   __syncthreads();
@@ -230,8 +222,6 @@ __global__ __launch_bounds__(DL_THREADS) WM_NO_PACKED_FP32 void depth_project_ke
   valid[e] = (vis && x >= 0.0 && x < (double)W && y >= 0.0 && y < (double)H && pc[2] > 0.0) ? 1 : 0;
 }
 
-size_t dl_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 bool dl_sizes_ok(int C, int H, int W, int M) {
   if (C < 1 || H < 2 || W < 2 || M < 0) return false;
   if ((long long)C * (H + 1) * (W + 1) >= (1LL << 31) - 1) return false;      // cell keys (and one past them) in 31 bits
@@ -251,28 +241,26 @@ struct DlWs {
 // with_backward = false stops behind the forward's part: no size query, nothing beyond fwd_total is valid
 DlWs dl_carve(char* base, int C, int H, int W, int M, bool with_backward) {
   DlWs w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += dl_align(b); return p; };
+  Carver c(base);
   const size_t rows = (size_t)C * M, cells = (size_t)C * (H + 1) * (W + 1);
-  w.nblk = (int)((rows + DL_THREADS - 1) / DL_THREADS);
-  w.partials = (double*)take((size_t)(w.nblk ? w.nblk : 1) * 2 * sizeof(double));
-  w.hdr = (DlHeader*)take(sizeof(DlHeader));
-  w.fwd_total = o;
-  if (!with_backward) { w.total = o; return w; }
-  w.coef = (float*)take(rows * 4);
-  w.keys[0] = (unsigned int*)take(rows * 4); w.keys[1] = (unsigned int*)take(rows * 4);
-  w.vals[0] = (unsigned int*)take(rows * 4); w.vals[1] = (unsigned int*)take(rows * 4);
-  w.start = (int*)take(cells * 4);
+  w.nblk = (int)blocks_for((long long)rows, DL_THREADS);
+  w.partials = c.take<double>((size_t)(w.nblk ? w.nblk : 1) * 2);
+  w.hdr = c.take<DlHeader>(1);
+  w.fwd_total = c.total();
+  if (!with_backward) { w.total = c.total(); return w; }
+  w.coef = c.take<float>(rows);
+  w.keys[0] = c.take<unsigned int>(rows); w.keys[1] = c.take<unsigned int>(rows);
+  w.vals[0] = c.take<unsigned int>(rows); w.vals[1] = c.take<unsigned int>(rows);
+  w.start = c.take<int>(cells);
   w.bits = 1;
   while (w.bits < 32 && (cells >> w.bits) != 0) ++w.bits;      // the key of a row without a cell, `cells`, is the largest
   // The sort's scratch by a rule of our own, not by the library's size query: the query needs a device for all but small inputs (it fails on
   // a machine without one), and a size call must give the same number everywhere.  With both buffers of (key, row) handed over, the
   // library keeps digit histograms and one look-back word per digit and block of a few thousand pairs: well under a byte per pair.  8 bytes
   // per row + 1 MiB is several times that; the backward asks the library what it needs and refuses (hipErrorOutOfMemory) if it were more.
-  const size_t tb = 8 * rows + ((size_t)1 << 20);
-  w.cub_bytes = tb;
-  w.cub = take(tb);
-  w.total = o;
+  w.cub_bytes = 8 * rows + ((size_t)1 << 20);
+  w.cub = c.take<char>(w.cub_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -320,11 +308,7 @@ hipError_t wm_launch_depthloss_bwd(const WmDepthLossArgs& a, const float* gout, 
     hipLaunchKernelGGL(depthloss_keys_kernel, dim3((unsigned)w.nblk), dim3(DL_THREADS), 0, s, k.g, a.points, (const float*)w.coef, none, w.keys[0],
                        w.vals[0]);
     hipcub::DoubleBuffer<unsigned int> dk(w.keys[0], w.keys[1]), dv(w.vals[0], w.vals[1]);
-    size_t tb = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (int)rows, 0, w.bits, s);      // the size alone: nothing is launched
-    if (e != hipSuccess) return e;
-    if (tb > w.cub_bytes) return hipErrorOutOfMemory;
-    e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, dk, dv, (int)rows, 0, w.bits, s);      // stable: a cell's rows stay in row order
+    hipError_t e = sort_pairs(w.cub, w.cub_bytes, dk, dv, (int)rows, 0, w.bits, s);      // stable: a cell's rows stay in row order
     if (e != hipSuccess) return e;
     k.keys = dk.Current(); k.vals = dv.Current();
     e = hipMemsetAsync(w.start, 0xff, cells * 4, s);
@@ -332,7 +316,7 @@ hipError_t wm_launch_depthloss_bwd(const WmDepthLossArgs& a, const float* gout, 
     hipLaunchKernelGGL(depthloss_starts_kernel, dim3((unsigned)w.nblk), dim3(DL_THREADS), 0, s, k.keys, rows, none, w.start);
   }
   const long long pixels = (long long)a.C * a.H * a.W;
-  hipLaunchKernelGGL(depthloss_bwd_kernel, dim3((unsigned)((pixels + DL_THREADS - 1) / DL_THREADS)), dim3(DL_THREADS), 0, s, k);
+  hipLaunchKernelGGL(depthloss_bwd_kernel, dim3(blocks_for(pixels, DL_THREADS)), dim3(DL_THREADS), 0, s, k);
   return hipGetLastError();
 }
 
@@ -341,7 +325,7 @@ hipError_t wm_launch_depth_project(const float* points_world, const float* camto
   if (C < 1 || P < 0 || W < 1 || H < 1 || (long long)C * P >= (1LL << 30)) return hipErrorInvalidValue;
   if (P == 0) return hipSuccess;
   const long long rows = (long long)C * P;
-  hipLaunchKernelGGL(depth_project_kernel, dim3((unsigned)((rows + DL_THREADS - 1) / DL_THREADS)), dim3(DL_THREADS), 0, s, points_world, camtoworlds,
+  hipLaunchKernelGGL(depth_project_kernel, dim3(blocks_for(rows, DL_THREADS)), dim3(DL_THREADS), 0, s, points_world, camtoworlds,
                      Ks, visible, C, P, W, H, points, depths, valid);
   return hipGetLastError();
 }

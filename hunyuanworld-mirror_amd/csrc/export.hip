@@ -4,8 +4,8 @@
 //
 // stages
 //   keep      one lane per input row: the row is kept when every one of its numbers is finite (14 + 3K of them) and, for
-//             ply_compressed, 1 / (1 + exp(-opacity)) > opacity_threshold.  The flags go through an exclusive scan (hipcub, as
-//             densify.hip) and a scatter: kept rows stay in input order.  The number kept is the one value the host waits for.
+//             ply_compressed, 1 / (1 + exp(-opacity)) > opacity_threshold.  The flags go through an exclusive scan (hipcub) and
+//             a scatter: kept rows stay in input order.  The number kept is the one value the host waits for.
 //   morton    (splat, ply_compressed) min / max of the kept means per axis by a two-level block reduction (no atomics),
 //             q = int(floor((c - min) / len * 1024)) with len == 0 -> 1, the low 10 bits per axis (1024 wraps to 0, as the reference's
 //             mask does), bits interleaved z<<2 | y<<1 | x, then a STABLE 30-bit radix sort of (code, row): equal codes stay in row order.
@@ -36,10 +36,8 @@
 //     chunk bound is whatever fminf / fmaxf give and is not pinned; nothing else of the file depends on it ((v - min) is 0 either way)
 //   * a non-finite opacity (the reference's `.any(dim=0)` on the 1-D opacities is one scalar for all rows, so a single NaN empties the
 //     file): here that row alone is dropped
-#include <hipcub/hipcub.hpp>
-
-#include "../../include/wm_hip.h"
-#include "wm_common.h"
+#include "scene_common.h"
+#include "wm_api.h"
 
 #pragma clang fp contract(off)
 
@@ -59,20 +57,19 @@ struct ExIn {
 struct ExCol { const float* base; int stride; int xf; };      // base null: zeros; xf 0 none, 1 log
 struct ExCols { ExCol c[EX_MAX_COLS]; int n; };
 
-__device__ __forceinline__ bool ex_finite(float v) { return fabsf(v) <= 3.4028234663852886e38f; }      // false for NaN
 __device__ __forceinline__ float ex_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- keep flags
 __global__ __launch_bounds__(EX_THREADS) WM_NO_PACKED_FP32 void export_flags_kernel(ExIn a, int use_threshold, float threshold, int* __restrict__ flags) {
   const long long i = (long long)blockIdx.x * EX_THREADS + threadIdx.x;
   if (i >= a.N) return;
-  bool ok = ex_finite(a.opac[i]);
+  bool ok = finite_f32(a.opac[i]);
 #pragma unroll
-  for (int j = 0; j < 3; ++j) ok = ok && ex_finite(a.means[3 * i + j]) && ex_finite(a.scales[3 * i + j]) && ex_finite(a.sh0[3 * i + j]);
+  for (int j = 0; j < 3; ++j) ok = ok && finite_f32(a.means[3 * i + j]) && finite_f32(a.scales[3 * i + j]) && finite_f32(a.sh0[3 * i + j]);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) ok = ok && ex_finite(a.quats[4 * i + j]);
+  for (int j = 0; j < 4; ++j) ok = ok && finite_f32(a.quats[4 * i + j]);
   const int nr = 3 * a.K;
-  for (int j = 0; j < nr; ++j) ok = ok && ex_finite(a.shN[(long long)nr * i + j]);
+  for (int j = 0; j < nr; ++j) ok = ok && finite_f32(a.shN[(long long)nr * i + j]);
   if (ok && use_threshold) ok = ex_sigmoid(a.opac[i]) > threshold;
   flags[i] = ok ? 1 : 0;
 }
@@ -92,17 +89,6 @@ __global__ __launch_bounds__(EX_THREADS) void export_scatter_kernel(const int* _
 }
 
 // ---- min / max of the kept means
-__device__ __forceinline__ float ex_wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float ex_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 // block min / max of NQ quantities; every lane of the block calls it; the results are in sOut[0 .. NQ) (min) and sOut[NQ .. 2 NQ) (max)
 template <int NQ>
 __device__ __forceinline__ void ex_block_minmax(const float (&lo)[NQ], const float (&hi)[NQ], float* sRed /* 2 NQ waves */, float* sOut /* 2 NQ */) {
@@ -110,7 +96,7 @@ __device__ __forceinline__ void ex_block_minmax(const float (&lo)[NQ], const flo
   const int tid = threadIdx.x;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-    const float a = ex_wave_min(lo[q]), b = ex_wave_max(hi[q]);
+    const float a = wave_min(lo[q]), b = wave_max(hi[q]);
     if ((tid & 63) == 0) { sRed[q * WAVES + (tid >> 6)] = a; sRed[(NQ + q) * WAVES + (tid >> 6)] = b; }
   }
   __syncthreads();
@@ -151,15 +137,6 @@ __global__ __launch_bounds__(EX_THREADS) void export_minmax_final_kernel(const f
   if (threadIdx.x < 6) mm[threadIdx.x] = sOut[threadIdx.x];
 }
 
-__device__ __forceinline__ unsigned int ex_part1by2(unsigned int x) {
-  x &= 0x000003ffu;
-  x = (x ^ (x << 16)) & 0xff0000ffu;
-  x = (x ^ (x << 8)) & 0x0300f00fu;
-  x = (x ^ (x << 4)) & 0x030c30c3u;
-  x = (x ^ (x << 2)) & 0x09249249u;
-  return x;
-}
-
 __global__ __launch_bounds__(EX_THREADS) WM_NO_PACKED_FP32 void export_morton_kernel(const float* __restrict__ means, const int* __restrict__ kept, int n,
                                                                                      const float* __restrict__ mm, unsigned int* __restrict__ keys,
                                                                                      unsigned int* __restrict__ vals) {
@@ -175,7 +152,7 @@ __global__ __launch_bounds__(EX_THREADS) WM_NO_PACKED_FP32 void export_morton_ke
     const float s = floorf((means[3 * i + j] - lo) / len * 1024.f);      // 0 .. 1024 for finite kept means
     q[j] = (unsigned int)(int)s;
   }
-  keys[r] = (ex_part1by2(q[2]) << 2) + (ex_part1by2(q[1]) << 1) + ex_part1by2(q[0]);
+  keys[r] = (part1by2_10(q[2]) << 2) + (part1by2_10(q[1]) << 1) + part1by2_10(q[0]);
   vals[r] = (unsigned int)i;
 }
 
@@ -319,9 +296,6 @@ __global__ __launch_bounds__(EX_THREADS) WM_NO_PACKED_FP32 void export_sh_bytes_
 }
 
 // ------------------------------------------------------------------ host side
-size_t ex_align(size_t n) { return (n + 255) & ~(size_t)255; }
-unsigned ex_blocks(long long n) { return (unsigned)((n + EX_THREADS - 1) / EX_THREADS); }
-
 struct ExWs {
   int* flags; int* offs; int* kept; int* count;
   float* partials; float* mm;
@@ -334,51 +308,40 @@ struct ExWs {
 // the same number on every machine, with or without a device; the launchers ask the library what it needs and refuse if it were more.
 ExWs ex_carve(char* base, long long N, bool with_sort) {
   ExWs w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += ex_align(b); return p; };
+  Carver c(base);
   const size_t rows = (size_t)(N > 0 ? N : 1);
-  w.flags = (int*)take(rows * 4); w.offs = (int*)take(rows * 4); w.kept = (int*)take(rows * 4); w.count = (int*)take(4);
+  w.flags = c.take<int>(rows); w.offs = c.take<int>(rows); w.kept = c.take<int>(rows); w.count = c.take<int>(1);
   if (with_sort) {
-    w.partials = (float*)take((size_t)ex_blocks((long long)rows) * 6 * 4); w.mm = (float*)take(6 * 4);
-    w.keys[0] = (unsigned int*)take(rows * 4); w.keys[1] = (unsigned int*)take(rows * 4);
-    w.vals[0] = (unsigned int*)take(rows * 4); w.vals[1] = (unsigned int*)take(rows * 4);
+    w.partials = c.take<float>((size_t)blocks_for((long long)rows, EX_THREADS) * 6); w.mm = c.take<float>(6);
+    w.keys[0] = c.take<unsigned int>(rows); w.keys[1] = c.take<unsigned int>(rows);
+    w.vals[0] = c.take<unsigned int>(rows); w.vals[1] = c.take<unsigned int>(rows);
   }
   w.cub_bytes = 8 * rows + ((size_t)1 << 20);
-  w.cub = take(w.cub_bytes);
-  w.total = o;
+  w.cub = c.take<char>(w.cub_bytes);
+  w.total = c.total();
   return w;
 }
 
 // flags (already written) -> kept list and *n_kept on the host; the one stream synchronisation of an export
 hipError_t ex_compact(const ExWs& w, int N, int* n_kept, hipStream_t s) {
-  size_t tb = 0;
-  hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, w.flags, w.offs, N, s);      // the size alone
+  hipError_t e = exclusive_sum(w.cub, w.cub_bytes, w.flags, w.offs, N, s);
   if (e != hipSuccess) return e;
-  if (tb > w.cub_bytes) return hipErrorOutOfMemory;
-  e = hipcub::DeviceScan::ExclusiveSum(w.cub, tb, w.flags, w.offs, N, s);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(export_scatter_kernel, dim3(ex_blocks(N)), dim3(EX_THREADS), 0, s, (const int*)w.flags, (const int*)w.offs, N, w.kept, w.count);
+  hipLaunchKernelGGL(export_scatter_kernel, dim3(blocks_for(N, EX_THREADS)), dim3(EX_THREADS), 0, s, (const int*)w.flags, (const int*)w.offs, N, w.kept, w.count);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(n_kept, w.count, sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  return hipStreamSynchronize(s);
+  return read_back(n_kept, w.count, sizeof(int), s);
 }
 
 // kept rows -> Morton order (original row indices) in *order
 hipError_t ex_morton_order(const ExWs& w, const float* means, int n, const unsigned int** order, hipStream_t s) {
-  const unsigned nb = ex_blocks(n);
+  const unsigned nb = blocks_for(n, EX_THREADS);
   hipLaunchKernelGGL(export_minmax_kernel, dim3(nb), dim3(EX_THREADS), 0, s, means, (const int*)w.kept, n, w.partials);
   hipLaunchKernelGGL(export_minmax_final_kernel, dim3(1), dim3(EX_THREADS), 0, s, (const float*)w.partials, (int)nb, w.mm);
   hipLaunchKernelGGL(export_morton_kernel, dim3(nb), dim3(EX_THREADS), 0, s, means, (const int*)w.kept, n, (const float*)w.mm, w.keys[0], w.vals[0]);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipcub::DoubleBuffer<unsigned int> dk(w.keys[0], w.keys[1]), dv(w.vals[0], w.vals[1]);
-  size_t tb = 0;
-  e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, n, 0, 30, s);
-  if (e != hipSuccess) return e;
-  if (tb > w.cub_bytes) return hipErrorOutOfMemory;
-  e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, dk, dv, n, 0, 30, s);      // stable: equal codes stay in row order
+  e = sort_pairs(w.cub, w.cub_bytes, dk, dv, n, 0, 30, s);      // stable: equal codes stay in row order
   if (e != hipSuccess) return e;
   *order = dv.Current();
   return hipSuccess;
@@ -387,7 +350,7 @@ hipError_t ex_morton_order(const ExWs& w, const float* means, int n, const unsig
 hipError_t ex_pack_rows(const ExCols& cols, const int* kept, int n, float* out, hipStream_t s) {
   const long long total = (long long)n * cols.n;
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(export_pack_rows_kernel, dim3(ex_blocks(total)), dim3(EX_THREADS), 0, s, cols, kept, total, out);
+  hipLaunchKernelGGL(export_pack_rows_kernel, dim3(blocks_for(total, EX_THREADS)), dim3(EX_THREADS), 0, s, cols, kept, total, out);
   return hipGetLastError();
 }
 
@@ -402,8 +365,6 @@ size_t ex_payload(long long n, int K, int format) {
 bool ex_sizes_ok(long long N, int K, int format) {
   return N >= 0 && N < (1LL << 31) && K >= 0 && K <= 15 && format >= WM_EXPORT_PLY && format <= WM_EXPORT_PLY_COMPRESSED;
 }
-
-wm_status ex_status(hipError_t e) { return e == hipSuccess ? WM_OK : e == hipErrorInvalidValue ? WM_ERR_INVALID : WM_ERR_HIP; }
 
 }  // namespace
 
@@ -431,10 +392,10 @@ extern "C" wm_status wm_export_splats(const float* means, const float* scales, c
   if (N == 0) return WM_OK;
   hipStream_t s = (hipStream_t)stream;
   const ExIn a{means, scales, quats, opacities, sh0, shN, (int)N, K};
-  hipLaunchKernelGGL(export_flags_kernel, dim3(ex_blocks(N)), dim3(EX_THREADS), 0, s, a, format == WM_EXPORT_PLY_COMPRESSED ? 1 : 0,
+  hipLaunchKernelGGL(export_flags_kernel, dim3(blocks_for(N, EX_THREADS)), dim3(EX_THREADS), 0, s, a, format == WM_EXPORT_PLY_COMPRESSED ? 1 : 0,
                      opacity_threshold, w.flags);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ex_status(e);
+  if (e != hipSuccess) return wm_status_of(e);
   int n = 0;
   e = ex_compact(w, (int)N, &n, s);
   if (e != hipSuccess) return WM_ERR_HIP;
@@ -453,14 +414,14 @@ extern "C" wm_status wm_export_splats(const float* means, const float* scales, c
     for (int j = 0; j < 3; ++j) add(scales + j, 3);
     for (int j = 0; j < 4; ++j) add(quats + j, 4);
     cols.n = c;
-    return ex_status(ex_pack_rows(cols, w.kept, n, (float*)out, s));
+    return wm_status_of(ex_pack_rows(cols, w.kept, n, (float*)out, s));
   }
   const unsigned int* order = nullptr;
   e = ex_morton_order(w, means, n, &order, s);
   if (e != hipSuccess) return WM_ERR_HIP;
   if (format == WM_EXPORT_SPLAT) {
-    hipLaunchKernelGGL(export_splat_kernel, dim3(ex_blocks(n)), dim3(EX_THREADS), 0, s, a, order, n, (uint4*)out);
-    return ex_status(hipGetLastError());
+    hipLaunchKernelGGL(export_splat_kernel, dim3(blocks_for(n, EX_THREADS)), dim3(EX_THREADS), 0, s, a, order, n, (uint4*)out);
+    return wm_status_of(hipGetLastError());
   }
   const int nchunks = (n + EX_CHUNK - 1) / EX_CHUNK;
   char* body = (char*)out;
@@ -470,9 +431,9 @@ extern "C" wm_status wm_export_splats(const float* means, const float* scales, c
   hipLaunchKernelGGL(export_compressed_kernel, dim3((unsigned)nchunks), dim3(EX_CHUNK), 0, s, a, order, n, chunks, verts);
   if (K > 0) {
     const long long total = (long long)n * 3 * K;
-    hipLaunchKernelGGL(export_sh_bytes_kernel, dim3(ex_blocks(total)), dim3(EX_THREADS), 0, s, shN, K, order, total, shb);
+    hipLaunchKernelGGL(export_sh_bytes_kernel, dim3(blocks_for(total, EX_THREADS)), dim3(EX_THREADS), 0, s, shN, K, order, total, shb);
   }
-  return ex_status(hipGetLastError());
+  return wm_status_of(hipGetLastError());
 }
 
 extern "C" size_t wm_pack_rows_workspace_bytes(int64_t N) {
@@ -497,12 +458,12 @@ extern "C" wm_status wm_pack_rows(const float* const* col_ptrs, const int* col_s
   *n_kept = 0;
   if (N == 0) return WM_OK;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(export_mask_flags_kernel, dim3(ex_blocks(N)), dim3(EX_THREADS), 0, s, keep, (int)N, w.flags);
+  hipLaunchKernelGGL(export_mask_flags_kernel, dim3(blocks_for(N, EX_THREADS)), dim3(EX_THREADS), 0, s, keep, (int)N, w.flags);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return ex_status(e);
+  if (e != hipSuccess) return wm_status_of(e);
   int n = 0;
   e = ex_compact(w, (int)N, &n, s);
   if (e != hipSuccess || n < 0 || n > N) return WM_ERR_HIP;
   *n_kept = n;
-  return ex_status(ex_pack_rows(cols, w.kept, n, out, s));
+  return wm_status_of(ex_pack_rows(cols, w.kept, n, out, s));
 }

@@ -27,8 +27,8 @@
 //   interpolates between.  All selections share four 8-bit radix passes; the only atomics are the integer histogram adds.
 #include <vector>
 
+#include "scene_common.h"
 #include "wm_api.h"
-#include "wm_common.h"
 
 namespace {
 
@@ -36,7 +36,6 @@ constexpr int GL_THREADS = 256;
 constexpr int GL_ROUNDS = 2;
 constexpr int GL_CHUNK = GL_THREADS * GL_ROUNDS;      // items of one view per block
 
-size_t gl_align(size_t n) { return (n + 255) & ~(size_t)255; }
 unsigned gl_bpv(long long hw) { return (unsigned)((hw + GL_CHUNK - 1) / GL_CHUNK); }
 
 struct GlWs {
@@ -47,53 +46,15 @@ struct GlWs {
 // S views of hw items; remap only for meshes
 GlWs gl_carve(char* base, int S, long long hw, bool mesh) {
   GlWs w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += gl_align(b); return p; };
+  Carver c(base);
   const size_t nblk = (size_t)S * gl_bpv(hw);
-  w.blk_v = (unsigned int*)take((nblk + 1) * 4);
-  w.blk_q = (unsigned int*)take((nblk + 1) * 4);
-  w.blk_bounds = (float*)take(nblk * 6 * 4);
-  w.res = (long long*)take((2 * (size_t)S + 2) * 8);
-  w.remap = mesh ? (int*)take((size_t)S * (size_t)hw * 4) : nullptr;
-  w.total = o;
+  w.blk_v = c.take<unsigned int>(nblk + 1);
+  w.blk_q = c.take<unsigned int>(nblk + 1);
+  w.blk_bounds = c.take<float>(nblk * 6);
+  w.res = c.take<long long>(2 * (size_t)S + 2);
+  w.remap = mesh ? c.take<int>((size_t)S * (size_t)hw) : nullptr;
+  w.total = c.total();
   return w;
-}
-
-// ordered rank of the lanes of a 256-thread block whose flag is set, and the number set; every lane calls it
-__device__ __forceinline__ unsigned int gl_block_rank(bool f, unsigned int* sW /* 4 */, unsigned int& total) {
-  const unsigned long long b = __ballot(f);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned int r = (unsigned int)__popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();      // sW may still be read from the call before
-  if (lane == 0) sW[w] = (unsigned int)__popcll(b);
-  __syncthreads();
-  unsigned int base = 0;
-  total = 0;
-#pragma unroll
-  for (int i = 0; i < GL_THREADS / 64; ++i) {
-    if (i < w) base += sW[i];
-    total += sW[i];
-  }
-  return base + r;
-}
-
-// in-place exclusive scan of v[0 .. n) by ONE 256-thread block; v[n] receives the total
-__device__ void gl_scan_in_place(unsigned int* v, unsigned int n, unsigned int* part /* 256, shared */) {
-  const unsigned int per = (n + GL_THREADS - 1) / GL_THREADS, lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  unsigned int s = 0;
-  for (unsigned int i = lo; i < hi; ++i) s += v[i];
-  __syncthreads();
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int run = 0;
-    for (int i = 0; i < GL_THREADS; ++i) { const unsigned int t = part[i]; part[i] = run; run += t; }
-    v[n] = run;
-  }
-  __syncthreads();
-  unsigned int run = part[threadIdx.x];
-  for (unsigned int i = lo; i < hi; ++i) { const unsigned int t = v[i]; v[i] = run; run += t; }
-  __syncthreads();
 }
 
 // the mask of pixel (y, x) of one view; outside the image: false; no mask: every pixel
@@ -131,10 +92,10 @@ __global__ __launch_bounds__(GL_THREADS) void gl_count_kernel(const unsigned cha
     const long long p = (long long)c * GL_CHUNK + r * GL_THREADS + threadIdx.x;
     bool used, quad;
     gl_flags<MESH>(m, H, W, hw, p, used, quad);
-    gl_block_rank(used, sW, tot);
+    block_rank<GL_THREADS>(used, sW, tot);
     nv += tot;
     if (MESH) {
-      gl_block_rank(quad, sW, tot);
+      block_rank<GL_THREADS>(quad, sW, tot);
       nq += tot;
     }
   }
@@ -145,8 +106,8 @@ __global__ __launch_bounds__(GL_THREADS) void gl_count_kernel(const unsigned cha
 __global__ __launch_bounds__(GL_THREADS) void gl_scan_kernel(unsigned int* blk_v, unsigned int* blk_q, unsigned int nblk, unsigned int bpv, int S,
                                                              long long* __restrict__ res) {
   __shared__ unsigned int part[GL_THREADS];
-  gl_scan_in_place(blk_v, nblk, part);
-  gl_scan_in_place(blk_q, nblk, part);
+  block_scan_in_place<GL_THREADS>(blk_v, nblk, part);
+  block_scan_in_place<GL_THREADS>(blk_q, nblk, part);
   for (int v = threadIdx.x; v < S; v += GL_THREADS) {
     res[v] = (long long)blk_v[(size_t)(v + 1) * bpv] - (long long)blk_v[(size_t)v * bpv];
     res[S + v] = (long long)blk_q[(size_t)(v + 1) * bpv] - (long long)blk_q[(size_t)v * bpv];
@@ -205,7 +166,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_vertex_kernel(const float* __re
     const long long p = (long long)c * GL_CHUNK + r * GL_THREADS + threadIdx.x;
     bool used, quad;
     gl_flags<MESH>(m, H, W, hw, p, used, quad);
-    const unsigned int pos = run + gl_block_rank(used, sW, tot);
+    const unsigned int pos = run + block_rank<GL_THREADS>(used, sW, tot);
     run += tot;
     if (used && (long long)pos < limit) {
       const size_t idx = (size_t)v * hw + (size_t)p;
@@ -242,7 +203,7 @@ __global__ __launch_bounds__(GL_THREADS) void gl_faces_kernel(const unsigned cha
       const int y = (int)(p / W), x = (int)(p - (long long)y * W);
       quad = gl_quad(m, H, W, y, x);
     }
-    const unsigned int pos = run + gl_block_rank(quad, sW, tot);
+    const unsigned int pos = run + block_rank<GL_THREADS>(quad, sW, tot);
     run += tot;
     if (quad && (long long)pos < total_q) {      // a valid quad has x + 1 < W and y + 1 < H: p + W + 1 < hw
       const int a = rm[p], b = rm[p + W], cc = rm[p + W + 1], d = rm[p + 1];
@@ -280,22 +241,13 @@ struct PnState {
   unsigned int hist[PN_MAXSEL][256];
 };
 
-// the order-preserving image of a float: smaller float <=> smaller key
-__device__ __forceinline__ unsigned int pn_key(float v) {
-  const unsigned int u = __builtin_bit_cast(unsigned int, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float pn_unkey(unsigned int k) {
-  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
 __global__ __launch_bounds__(GL_THREADS) void pn_count_kernel(const unsigned char* __restrict__ mask, long long N, unsigned int* __restrict__ blk_cnt) {
   __shared__ unsigned int sW[GL_THREADS / 64];
   unsigned int cnt = 0, tot;
   const long long per = (N + gridDim.x - 1) / gridDim.x, lo = (long long)blockIdx.x * per, hi = lo + per < N ? lo + per : N;
   for (long long i0 = lo; i0 < hi; i0 += GL_THREADS) {      // uniform trip count within the block
     const long long i = i0 + threadIdx.x;
-    gl_block_rank(i < hi && (mask ? mask[i] != 0 : true), sW, tot);
+    block_rank<GL_THREADS>(i < hi && (mask ? mask[i] != 0 : true), sW, tot);
     cnt += tot;
   }
   if (threadIdx.x == 0) blk_cnt[blockIdx.x] = cnt;
@@ -344,7 +296,7 @@ __global__ __launch_bounds__(GL_THREADS) void pn_hist_kernel(const float* __rest
   for (long long i = (long long)blockIdx.x * GL_THREADS + threadIdx.x; i < N; i += (long long)gridDim.x * GL_THREADS) {
     if (mask && !mask[i]) continue;
     for (int col = 0; col < 3; ++col) {
-      const unsigned int key = pn_key(points[3 * i + col]);
+      const unsigned int key = ordered_key(points[3 * i + col]);
       for (int s = col * per_col; s < (col + 1) * per_col; ++s)
         if ((key & himask) == sPrefix[s]) atomicAdd(&lh[s][(key >> shift) & 255u], 1u);
     }
@@ -370,15 +322,15 @@ __global__ __launch_bounds__(GL_THREADS) void pn_pick_kernel(PnState* st, int nq
     const unsigned int prefix = st->prefix[s] | (bin << shift);
     st->prefix[s] = prefix;
     st->remaining[s] = rem;
-    if (shift == 0) out[s] = pn_unkey(prefix);
+    if (shift == 0) out[s] = ordered_value(prefix);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nsel * 256; i += GL_THREADS) (&st->hist[0][0])[i] = 0;
 }
 
 unsigned pn_blocks(long long N) {
-  const long long b = (N + GL_THREADS - 1) / GL_THREADS;
-  return (unsigned)(b < 1 ? 1 : (b > PN_MAXBLK ? PN_MAXBLK : b));
+  const unsigned b = blocks_for(N, GL_THREADS);
+  return b < 1 ? 1 : (b > PN_MAXBLK ? PN_MAXBLK : b);
 }
 
 bool pn_sizes_ok(long long N, int nq) { return N >= 0 && N < (1LL << 31) / 3 && nq >= 1 && nq <= PN_MAXQ; }
@@ -402,9 +354,7 @@ hipError_t wm_launch_image_mesh_count(const unsigned char* mask, int S, int H, i
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   std::vector<long long> res(2 * (size_t)S + 2);
-  e = hipMemcpyAsync(res.data(), w.res, res.size() * 8, hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);      // the one synchronisation: the caller sizes its outputs by the counts
+  e = read_back(res.data(), w.res, res.size() * 8, s);      // the one synchronisation: the caller sizes its outputs by the counts
   if (e != hipSuccess) return e;
   for (int v = 0; v < S; ++v) { n_vertices[v] = res[v]; n_quads[v] = res[(size_t)S + v]; }
   n_vertices[S] = res[2 * (size_t)S];
@@ -447,9 +397,7 @@ hipError_t wm_launch_glb_points(const float* points, const float* colors, const 
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   long long total = 0;
-  e = hipMemcpyAsync(&total, w.res + 2, 8, hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);
+  e = read_back(&total, w.res + 2, 8, s);
   if (e != hipSuccess) return e;
   if (total < 0 || total > N) return hipErrorUnknown;
   *n_kept = total;
@@ -458,7 +406,7 @@ hipError_t wm_launch_glb_points(const float* points, const float* colors, const 
 
 size_t wm_percentile_neighbours_ws_bytes(long long N, int nq) {
   if (!pn_sizes_ok(N, nq)) return 0;
-  return gl_align(sizeof(PnState)) + gl_align((size_t)PN_MAXBLK * 4);
+  return align256(sizeof(PnState)) + align256((size_t)PN_MAXBLK * 4);
 }
 
 hipError_t wm_launch_percentile_neighbours(const float* points, const unsigned char* mask, long long N, const double* q, int nq, void* workspace,
@@ -470,7 +418,7 @@ hipError_t wm_launch_percentile_neighbours(const float* points, const unsigned c
     qs.q[j] = q[j];
   }
   PnState* st = (PnState*)workspace;
-  unsigned int* blk_cnt = (unsigned int*)((char*)workspace + gl_align(sizeof(PnState)));
+  unsigned int* blk_cnt = (unsigned int*)((char*)workspace + align256(sizeof(PnState)));
   const unsigned nblk = pn_blocks(N);
   hipLaunchKernelGGL(pn_count_kernel, dim3(nblk), dim3(GL_THREADS), 0, s, mask, N, blk_cnt);
   hipLaunchKernelGGL(pn_setup_kernel, dim3(1), dim3(GL_THREADS), 0, s, (const unsigned int*)blk_cnt, nblk, qs, nq, st, count_out);

@@ -5,7 +5,7 @@
 //   init / bbox   the bounding box (integer atomic min / max of the order-preserving image of the floats) and the non-finite flag
 //   keys          t = x - min per axis, q = floor(t * scale) clamped to 21 bits, ONE scale for the three axes (2^21 / the largest extent:
 //                 cubic cells, so a flat or thin cloud keeps cubic neighbourhoods), 63-bit Morton key; value = the row
-//   sort          hipcub::DeviceRadixSort::SortPairs (stable), as raster.hip and splat_prune.hip
+//   sort          hipcub::DeviceRadixSort::SortPairs (stable)
 //   gather        the points in sorted order, (x, y, z, row) as one 16-byte record
 //   query         one query per lane, queries in sorted order (the lanes of a wave walk the same cells).  A level-L cell is 2^L finest
 //                 cells wide: all keys with the same top 63 - 3L bits, a contiguous run of the sorted keys found by two binary searches.
@@ -39,10 +39,8 @@
 // than 2^-21 of its bounding box falls into one finest cell and every query of it scans that cell: towards N per query.  A far outlier
 // starts at a coarse level; what it scans is what lies within its K-th distance of its cells' boxes, which for an outlier whose
 // neighbours are farther away than the dense part is, is the dense part: many such outliers cost N each.  Both stay exact.
-#include <hipcub/hipcub.hpp>
-
+#include "scene_common.h"
 #include "wm_api.h"
-#include "wm_common.h"
 
 namespace {
 
@@ -56,19 +54,13 @@ constexpr int KN_NONE = 0x7fffffff;                 // the row of an empty list 
 // bb: [0..3) min, [3..6) max, as order-preserving unsigned images
 struct KnFrame { float mn[3]; float scale, cell, slack; int degenerate; };
 
-__device__ __forceinline__ unsigned int kn_ord(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float kn_unord(unsigned int k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 __device__ __forceinline__ KnFrame kn_frame(const unsigned int* __restrict__ bb) {
   KnFrame f;
   float ext = 0.f;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    f.mn[a] = kn_unord(bb[a]);
-    ext = fmaxf(ext, __fsub_rn(kn_unord(bb[3 + a]), f.mn[a]));
+    f.mn[a] = ordered_value(bb[a]);
+    ext = fmaxf(ext, __fsub_rn(ordered_value(bb[3 + a]), f.mn[a]));
   }
   f.degenerate = !(ext >= 1e-30f && ext <= 1e38f);
   f.scale = f.degenerate ? 0.f : __fdiv_rn(2097152.f, ext);
@@ -107,8 +99,8 @@ __global__ __launch_bounds__(KN_THREADS) void kn_bbox_kernel(const float* __rest
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const float v = pts[3 * i + a];
-      bad |= !(fabsf(v) <= 3.4028234663852886e38f);      // NaN or infinite
-      const unsigned int k = kn_ord(v);
+      bad |= !finite_f32(v);      // NaN or infinite
+      const unsigned int k = ordered_key(v);
       lo[a] = k < lo[a] ? k : lo[a];
       hi[a] = k > hi[a] ? k : hi[a];
     }
@@ -354,25 +346,18 @@ __global__ __launch_bounds__(KN_THREADS) void kn_query_kernel(const float4* __re
   }
 }
 
-size_t kn_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct KnWs { unsigned int* bb; u64* keys[2]; unsigned int* rows[2]; float4* sp; void* cub; size_t cub_bytes, total; };
 
 KnWs kn_carve(char* base, size_t N) {
   KnWs w{};
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += kn_align(b); return p; };
-  w.bb = (unsigned int*)take(8 * 4);
-  w.keys[0] = (u64*)take(N * 8); w.keys[1] = (u64*)take(N * 8);
-  w.rows[0] = (unsigned int*)take(N * 4); w.rows[1] = (unsigned int*)take(N * 4);
-  w.sp = (float4*)take(N * 16);
-  size_t tb = 0;
-  hipcub::DoubleBuffer<u64> dk((u64*)nullptr, (u64*)nullptr);
-  hipcub::DoubleBuffer<unsigned int> dv((unsigned int*)nullptr, (unsigned int*)nullptr);
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, dk, dv, (int)N, 0, 63);
-  w.cub_bytes = tb;
-  w.cub = take(tb ? tb : 4);
-  w.total = o;
+  Carver c(base);
+  w.bb = c.take<unsigned int>(8);
+  w.keys[0] = c.take<u64>(N); w.keys[1] = c.take<u64>(N);
+  w.rows[0] = c.take<unsigned int>(N); w.rows[1] = c.take<unsigned int>(N);
+  w.sp = c.take<float4>(N);
+  w.cub_bytes = sort_pairs_bytes<u64, unsigned int>((int)N, 0, 63);
+  w.cub = c.take<char>(w.cub_bytes ? w.cub_bytes : 4);
+  w.total = c.total();
   return w;
 }
 
@@ -388,7 +373,7 @@ size_t wm_knn_ws_bytes(long long N, int K) {
 hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspace, float* dist, int* idx, int* nonfinite_flag, hipStream_t s) {
   if (!kn_sizes_ok(N, K)) return hipErrorInvalidValue;
   const KnWs w = kn_carve((char*)workspace, (size_t)N);
-  const unsigned nb = (unsigned)((N + KN_THREADS - 1) / KN_THREADS);
+  const unsigned nb = blocks_for(N, KN_THREADS);
   hipLaunchKernelGGL(kn_init_kernel, dim3(1), dim3(64), 0, s, w.bb, nonfinite_flag);
   hipLaunchKernelGGL(kn_bbox_kernel, dim3(nb < 2048u ? nb : 2048u), dim3(KN_THREADS), 0, s, points, N, w.bb, nonfinite_flag);
   hipLaunchKernelGGL(kn_keys_kernel, dim3(nb), dim3(KN_THREADS), 0, s, points, N, (const unsigned int*)w.bb, (const int*)nonfinite_flag, w.keys[0],
@@ -397,8 +382,7 @@ hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspac
   if (e != hipSuccess) return e;
   hipcub::DoubleBuffer<u64> dk(w.keys[0], w.keys[1]);
   hipcub::DoubleBuffer<unsigned int> dv(w.rows[0], w.rows[1]);
-  size_t tb = w.cub_bytes;
-  e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, dk, dv, (int)N, 0, 63, s);      // stable: equal keys stay in row order
+  e = sort_pairs(w.cub, w.cub_bytes, dk, dv, (int)N, 0, 63, s);      // stable: equal keys stay in row order
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kn_gather_kernel, dim3(nb), dim3(KN_THREADS), 0, s, points, N, (const unsigned int*)dv.Current(), (const int*)nonfinite_flag, w.sp);
   const float4* sp = w.sp;

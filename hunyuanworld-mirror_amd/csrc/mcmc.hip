@@ -6,17 +6,16 @@
 //                 load of the quaternions 1 KiB, its opacities 256 bytes.  The gate 1 / (1 + exp(-100 (sigmoid(-o) - 0.995))) loses
 //                 seven digits to the factor 100 when it is formed in fp32, so its two exponentials are fp64; everything else is fp32.
 //   partition     at a refinement (mcmc.py:154-155, ops.py:258-259): dead = sigmoid(o) <= min_opacity, or a caller's byte mask; one
-//                 exclusive sum (rocPRIM through hipCUB, the scan of densify.hip) gives every destination in both ascending lists.
+//                 exclusive sum (rocPRIM through hipCUB) gives every destination in both ascending lists.
 //   relocation    eq. 9 of the paper (RelocationCUDA.cu:26-43) for the drawn sources: an integer histogram of the draw, then per
 //                 draw the new opacity and scale in fp64, rounded once.  The double sum over (i, k) collapses by the hockey-stick
 //                 identity sum_{i=k+1..n} C(i-1, k) = C(n, k+1) to one sum of n terms; the binomials come by recurrence.
 //   scatter       param_fn of relocate and sample_add (ops.py:280-286, 322-328): sampled rows take their new values, dest rows a copy.
 //   zero_rows     optimizer_fn of relocate (ops.py:288-290).
-#include "wm_common.h"
-#include "wm_kernels.h"
-
 #include <cfloat>
-#include <hipcub/hipcub.hpp>
+
+#include "scene_common.h"
+#include "wm_kernels.h"
 
 namespace {
 
@@ -123,22 +122,17 @@ __global__ __launch_bounds__(256) void mcmc_zero_rows_kernel(float* __restrict__
   if ((unsigned int)g < (unsigned int)rows) t[(size_t)g * R + (i - j * (size_t)R)] = 0.f;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct PartWs { unsigned int* flags; unsigned int* excl; int* counts; void* cub; size_t cub_bytes, total; };
 
 PartWs carve(char* base, size_t N) {
   PartWs w;
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += al256(b); return p; };
-  w.flags = (unsigned int*)take((N + 1) * sizeof(unsigned int));
-  w.excl = (unsigned int*)take((N + 1) * sizeof(unsigned int));
-  w.counts = (int*)take(2 * sizeof(int));
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (unsigned int*)nullptr, (unsigned int*)nullptr, (int)(N + 1));
-  w.cub_bytes = b;
-  w.cub = take(b);
-  w.total = o;
+  Carver c(base);
+  w.flags = c.take<unsigned int>(N + 1);
+  w.excl = c.take<unsigned int>(N + 1);
+  w.counts = c.take<int>(2);
+  w.cub_bytes = exclusive_sum_bytes<unsigned int>((int)(N + 1));
+  w.cub = c.take<char>(w.cub_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -162,13 +156,10 @@ hipError_t wm_launch_mcmc_partition(const float* opacities, const unsigned char*
   PartWs w = carve((char*)workspace, (size_t)N);
   if (w.total > workspace_bytes) return hipErrorInvalidValue;
   hipLaunchKernelGGL(mcmc_dead_kernel, dim3((unsigned)(((size_t)N + 1 + 255) / 256)), dim3(256), 0, s, opacities, mask, N, min_opacity, w.flags);
-  size_t tb = w.cub_bytes;
-  hipError_t e = hipcub::DeviceScan::ExclusiveSum(w.cub, tb, w.flags, w.excl, N + 1, s);
+  hipError_t e = exclusive_sum(w.cub, w.cub_bytes, w.flags, w.excl, N + 1, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(mcmc_partition_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, w.flags, w.excl, N, dead_idx, alive_idx, w.counts);
-  e = hipMemcpyAsync(counts_host, w.counts, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);
+  e = read_back(counts_host, w.counts, 2 * sizeof(int), s);
   if (e != hipSuccess) return e;
   return hipGetLastError();
 }

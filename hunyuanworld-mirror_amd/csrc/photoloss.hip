@@ -17,7 +17,7 @@
 // Reproducibility: no atomics.  Each block writes its two partial sums to the workspace, one small kernel adds them in index
 // order.  Nothing in a plane's arithmetic or in the order of the partials depends on the strides: NCHW and channels-last give
 // the same bits.
-#include "wm_common.h"
+#include "scene_common.h"
 #include "wm_kernels.h"
 
 namespace {
@@ -61,12 +61,6 @@ __device__ __forceinline__ void pl_stage(float (*dst)[PL_IN][PL_PITCH], const fl
   _Pragma("unroll") for (int o = 0; o < PL_SEG; ++o) {              \
     if ((j) - o >= 0 && (j) - o < 11) acc[o] = fma(pl_g((j) - o), (v), acc[o]); \
   }
-
-__device__ __forceinline__ double pl_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 struct PlFwdArgs {
   const float* a; const float* b;
@@ -151,8 +145,8 @@ __global__ __launch_bounds__(PL_THREADS) WM_NO_PACKED_FP32 void photoloss_fwd_ke
       __syncthreads();   // sH is rewritten by the next channel, sA / sB by the next chunk
     }
   }
-  acc_s = pl_wave_sum(acc_s);
-  acc_l = pl_wave_sum(acc_l);
+  acc_s = wave_sum(acc_s);
+  acc_l = wave_sum(acc_l);
   if ((tid & 63) == 0) { sRed[0][tid >> 6] = acc_s; sRed[1][tid >> 6] = acc_l; }
   __syncthreads();
   if (tid == 0) {
@@ -269,8 +263,6 @@ __global__ __launch_bounds__(PL_THREADS) WM_NO_PACKED_FP32 void photoloss_bwd_ke
   }
 }
 
-size_t pl_align(size_t n) { return (n + 255) & ~(size_t)255; }
-
 bool pl_geom(const WmPhotoLossArgs& a, PlGeom& g, long long& nblk) {
   if (a.B <= 0 || a.C <= 0 || a.H <= 0 || a.W <= 0) return false;
   if (a.padding_valid && (a.H < 2 * PL_R + 1 || a.W < 2 * PL_R + 1)) return false;   // the mean of an empty map
@@ -289,7 +281,7 @@ double pl_count(const PlGeom& g) {
 
 size_t wm_photoloss_workspace_bytes(int B, int C, int H, int W) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-  return pl_align(wm_photoloss_forward_only_bytes(B, H, W)) + 3 * (size_t)B * C * H * W * sizeof(float);
+  return align256(wm_photoloss_forward_only_bytes(B, H, W)) + 3 * (size_t)B * C * H * W * sizeof(float);
 }
 // the per-tile partials alone: what a forward without a backward to follow touches
 size_t wm_photoloss_forward_only_bytes(int B, int H, int W) {
@@ -307,7 +299,7 @@ hipError_t wm_launch_photoloss_fwd(const WmPhotoLossArgs& a, int want_backward, 
   k.a = a.img1; k.b = a.img2; k.g = g;
   for (int i = 0; i < 4; ++i) { k.sa[i] = a.strides1[i]; k.sb[i] = a.strides2[i]; }
   k.partials = (double*)a.workspace;
-  k.maps = (float*)((char*)a.workspace + pl_align((size_t)nblk * 2 * sizeof(double)));
+  k.maps = (float*)((char*)a.workspace + align256((size_t)nblk * 2 * sizeof(double)));
   if (want_backward) hipLaunchKernelGGL(photoloss_fwd_kernel<true>, dim3((unsigned)nblk), dim3(PL_THREADS), 0, s, k);
   else hipLaunchKernelGGL(photoloss_fwd_kernel<false>, dim3((unsigned)nblk), dim3(PL_THREADS), 0, s, k);
   hipLaunchKernelGGL(photoloss_reduce_kernel, dim3(1), dim3(PL_THREADS), 0, s, (const double*)k.partials, (int)nblk, 1.0 / pl_count(g),
@@ -322,7 +314,7 @@ hipError_t wm_launch_photoloss_bwd(const WmPhotoLossArgs& a, const float* g_ssim
   PlBwdArgs k;
   k.a = a.img1; k.b = a.img2; k.g = g;
   for (int i = 0; i < 4; ++i) { k.sa[i] = a.strides1[i]; k.sb[i] = a.strides2[i]; }
-  k.maps = (const float*)((const char*)a.workspace + pl_align((size_t)nblk * 2 * sizeof(double)));
+  k.maps = (const float*)((const char*)a.workspace + align256((size_t)nblk * 2 * sizeof(double)));
   k.g_ssim = g_ssim; k.g_l1 = g_l1;
   k.inv_count = 1.0 / pl_count(g); k.inv_total = 1.0 / ((double)g.B * g.C * g.H * g.W);
   k.grad = grad_img1;

@@ -29,7 +29,7 @@
 // Stage 1 evaluates one acosf per pixel: acos is non-increasing, so the window maximum of arccos(dot) is
 // arccos(min dot) over the unmasked entries; an entry outside [-1, 1] (NaN from arccos) makes the result NaN, and any
 // masked entry contributes 0 (<= every arccos value).
-#include "wm_common.h"
+#include "scene_common.h"
 #include "wm_kernels.h"
 
 #pragma clang fp contract(off)
@@ -56,11 +56,7 @@ struct QState {
 // order-preserving uint32 image of an fp32 value; -0 folds onto +0 (numpy orders them as equal), every NaN onto the top
 __device__ __forceinline__ unsigned int q_key(float c) {
   if (c != c) return 0xFFFFFFFFu;
-  const unsigned int u = __builtin_bit_cast(unsigned int, c == 0.f ? 0.f : c);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float q_value(unsigned int k) {
-  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+  return ordered_key(c == 0.f ? 0.f : c);
 }
 
 constexpr int Q_EPT = 16;
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(256) void q_pick_kernel(QState* st, int shift, floa
   q.hist[1][threadIdx.x] = 0;
   if (shift == 0 && threadIdx.x == 0) {
     // _lerp: diff = b - a; r = a + diff * g, or b - diff * (1 - g) where g >= 0.5, all fp32 (numpy ufuncs: no FMA)
-    const float a = q_value(q.prefix[0]), b = q_value(q.prefix[1]);
+    const float a = ordered_value(q.prefix[0]), b = ordered_value(q.prefix[1]);
     const float d = f_sub(b, a);
     float r = gamma >= 0.5f ? f_sub(b, f_mul(d, f_sub(1.f, gamma))) : f_add(a, f_mul(d, gamma));
     if (q.nan_count) r = __builtin_nanf("");  // NaN sorts last and numpy's result for the slice is NaN

@@ -18,11 +18,8 @@
 // are SGPR operands of the per-pixel arithmetic: no LDS staging, no workgroup barrier, no shared early-out.  A step is
 // branch-free per lane (the reference's skip / stop / blend decisions are three lane masks); the two branches are wave-uniform:
 // skip the blend when no pixel of the quadrant is hit, leave the list when all 64 are saturated.
-#include "wm_common.h"
 #include "wm_kernels.h"
 #include "raster_common.h"
-
-#include <hipcub/hipcub.hpp>
 
 using namespace wm_raster;
 
@@ -284,24 +281,20 @@ __global__ __launch_bounds__(256 / (PX * PY)) void raster_composite_kernel(const
 
 RasterWs wm_raster::carve(char* base, size_t N, size_t C, int tiles, size_t max_isects) {
   RasterWs w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += align256(bytes); return p; };
+  Carver c(base);
   const size_t CN = N * C;
-  w.g2d = (G2D*)take(CN * sizeof(G2D));
-  w.counts = (unsigned long long*)take((CN + 1) * 8);
-  w.offsets = (unsigned long long*)take((CN + 1) * 8);
-  w.rgb = (float4*)take(N * sizeof(float4));
-  w.keys[0] = (unsigned long long*)take(max_isects * 8); w.keys[1] = (unsigned long long*)take(max_isects * 8);
-  w.vals[0] = (unsigned int*)take(max_isects * 4); w.vals[1] = (unsigned int*)take(max_isects * 4);
-  w.tile_offs = (unsigned int*)take((C * (size_t)tiles + 1) * 4);
-  size_t scan_b = 0, sort_b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)(CN + 1));
-  hipcub::DoubleBuffer<unsigned long long> dk((unsigned long long*)nullptr, (unsigned long long*)nullptr);
-  hipcub::DoubleBuffer<unsigned int> dv((unsigned int*)nullptr, (unsigned int*)nullptr);
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, dk, dv, (int)(max_isects > 0 ? max_isects : 1), 0, 64);
+  w.g2d = c.take<G2D>(CN);
+  w.counts = c.take<unsigned long long>(CN + 1);
+  w.offsets = c.take<unsigned long long>(CN + 1);
+  w.rgb = c.take<float4>(N);
+  w.keys[0] = c.take<unsigned long long>(max_isects); w.keys[1] = c.take<unsigned long long>(max_isects);
+  w.vals[0] = c.take<unsigned int>(max_isects); w.vals[1] = c.take<unsigned int>(max_isects);
+  w.tile_offs = c.take<unsigned int>(C * (size_t)tiles + 1);
+  const size_t scan_b = exclusive_sum_bytes<unsigned long long>((int)(CN + 1));
+  const size_t sort_b = sort_pairs_bytes<unsigned long long, unsigned int>((int)(max_isects > 0 ? max_isects : 1), 0, 64);
   w.cub_bytes = scan_b > sort_b ? scan_b : sort_b;
-  w.cub = take(w.cub_bytes);
-  w.total = o;
+  w.cub = c.take<char>(w.cub_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -337,13 +330,10 @@ hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned lo
   if (a.sh_degree > 0) launch_sh_colors(a, w.g2d, s);
   hipError_t e = hipMemsetAsync(w.counts + CN, 0, 8, s);
   if (e != hipSuccess) return e;
-  size_t tb = w.cub_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(w.cub, tb, w.counts, w.offsets, (int)(CN + 1), s);
+  e = exclusive_sum(w.cub, w.cub_bytes, w.counts, w.offsets, (int)(CN + 1), s);
   if (e != hipSuccess) return e;
   unsigned long long n_isects = 0;
-  e = hipMemcpyAsync(&n_isects, w.offsets + CN, 8, hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);  // the list length sizes the sort (the reference's isect_tiles does .item() here too)
+  e = read_back(&n_isects, w.offsets + CN, 8, s);  // the list length sizes the sort (the reference's isect_tiles does .item() here too)
   if (e != hipSuccess) return e;
   if (n_isects_out) *n_isects_out = n_isects;
   if (n_isects > a.max_isects || n_isects >= (1ull << 31)) return hipSuccess;  // caller checks n_isects_out against max_isects
@@ -353,8 +343,7 @@ hipError_t wm_launch_rasterize(const WmRasterArgs& a, hipStream_t s, unsigned lo
     hipLaunchKernelGGL(raster_emit_kernel, dim3((unsigned)((CN + 255) / 256)), dim3(256), 0, s, w.g2d, w.offsets, CN, a.N, tw, tile_bits, w.keys[0], w.vals[0]);
     hipcub::DoubleBuffer<unsigned long long> dk(w.keys[0], w.keys[1]);
     hipcub::DoubleBuffer<unsigned int> dv(w.vals[0], w.vals[1]);
-    tb = w.cub_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, dk, dv, (int)n_isects, 0, 32 + tile_bits + cam_bits, s);
+    e = sort_pairs(w.cub, w.cub_bytes, dk, dv, (int)n_isects, 0, 32 + tile_bits + cam_bits, s);
     if (e != hipSuccess) return e;
     sorted_keys = dk.Current(); sorted_vals = dv.Current();
   }

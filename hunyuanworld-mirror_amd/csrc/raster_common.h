@@ -1,7 +1,7 @@
 // Shared between the rasteriser's forward (raster.hip) and backward (raster_bwd.hip): the per-(camera, Gaussian) record the
 // projection writes, and the layout of the caller's workspace.  The backward reads what the forward left there.
 #pragma once
-#include "wm_common.h"
+#include "scene_common.h"
 #include "wm_kernels.h"
 
 namespace wm_raster {
@@ -20,8 +20,6 @@ struct __attribute__((aligned(16))) G2D {  // per (camera, Gaussian): 48 B = thr
   int pad;
 };
 static_assert(sizeof(G2D) == 48, "G2D is read as three dwordx4");
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct RasterWs {
   G2D* g2d; unsigned long long* counts; unsigned long long* offsets; float4* rgb;

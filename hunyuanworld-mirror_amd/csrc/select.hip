@@ -9,7 +9,7 @@
 // the top), then one pass writes the mask.  Ties at the K-th value are broken by lowest index (the reference's
 // torch.topk leaves the choice unspecified): a per-block count of the tied elements, a single-block exclusive scan and
 // an in-block ordered rank.  Everything is integer / comparison arithmetic: the result is exact and deterministic.
-#include "wm_common.h"
+#include "scene_common.h"
 #include "wm_kernels.h"
 
 namespace {
@@ -22,13 +22,6 @@ struct SelState {
   unsigned int need_eq;      // number of elements equal to kth that belong to the top-K
   unsigned int total_eq;     // number of elements equal to kth
 };
-
-__device__ __forceinline__ unsigned int conf_key(float c) {
-  if (c != c) return 0xFFFFFFFFu;  // any NaN, either sign, any payload: the one top key, above +inf like torch.topk's NaN-largest
-  const float v = c <= 1e-5f ? -INFINITY : c;
-  const unsigned int u = __builtin_bit_cast(unsigned int, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone: larger float <=> larger key
-}
 
 constexpr int SEL_EPT = 16;                 // consecutive elements per thread
 constexpr int SEL_CHUNK = 256 * SEL_EPT;    // elements per block
@@ -96,21 +89,10 @@ __global__ __launch_bounds__(256) void sel_count_eq_kernel(const float* __restri
   if (threadIdx.x == 0) blk_eq[blockIdx.x] = cnt;
 }
 
-// single block: exclusive scan of the per-block tie counts (in place)
-__global__ __launch_bounds__(256) void sel_scan_kernel(unsigned int* __restrict__ blk_eq, unsigned int nblk) {
+// single block: exclusive scan of the per-block tie counts (in place); the total goes to blk_eq[nblk], which nothing reads
+__global__ __launch_bounds__(256) void sel_scan_kernel(unsigned int* blk_eq, unsigned int nblk) {
   __shared__ unsigned int part[256];
-  const unsigned int per = (nblk + 255) / 256, lo = threadIdx.x * per, hi = lo + per < nblk ? lo + per : nblk;
-  unsigned int s = 0;
-  for (unsigned int i = lo; i < hi; ++i) s += blk_eq[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int run = 0;
-    for (int i = 0; i < 256; ++i) { const unsigned int t = part[i]; part[i] = run; run += t; }
-  }
-  __syncthreads();
-  unsigned int run = part[threadIdx.x];
-  for (unsigned int i = lo; i < hi; ++i) { const unsigned int t = blk_eq[i]; blk_eq[i] = run; run += t; }
+  block_scan_in_place<256>(blk_eq, nblk, part);
 }
 
 // mask: key > kth -> 1; key == kth -> 1 for the first need_eq of them in index order
@@ -151,6 +133,9 @@ __global__ __launch_bounds__(256) void sel_mask_kernel(const float* __restrict__
 
 }  // namespace
 
+// blk_eq starts at align256(sizeof(SelState)) and holds nblk + 1 words (the scan's total): inside the size below, which is part of the C ABI
+static_assert(align256(sizeof(SelState)) + sizeof(unsigned int) <= sizeof(SelState) + 256, "the scan's total must fit the workspace");
+
 size_t wm_confidence_mask_workspace(size_t n) {
   const size_t nblk = (n + SEL_CHUNK - 1) / SEL_CHUNK;
   return sizeof(SelState) + 256 + nblk * sizeof(unsigned int);
@@ -161,7 +146,7 @@ hipError_t wm_launch_confidence_mask(const float* conf, size_t n, unsigned int K
   if (n == 0) return hipSuccess;
   if (K < 1 || K > n || n >= ((size_t)1 << 32)) return hipErrorInvalidValue;
   SelState* st = (SelState*)workspace;
-  unsigned int* blk_eq = (unsigned int*)((char*)workspace + ((sizeof(SelState) + 255) / 256) * 256);
+  unsigned int* blk_eq = (unsigned int*)((char*)workspace + align256(sizeof(SelState)));
   const unsigned int nblk = (unsigned int)((n + SEL_CHUNK - 1) / SEL_CHUNK);
   hipLaunchKernelGGL(sel_init_kernel, dim3(1), dim3(256), 0, s, st, K);
   for (int shift = 24; shift >= 0; shift -= 8) {

@@ -7,10 +7,8 @@
 //   merge    one thread per voxel walks its run IN ORIGINAL INDEX ORDER (the sort is stable): weighted sums of means, sh,
 //            scales, quats, sum of w and of w^2, then the reference's normalisations (:341-376).  The reference's
 //            scatter_add_ adds in index order on the CPU, so the sums here are bit-identical to its CPU result.
-#include "wm_common.h"
+#include "scene_common.h"
 #include "wm_kernels.h"
-
-#include <hipcub/hipcub.hpp>
 
 namespace {
 
@@ -89,26 +87,19 @@ __global__ __launch_bounds__(256) void prune_merge_kernel(const float* __restric
   for (int d = 0; d < 4; ++d) o_quats[4 * k + d] = q[d] / qn;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct PruneWs { i64* mm; u64* keys[2]; unsigned int* idx[2]; unsigned int* head; unsigned int* excl; unsigned int* start; void* cub; size_t cub_bytes, total; };
 
 PruneWs carve(char* base, size_t N) {
   PruneWs w;
-  size_t o = 0;
-  auto take = [&](size_t b) { char* p = base ? base + o : nullptr; o += al256(b); return p; };
-  w.mm = (i64*)take(6 * 8);
-  w.keys[0] = (u64*)take(N * 8); w.keys[1] = (u64*)take(N * 8);
-  w.idx[0] = (unsigned int*)take(N * 4); w.idx[1] = (unsigned int*)take(N * 4);
-  w.head = (unsigned int*)take((N + 1) * 4); w.excl = (unsigned int*)take((N + 1) * 4); w.start = (unsigned int*)take((N + 2) * 4);
-  size_t a = 0, b = 0;
-  hipcub::DoubleBuffer<u64> dk((u64*)nullptr, (u64*)nullptr);
-  hipcub::DoubleBuffer<unsigned int> dv((unsigned int*)nullptr, (unsigned int*)nullptr);
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, dk, dv, (int)(N ? N : 1), 0, 64);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (unsigned int*)nullptr, (unsigned int*)nullptr, (int)(N + 1));
+  Carver c(base);
+  w.mm = c.take<i64>(6);
+  w.keys[0] = c.take<u64>(N); w.keys[1] = c.take<u64>(N);
+  w.idx[0] = c.take<unsigned int>(N); w.idx[1] = c.take<unsigned int>(N);
+  w.head = c.take<unsigned int>(N + 1); w.excl = c.take<unsigned int>(N + 1); w.start = c.take<unsigned int>(N + 2);
+  const size_t a = sort_pairs_bytes<u64, unsigned int>((int)(N ? N : 1), 0, 64), b = exclusive_sum_bytes<unsigned int>((int)(N + 1));
   w.cub_bytes = a > b ? a : b;
-  w.cub = take(w.cub_bytes);
-  w.total = o;
+  w.cub = c.take<char>(w.cub_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -128,27 +119,23 @@ hipError_t wm_launch_prune_gs(const float* means, const float* quats, const floa
   const i64 init[6] = {LLONG_MAX, LLONG_MAX, LLONG_MAX, LLONG_MIN, LLONG_MIN, LLONG_MIN};
   hipError_t e = hipMemcpyAsync(w.mm, init, sizeof(init), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return e;
-  const unsigned nb = (unsigned)((N + 255) / 256);
+  const unsigned nb = blocks_for(N, 256);
   hipLaunchKernelGGL(prune_minmax_kernel, dim3(nb), dim3(256), 0, s, means, N, voxel, w.mm);
   hipLaunchKernelGGL(prune_keys_kernel, dim3(nb), dim3(256), 0, s, means, N, voxel, w.mm, w.keys[0], w.idx[0]);
   hipcub::DoubleBuffer<u64> dk(w.keys[0], w.keys[1]);
   hipcub::DoubleBuffer<unsigned int> dv(w.idx[0], w.idx[1]);
-  size_t tb = w.cub_bytes;
-  e = hipcub::DeviceRadixSort::SortPairs(w.cub, tb, dk, dv, N, 0, 64, s);
+  e = sort_pairs(w.cub, w.cub_bytes, dk, dv, N, 0, 64, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(prune_heads_kernel, dim3(nb), dim3(256), 0, s, dk.Current(), N, w.head);
   e = hipMemsetAsync(w.head + N, 0, 4, s);
   if (e != hipSuccess) return e;
-  tb = w.cub_bytes;
-  e = hipcub::DeviceScan::ExclusiveSum(w.cub, tb, w.head, w.excl, N + 1, s);
+  e = exclusive_sum(w.cub, w.cub_bytes, w.head, w.excl, N + 1, s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(prune_starts_kernel, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, w.head, w.excl, N, w.start);
+  hipLaunchKernelGGL(prune_starts_kernel, dim3(blocks_for(N + 1, 256)), dim3(256), 0, s, w.head, w.excl, N, w.start);
   hipLaunchKernelGGL(prune_merge_kernel, dim3(nb), dim3(256), 0, s, means, quats, scales, sh, weights, dv.Current(), w.start, w.excl + N, o_means, o_quats,
                      o_scales, o_opac, o_sh);
   unsigned int K = 0;
-  e = hipMemcpyAsync(&K, w.excl + N, 4, hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
-  e = hipStreamSynchronize(s);
+  e = read_back(&K, w.excl + N, 4, s);
   if (e != hipSuccess) return e;
   if (K_out) *K_out = (int)K;
   return hipGetLastError();

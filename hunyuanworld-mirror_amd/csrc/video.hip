@@ -23,7 +23,7 @@
 //    pointmask.hip's select keeps its own helpers: its lerp is numpy's (no FMA, gamma >= 0.5 on the other side) and it counts NaN, so a
 //    shared header would have to change its code; here NaN depths are out of contract.
 #include "wm_api.h"
-#include "wm_common.h"
+#include "scene_common.h"
 
 #pragma clang fp contract(off)
 
@@ -150,11 +150,7 @@ struct VState {
 
 // order-preserving uint32 image of an fp32 value; -0 folds onto +0 (a sort holds them equal and either gives log = -inf)
 __device__ __forceinline__ unsigned int v_key(float c) {
-  const unsigned int u = __builtin_bit_cast(unsigned int, c == 0.f ? 0.f : c);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float v_value(unsigned int k) {
-  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+  return ordered_key(c == 0.f ? 0.f : c);
 }
 
 constexpr int V_EPT = 16;
@@ -250,7 +246,7 @@ __global__ __launch_bounds__(256) void v_pick_kernel(VState* st, int shift, int 
   for (int t = 0; t < 4; ++t) q.hist[t][threadIdx.x] = 0;
   if (shift == 0 && threadIdx.x < 2) {
     const int set = threadIdx.x;
-    const float a = v_value(q.prefix[2 * set]), b = v_value(q.prefix[2 * set + 1]), w = q.weight[set];
+    const float a = ordered_value(q.prefix[2 * set]), b = ordered_value(q.prefix[2 * set + 1]), w = q.weight[set];
     const float diff = b - a;
     const float v = w < 0.5f ? fmaf(w, diff, a) : fmaf(-diff, 1.f - w, b);
     float r = (float)log((double)v);
