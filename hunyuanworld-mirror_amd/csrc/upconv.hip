@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void f32_to_16_2d_kernel(const float* __restri
   }
 }
 
-// Token-conv border fix (gemm.hip, WM_EPI_CONV with tc_k > 0): the composed GEMM adds the ConvTranspose's bias through ALL nine taps of the 3x3
+// Token-conv border fix (gemm_pp2.hip, WM_EPI_CONV with tc_k > 0): the composed GEMM adds the ConvTranspose's bias through ALL nine taps of the 3x3
 // conv; on the image border the taps that fall outside see zero padding, not bias: subtract bmiss[tap][f] = (W_rn[tap] b_ct)[f] for those.
 __global__ __launch_bounds__(256) void tconv_border_kernel(float* __restrict__ out, const float* __restrict__ bmiss, int N, int H, int W, int F) {
   const int per = 2 * W + 2 * (H - 2 > 0 ? H - 2 : 0), f4n = F / 4;

@@ -188,7 +188,7 @@ wm_status backbone_block(Ctx& c, const BlockW& w, float* X, int M, int seq_len, 
     st = layernorm(c, ln);
     if (st) return st;
   }
-  // the residual GEMMs carry the LayerNorm that follows them when the launch allows it (gemm.hip epilogue_resid_ln)
+  // the residual GEMMs carry the LayerNorm that follows them when the launch allows it (gemm_pp2.hip epilogue_resid_ln)
   auto fuse_args = [&](WmGemmArgs& ex, const Norm& n) {
     ex.ln_out = A16; ex.ln_ld = D; ex.ln_w = n.w; ex.ln_b = n.b; ex.ln_eps = eps;
     ex.ln_stats = ws.LN_STATS;

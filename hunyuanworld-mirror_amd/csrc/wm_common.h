@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 // Packed-fp32 VALU instructions (v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32) are kept out of every kernel except the GELU GEMM
-// instantiations of gemm.hip: with two or more HIP queues active such an instruction can lose a half result
+// instantiations of the gemm_*.hip kernels: with two or more HIP queues active such an instruction can lose a half result
 // (profiles/r02_multiqueue_hazard.md), and the forward runs the DPT heads, the camera head and the sharded K/V all-gather on their own
 // queues.  How: the build's -fno-slp-vectorize removes the compiler-formed ones; WM_NO_PACKED_FP32 on a function removes what is left
 // where vector-typed source still packs (a whole-translation-unit attribute was tried: it also doubled the v_mov_b32 count of the

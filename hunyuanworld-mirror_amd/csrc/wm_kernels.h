@@ -8,7 +8,7 @@
 // The shipped library reads NO environment variable: kernel variants are chosen by the launchers and, for tests and A/B tools,
 // through wm_set_tuning (the table at the end of this file).
 
-// ------------------------------------------------------------------ GEMM (gemm.hip)
+// ------------------------------------------------------------------ GEMM (gemm_launch.cpp; plan: gemm_launch.h, gemm_plan.cpp; kernels: gemm_nt.hip, gemm_nt16.hip, gemm_pp.hip, gemm_pp2.hip)
 enum {
   WM_EPI_F32 = 0,         // C f32 = acc + bias
   WM_EPI_T16 = 1,         // C 16-bit = acc + bias
@@ -472,6 +472,6 @@ hipError_t wm_launch_prune_gs(const float* means, const float* quats, const floa
 #define WM_TUNE_ENUM(name_, key_) WM_TUNE_##name_,
 enum { WM_TUNE_KEYS(WM_TUNE_ENUM) WM_TUNE_COUNT };
 #undef WM_TUNE_ENUM
-extern int wm_tuning[WM_TUNE_COUNT];   // one definition, beside wm_set_tuning in wm_weights.cpp; the launchers and wm_api_ops.cpp read it too
+extern int wm_tuning[WM_TUNE_COUNT];   // one definition, beside wm_set_tuning in wm_tuning.cpp; the launchers and wm_api_ops.cpp read it too
 inline int wm_tune(int key, int dflt) { return wm_tuning[key] < 0 ? dflt : wm_tuning[key]; }
 

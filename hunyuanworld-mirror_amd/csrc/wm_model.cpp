@@ -3,7 +3,7 @@
 // One wm_handle = one process/GPU: owns the repacked weights and a workspace arena, and turns
 // WorldMirror.forward (reference src/models/models/worldmirror.py:120-216) into a fixed sequence of
 // HIP kernel launches on the caller's stream.  No torch, no hidden per-call allocation once the
-// workspace for a shape exists.  The orchestrator's other concerns, each behind wm_model.h: wm_weights.cpp (weight store, lifecycle, tuning),
+// workspace for a shape exists.  The orchestrator's other concerns, each behind wm_model.h: wm_weights.cpp (weight store, lifecycle),
 // wm_compose.cpp (composed head weights), wm_plan.cpp (arena, binder, host tables, queues: wm_reserve), wm_comm.cpp (communicator),
 // wm_backbone.cpp (transformer block), wm_heads.cpp (camera and DPT heads).  The other entries of the C ABI are in wm_api_ops.cpp (wm_op_*) and
 // wm_api_scene.cpp (ingest, masks, rasteriser, densify, MCMC, losses, bilagrid, appearance).
@@ -127,7 +127,7 @@ wm_status forward_impl(wm_handle* h, const float* img, int n, int first_view, in
   // instructions (compiler-generated v_pk_mul_f32 / v_pk_fma_f32, op_sel forms) dropping one half's result in 16-lane groups when a
   // kernel of another kind shares the SIMD from another queue — reproduced without torch on the ROCm 7.2 runtime with the library's own
   // kernels (tools/micro/splat_hazard_repro.cpp, profiles/r02_multiqueue_hazard.md), never with one queue, never without packed fp32.
-  // No kernel outside the GELU instantiations of gemm.hip contains a packed-fp32 instruction any more (-fno-slp-vectorize,
+  // No kernel outside the GELU instantiations of the gemm_*.hip kernels contains a packed-fp32 instruction any more (-fno-slp-vectorize,
   // WM_NO_PACKED_FP32 in wm_common.h; held by tests/test_kernel_resources_cpu.py, which disassembles every object), and those
   // GELU GEMMs of the backbone have finished before this fork.  tools/stress_concurrent_heads.py: 4 900 concurrent forwards (C2, C3, C5 flag set) bit-identical
   // to the serial one.

@@ -1,4 +1,4 @@
-// The weight store of a handle: the parameter list, the 16-bit repack at load, the handle's lifecycle and the tuning table.
+// The weight store of a handle: the parameter list, the 16-bit repack at load, and the handle's lifecycle.
 #include "wm_model.h"
 
 namespace wm_host {
@@ -155,17 +155,6 @@ const Weight* W(const wm_handle* h, const std::string& n) {
 
 }  // namespace wm_host
 using namespace wm_host;
-
-#define WM_TUNE_UNSET(name_, key_) -1,
-#define WM_TUNE_NAME(name_, key_) key_,
-int wm_tuning[WM_TUNE_COUNT] = {WM_TUNE_KEYS(WM_TUNE_UNSET)};
-static const char* const wm_tuning_keys[WM_TUNE_COUNT] = {WM_TUNE_KEYS(WM_TUNE_NAME)};
-
-extern "C" int wm_set_tuning(const char* key, int value) {
-  for (int i = 0; i < WM_TUNE_COUNT; ++i)
-    if (key && strcmp(key, wm_tuning_keys[i]) == 0) { wm_tuning[i] = value; return 0; }
-  return -1;
-}
 
 extern "C" void wm_host_to_16(const float* in, uint16_t* out, size_t n, int dtype) {
   for (size_t i = 0; i < n; ++i) out[i] = h_to16(in[i], dtype);

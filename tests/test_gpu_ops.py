@@ -76,6 +76,58 @@ def test_gemm_epilogues(dev, M, N, K, dt):
     assert _rel(X, X0 + gamma * ref) < 2e-5
 
 
+_FAMILY_CASES = {}   # (M, N, K, dt) -> operands, fp32 torch reference and the default kernel's fp32 output: computed once, never written
+
+
+def _family_case(dev, M, N, K, dt):
+    key = (M, N, K, dt)
+    if key not in _FAMILY_CASES:
+        g = torch.Generator(device="cpu").manual_seed(M * 7 + N)
+        A = _t16(torch.randn(M, K, generator=g), dt).to(dev)
+        W = _t16(torch.randn(N, K, generator=g) / math.sqrt(K), dt).to(dev)
+        bias = torch.randn(N, generator=g).to(dev)
+        gamma = torch.randn(N, generator=g).to(dev)
+        X0 = torch.randn(M, N, generator=g).to(dev)
+        ref = A.float() @ W.float().t() + bias
+        dflt = torch.empty(M, N, device=dev)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        assert _lib().wm_op_gemm(dt, 0, _p(A), _p(W), _p(dflt), _p(bias), None, M, N, K, s) == 0
+        torch.cuda.synchronize()
+        _FAMILY_CASES[key] = (A, W, bias, gamma, X0, ref, dflt)
+    return _FAMILY_CASES[key]
+
+
+@pytest.mark.parametrize("cfg", [4, 5])
+@pytest.mark.parametrize("family,pp,mfma16", [("nt32", 0, 0), ("nt16", 0, 2), ("pp1", 3, -1)])
+def test_gemm_lockstep_and_pingpong_v1_families(dev, family, pp, mfma16, cfg):
+    """The kernel families the default launch does not reach, on the 256- and 192-row tiles: gemm_nt_kernel (gemm_pp = 0, gemm_mfma16 = 0),
+    gemm_nt16_kernel (gemm_pp = 0, gemm_mfma16 = 2) and ping-pong v1 gemm_pp_kernel (gemm_pp = 3), epilogues 0-3, against the fp32 torch
+    reference and tolerances of test_gemm_epilogues.  Whether the fp32 output equals the default launch's bit for bit is printed, not
+    asserted: no family promises the others' summation order."""
+    L = _lib()
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    cases = [(_family_case(dev, M, N, K, dt), M, N, K, dt) for M, N, K, dt in ((1000, 384, 640, BF16), (1000, 384, 640, F16), (2752, 1024, 1024, BF16))]
+    assert L.wm_set_tuning(b"gemm_cfg", cfg) == 0 and L.wm_set_tuning(b"gemm_pp", pp) == 0 and L.wm_set_tuning(b"gemm_mfma16", mfma16) == 0
+    try:
+        for (A, W, bias, gamma, X0, ref, dflt), M, N, K, dt in cases:
+            tol16 = 6e-3 if dt == BF16 else 8e-4
+            out = torch.empty(M, N, device=dev)
+            o16 = torch.empty(M, N, device=dev, dtype=torch.int16)
+            ge = torch.empty(M, N, device=dev, dtype=torch.int16)
+            X = X0.clone()
+            assert L.wm_op_gemm(dt, 0, _p(A), _p(W), _p(out), _p(bias), None, M, N, K, s) == 0
+            assert L.wm_op_gemm(dt, 1, _p(A), _p(W), _p(o16), _p(bias), None, M, N, K, s) == 0
+            assert L.wm_op_gemm(dt, 2, _p(A), _p(W), _p(ge), _p(bias), None, M, N, K, s) == 0
+            assert L.wm_op_gemm(dt, 3, _p(A), _p(W), _p(X), _p(bias), _p(gamma), M, N, K, s) == 0
+            torch.cuda.synchronize()
+            e = (_rel(out, ref), _rel(_from16(o16, dt), ref), _rel(_from16(ge, dt), torch.nn.functional.gelu(ref)), _rel(X, X0 + gamma * ref))
+            print(f"{family} cfg{cfg} {M}x{N}x{K} dt{dt}: f32 {e[0]:.2e} t16 {e[1]:.2e} gelu {e[2]:.2e} resid {e[3]:.2e}; "
+                  f"f32 bit-equal to the default kernel: {torch.equal(out, dflt)}")
+            assert e[0] < 2e-5 and e[1] < tol16 and e[2] < tol16 and e[3] < 2e-5
+    finally:
+        L.wm_set_tuning(b"gemm_cfg", -1); L.wm_set_tuning(b"gemm_pp", -1); L.wm_set_tuning(b"gemm_mfma16", -1)
+
+
 @pytest.mark.parametrize("M,N,K", [(11008, 1024, 1024), (11008, 3072, 256), (2752, 1024, 512), (1376 * 3 + 5, 512, 256), (200, 256, 128)])
 @pytest.mark.parametrize("cfg", [4, 5])
 def test_gemm_row_band_schedule_is_bit_identical(dev, M, N, K, cfg):
@@ -157,7 +209,7 @@ def test_gemm_pingpong_v3_matches_v2_bitwise(dev, K, cfg):
 @pytest.mark.parametrize("cfg", [4, 5])
 def test_gemm_residual_prefetch_is_bit_identical(dev, K, cfg):
     """Tuning resid_prefetch = 1: the residual epilogue's old C tile is touched line by line during the last two K-tiles (4-byte LDS-DMA
-    into a scratch corner, counted by the same vmcnt as the operand refills — gemm.hip prefetch_c).  It moves no value: X must come out
+    into a scratch corner, counted by the same vmcnt as the operand refills — gemm_pp2.hip prefetch_c).  It moves no value: X must come out
     bit-identical, from one K-tile (no prefetch window) up, on both tile heights, ragged row counts (rows past M clamp), scheduled bands."""
     L = _lib()
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -190,7 +242,7 @@ def test_gemm_residual_prefetch_is_bit_identical(dev, K, cfg):
 @pytest.mark.parametrize("dt", [BF16, F16])
 def test_gemm_residual_with_fused_layernorm(dev, M, K, dt):
     """X += gamma (A W^T + b) with the following LayerNorm fused into the epilogue (the four column tiles of a row band exchange per-row
-    (mean, M2) partials inside the launch; gemm.hip epilogue_resid_ln).  Checked: X bit-identical to the unfused epilogue; the LayerNorm
+    (mean, M2) partials inside the launch; gemm_pp2.hip epilogue_resid_ln).  Checked: X bit-identical to the unfused epilogue; the LayerNorm
     output against fp32 torch LayerNorm of THAT X at the 16-bit tolerance, and against the library's own LayerNorm kernel up to rounding
     flips (partial-combined statistics instead of a two-pass row: a few outputs differ by one ulp); several launches back to back on the
     same buffers (the counters must come back to zero), ragged row counts, both tile schedules."""
@@ -211,7 +263,7 @@ def test_gemm_residual_with_fused_layernorm(dev, M, K, dt):
     stats = torch.empty(M * 8, device=dev); sync = torch.zeros(3 * (M // 16 + 2), device=dev, dtype=torch.int32)
     fused = C.c_int(-1)
     for sched in (-1, 0):
-        assert L.wm_set_tuning(b"gemm_sched", sched) == 0 and L.wm_set_tuning(b"ln_fuse", 1) == 0   # (the fused epilogue is opt-in: gemm.hip wm_gemm_fuses_ln)
+        assert L.wm_set_tuning(b"gemm_sched", sched) == 0 and L.wm_set_tuning(b"ln_fuse", 1) == 0   # (the fused epilogue is opt-in: gemm_plan.cpp wm_gemm_plan)
         try:
             for rep in range(3):
                 X = X0.clone()
@@ -1013,7 +1065,7 @@ def test_up_conv_n32_unfused(dev, N, Hs, Ws, Hi, Wi, Cin):
 @pytest.mark.parametrize("N,gh,gw,k,Cin", [(2, 16, 16, 4, 256), (3, 10, 7, 2, 512), (1, 37, 37, 4, 256), (8, 37, 37, 2, 512), (1, 1, 5, 4, 64), (2, 3, 1, 2, 128)])
 def test_token_conv_composition(dev, dt, N, gh, gw, k, Cin):
     """wm_op_tconv: Conv2d(3x3, pad 1, no bias) o ConvTranspose2d(kernel = stride = k) as ONE block-sparse GEMM at the token resolution
-    (per output phase the combined matrices of the <= 2 x 2 neighbour tokens its taps land in; gemm.hip WM_EPI_CONV tc_k, wm_compose.cpp
+    (per output phase the combined matrices of the <= 2 x 2 neighbour tokens its taps land in; gemm_pp2.hip WM_EPI_CONV tc_k, wm_compose.cpp
     build_tconv) — against fp32 torch conv2d(conv_transpose2d(tokens)) on the same 16-bit tokens: interior, the image border (zero
     padding of the 3x3 sees neither neighbour tokens nor the ConvTranspose bias there), single-row / single-column token grids, both k."""
     g = torch.Generator().manual_seed(N * 7 + gh + k + Cin + dt)
