@@ -21,3 +21,5 @@ from .metrics import (Evaluator, PeakSignalNoiseRatio, StructuralSimilarityIndex
 from .glb import (GLBScene, convert_predictions_to_glb_scene, image_mesh, load_glb, save_camera_params)  # noqa: F401
 from .nvs import apply_confidence_filter, calculate_in_frustum_mask, calculate_unprojected_mask  # noqa: F401
 from .compression import PngCompression, kmeans_l1, sort_splats  # noqa: F401
+from .recon_metrics import (NearestIndex, accuracy_completeness, apply_transform, direction_statistics, evaluate_pointmaps, icp,  # noqa: F401
+                            nearest, umeyama)

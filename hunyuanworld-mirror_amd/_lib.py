@@ -77,6 +77,8 @@ EXPORTS = [
     "wm_colmap_select_workspace_bytes", "wm_colmap_select", "wm_colmap_gather", "wm_colmap_pack_workspace_bytes", "wm_colmap_pack",
     "wm_pack_point_ply_workspace_bytes", "wm_pack_point_ply",
     "wm_knn_workspace_bytes", "wm_knn",
+    "wm_nearest_build_workspace_bytes", "wm_nearest_build", "wm_nearest_query_workspace_bytes", "wm_nearest_query",
+    "wm_cloud_stats_workspace_bytes", "wm_cloud_stats", "wm_umeyama_workspace_bytes", "wm_umeyama",
     "wm_gs_effect_spread_workspace_bytes", "wm_gs_effect_spread", "wm_video_frames_workspace_bytes", "wm_video_frames", "wm_turbo_lut",
     "wm_image_mesh_workspace_bytes", "wm_image_mesh_count", "wm_image_mesh_pack", "wm_glb_pack_points_workspace_bytes", "wm_glb_pack_points",
     "wm_masked_percentile_neighbours_workspace_bytes", "wm_masked_percentile_neighbours",
@@ -252,6 +254,18 @@ def lib() -> C.CDLL:
     L.wm_knn_workspace_bytes.argtypes = [i64, i32]
     L.wm_knn_workspace_bytes.restype = C.c_size_t
     L.wm_knn.argtypes = [vp, i64, i32, vp, C.c_size_t, vp, vp, vp, vp]
+    L.wm_nearest_build_workspace_bytes.argtypes = [i64]
+    L.wm_nearest_build_workspace_bytes.restype = C.c_size_t
+    L.wm_nearest_build.argtypes = [vp, i64, vp, C.c_size_t, vp, vp]
+    L.wm_nearest_query_workspace_bytes.argtypes = [i64]
+    L.wm_nearest_query_workspace_bytes.restype = C.c_size_t
+    L.wm_nearest_query.argtypes = [vp, C.c_size_t, i64, vp, i64, vp, C.c_size_t, vp, vp, vp]
+    L.wm_cloud_stats_workspace_bytes.argtypes = [i64]
+    L.wm_cloud_stats_workspace_bytes.restype = C.c_size_t
+    L.wm_cloud_stats.argtypes = [vp, vp, i64, vp, vp, i64, C.POINTER(f32), i32, vp, C.c_size_t, vp, vp]
+    L.wm_umeyama_workspace_bytes.argtypes = [i64]
+    L.wm_umeyama_workspace_bytes.restype = C.c_size_t
+    L.wm_umeyama.argtypes = [vp, vp, vp, i64, i32, vp, C.c_size_t, vp, vp]
     L.wm_gs_effect_spread_workspace_bytes.argtypes = [i64]
     L.wm_gs_effect_spread_workspace_bytes.restype = C.c_size_t
     L.wm_gs_effect_spread.argtypes = [vp, vp, vp, vp, vp, i64, f64, i32, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]

@@ -370,9 +370,8 @@ size_t wm_knn_ws_bytes(long long N, int K) {
   return kn_carve(nullptr, (size_t)N).total;
 }
 
-hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspace, float* dist, int* idx, int* nonfinite_flag, hipStream_t s) {
-  if (!kn_sizes_ok(N, K)) return hipErrorInvalidValue;
-  const KnWs w = kn_carve((char*)workspace, (size_t)N);
+// bbox, keys, stable sort, gather: the index both searches walk.  keys_out: the buffer the sorted keys ended in.
+static hipError_t kn_build(const float* points, long long N, const KnWs& w, int* nonfinite_flag, const u64** keys_out, hipStream_t s) {
   const unsigned nb = blocks_for(N, KN_THREADS);
   hipLaunchKernelGGL(kn_init_kernel, dim3(1), dim3(64), 0, s, w.bb, nonfinite_flag);
   hipLaunchKernelGGL(kn_bbox_kernel, dim3(nb < 2048u ? nb : 2048u), dim3(KN_THREADS), 0, s, points, N, w.bb, nonfinite_flag);
@@ -385,8 +384,18 @@ hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspac
   e = sort_pairs(w.cub, w.cub_bytes, dk, dv, (int)N, 0, 63, s);      // stable: equal keys stay in row order
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kn_gather_kernel, dim3(nb), dim3(KN_THREADS), 0, s, points, N, (const unsigned int*)dv.Current(), (const int*)nonfinite_flag, w.sp);
+  *keys_out = dk.Current();
+  return hipGetLastError();
+}
+
+hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspace, float* dist, int* idx, int* nonfinite_flag, hipStream_t s) {
+  if (!kn_sizes_ok(N, K)) return hipErrorInvalidValue;
+  const KnWs w = kn_carve((char*)workspace, (size_t)N);
+  const unsigned nb = blocks_for(N, KN_THREADS);
+  const u64* keys = nullptr;
+  const hipError_t e = kn_build(points, N, w, nonfinite_flag, &keys, s);
+  if (e != hipSuccess) return e;
   const float4* sp = w.sp;
-  const u64* keys = dk.Current();
   const unsigned int* bb = w.bb;
   const int* flag = nonfinite_flag;
   if (K <= 4)
@@ -395,5 +404,189 @@ hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspac
     hipLaunchKernelGGL(kn_query_kernel<8>, dim3(nb), dim3(KN_THREADS), 0, s, sp, keys, (unsigned int)N, K, bb, flag, dist, idx);
   else
     hipLaunchKernelGGL(kn_query_kernel<16>, dim3(nb), dim3(KN_THREADS), 0, s, sp, keys, (unsigned int)N, K, bb, flag, dist, idx);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the nearest point of ANOTHER cloud (wm_nearest_build / wm_nearest_query)
+// The index is the one above (bbox, keys, stable sort, 16-byte records), built once over ref [N,3] and left in the caller's index memory;
+// a query call keys the queries [M,3] in the reference's frame (clamped to the grid), sorts them so that the lanes of a wave walk the same
+// cells, and runs one query per lane:
+//   seed    the 8 sorted records around the position of the query's key (a finite best distance before the walk starts)
+//   walk    nn_walk, the stackless octree walk of kn_walk from level 21 (the whole cloud) with a one-slot best in registers: a cell whose
+//           box is farther than the best is stepped over, a cell of at most 48 points is scanned, a larger one is taken apart.
+// There is no acceptance rule: the walk covers the whole cloud and only prunes, so it is exact wherever the query lies.
+//
+// Exactness.  dist = sqrt(min_j fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz))), dx = fl(q.x - r.x), every operation rounded on its own; idx is
+// the lowest row that attains the minimum square (the best is ordered by (square, row), and no search ends early on a zero: a lower row
+// with the same square may follow).  A cell is stepped over only when its conservative box distance exceeds the best square, strictly.
+// The box distance per axis is fl(fl(qlo cell) - t) - slack_q with t = fl(q - min): beside the 8u ext of the structure (see the top of
+// this file) t carries u |t| and the product u ext, which for a query far outside the box is NOT small against ext, so
+// slack_q = 16u ext + 8u max|t| (u = 2^-24); the relative error of the last subtraction, of the squares and of their sum (< 4u) and of a
+// pruned point's own fp32 square (< 3.5u) are covered by the factor 0.9999.  A bound below 1e-30 counts as 0 (nothing is pruned by it):
+// squares that small are denormal in fp32 and carry no relative accuracy.  An overflowing distance is +inf on both sides of a comparison
+// and prunes nothing.
+// A frame without usable cells (all of ref in one point, extent below 1e-30 or above 1e38) scans the cloud for every query.
+//
+// Determinism.  The minimum over (square, row) does not depend on the order the candidates are met in; both sorts are stable; the only
+// atomics are the integer min / max / or of the bounding box.
+//
+// Worst case.  A query costs the points of the cells its best-distance ball touches.  All of ref inside one finest cell (a dense part
+// below 2^-21 of the extent): N per query.  A query much farther from the cloud than the cloud is wide sees every cell at nearly the same
+// distance, and pruning by a 1e-4 margin fails once the cloud's extent is below 1e-4 of that distance: towards N per such query.  Both
+// stay exact.
+// One rounding per operation, for the rest of this file: the compiler's default for device code is to contract a product and a sum into a
+// fused multiply-add wherever it can, and the __f*_rn functions of this toolchain are plain operators that take part in that.  The
+// candidate squares below are therefore written with plain operators under this pragma (the pruning bounds, which are only conservative,
+// may be rounded either way).
+#pragma clang fp contract(off)
+namespace {
+
+__device__ __forceinline__ void nn_scan(const float4* __restrict__ sp, unsigned int lo, unsigned int hi, float xi, float yi, float zi, float& bd,
+                                        int& br) {
+  for (unsigned int j = lo; j < hi; ++j) {
+    const float4 s = sp[j];
+    const float dx = xi - s.x, dy = yi - s.y, dz = zi - s.z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;      // three products and two sums, each rounded (contract off)
+    const int row = __float_as_int(s.w);
+    if (d2 < bd || (d2 == bd && row < br)) { bd = d2; br = row; }
+  }
+}
+
+// kn_cell_dmin2 with the query's own slack
+__device__ __forceinline__ float nn_cell_dmin2(const unsigned int* qlo, int l, const float* t, float cell, float slack) {
+  float d2 = 0.f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float below = __fsub_rn(__fsub_rn(__fmul_rn((float)qlo[a], cell), t[a]), slack);
+    const float above = __fsub_rn(__fsub_rn(t[a], __fmul_rn((float)(qlo[a] + (1u << l)), cell)), slack);
+    const float da = fmaxf(below, above);
+    if (da > 0.f) d2 = __fadd_rn(d2, __fmul_rn(da, da));
+  }
+  return d2 > 1e-30f ? __fmul_rn(d2, 0.9999f) : 0.f;
+}
+
+// kn_walk over the whole cloud keys[0 .. N) from level 21, one-slot best (bd, br), no early end
+__device__ __forceinline__ void nn_walk(const float4* __restrict__ sp, const u64* __restrict__ keys, unsigned int N, const float* x, const float* t,
+                                        float cell, float slack, float& bd, int& br) {
+  unsigned int j = 0u, cap = N;
+  int l = KN_BITS;
+  while (j < N) {
+    const u64 key = keys[j];
+    const u64 k0 = (key >> (3 * l)) << (3 * l);
+    const unsigned int end = (l == KN_BITS) ? N : kn_lower_bound(keys, j + 1u, cap, k0 + (1ull << (3 * l)));
+    bool skip = false;
+    if (br != KN_NONE) {
+      const unsigned int qlo[3] = {kn_compact(k0), kn_compact(k0 >> 1), kn_compact(k0 >> 2)};
+      skip = nn_cell_dmin2(qlo, l, t, cell, slack) > bd;
+    }
+    if (!skip && end - j > KN_LEAF && l > 0) { --l; cap = end; continue; }
+    if (!skip) nn_scan(sp, j, end, x[0], x[1], x[2], bd, br);
+    j = end;
+    cap = N;
+    if (j < N) {
+      const int top = 63 - __clzll((long long)(keys[j] ^ keys[j - 1u]));      // the keys differ: j starts another cell of level l
+      l = top / 3 < KN_BITS ? top / 3 : KN_BITS;
+    }
+  }
+}
+
+// bb[6]: the non-finite flag of the build, bb[7]: N
+__global__ void nn_seal_kernel(unsigned int* __restrict__ bb, const int* __restrict__ flag, unsigned int N) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { bb[6] = (unsigned int)*flag; bb[7] = N; }
+}
+
+__global__ __launch_bounds__(KN_THREADS) void nn_query_kernel(const float4* __restrict__ sp, const u64* __restrict__ keys, unsigned int N,
+                                                              const unsigned int* __restrict__ bb, const float* __restrict__ queries,
+                                                              const unsigned int* __restrict__ qrows, unsigned int M, float* __restrict__ dist,
+                                                              int* __restrict__ idx) {
+  const long long pl = (long long)blockIdx.x * KN_THREADS + threadIdx.x;
+  if (pl >= (long long)M || bb[6]) return;
+  const size_t row = qrows[pl];
+  const float x[3] = {queries[3 * row], queries[3 * row + 1], queries[3 * row + 2]};
+  if (!(finite_f32(x[0]) && finite_f32(x[1]) && finite_f32(x[2]))) {
+    dist[row] = __int_as_float(0x7fc00000);
+    if (idx) idx[row] = -1;
+    return;
+  }
+  const KnFrame f = kn_frame(bb);
+  float bd = INFINITY;
+  int br = KN_NONE;
+  if (f.degenerate) {
+    nn_scan(sp, 0u, N, x[0], x[1], x[2], bd, br);
+  } else {
+    float t[3], tmax = 0.f;
+    u64 key = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      t[a] = __fsub_rn(x[a], f.mn[a]);
+      tmax = fmaxf(tmax, fabsf(t[a]));
+      key |= kn_spread(kn_quant(t[a], f.scale)) << a;      // a negative t gives cell 0, one beyond the box the last cell
+    }
+    const unsigned int p = kn_lower_bound(keys, 0u, N, key);
+    const unsigned int lo = p >= 4u ? p - 4u : 0u, hi = lo + 8u < N ? lo + 8u : N;
+    nn_scan(sp, lo, hi, x[0], x[1], x[2], bd, br);
+    nn_walk(sp, keys, N, x, t, f.cell, __fadd_rn(f.slack, __fmul_rn(tmax, 1.f / 2097152.f)), bd, br);
+  }
+  dist[row] = (float)sqrt((double)bd);      // the correctly rounded fp32 root: an fp64 root rounded once more is exact for fp32 inputs
+  if (idx) idx[row] = br;
+}
+
+struct NnQueryWs { u64* keys[2]; unsigned int* rows[2]; void* cub; size_t cub_bytes, total; };
+
+NnQueryWs nn_carve(char* base, size_t M) {
+  NnQueryWs w{};
+  Carver c(base);
+  const size_t m = M ? M : 1;
+  w.keys[0] = c.take<u64>(m); w.keys[1] = c.take<u64>(m);
+  w.rows[0] = c.take<unsigned int>(m); w.rows[1] = c.take<unsigned int>(m);
+  w.cub_bytes = sort_pairs_bytes<u64, unsigned int>((int)m, 0, 63);
+  w.cub = c.take<char>(w.cub_bytes ? w.cub_bytes : 4);
+  w.total = c.total();
+  return w;
+}
+
+}  // namespace
+
+size_t wm_nearest_index_bytes(long long N) {
+  if (N < 1 || N >= (1LL << 31)) return 0;
+  return kn_carve(nullptr, (size_t)N).total;
+}
+
+size_t wm_nearest_query_ws_bytes(long long M) {
+  if (M < 0 || M >= (1LL << 31)) return 0;
+  return nn_carve(nullptr, (size_t)M).total;
+}
+
+hipError_t wm_launch_nearest_build(const float* ref, long long N, void* index, int* nonfinite_flag, hipStream_t s) {
+  if (N < 1 || N >= (1LL << 31)) return hipErrorInvalidValue;
+  const KnWs w = kn_carve((char*)index, (size_t)N);
+  const u64* keys = nullptr;
+  hipError_t e = kn_build(ref, N, w, nonfinite_flag, &keys, s);
+  if (e != hipSuccess) return e;
+  if (keys != w.keys[0]) {      // a query finds the sorted keys in the first buffer
+    e = hipMemcpyAsync(w.keys[0], keys, (size_t)N * sizeof(u64), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(nn_seal_kernel, dim3(1), dim3(64), 0, s, w.bb, (const int*)nonfinite_flag, (unsigned int)N);
+  return hipGetLastError();
+}
+
+hipError_t wm_launch_nearest_query(const void* index, long long N, const float* queries, long long M, void* workspace, float* dist, int* idx,
+                                   hipStream_t s) {
+  if (N < 1 || N >= (1LL << 31) || M < 0 || M >= (1LL << 31)) return hipErrorInvalidValue;
+  if (M == 0) return hipSuccess;
+  const KnWs ix = kn_carve((char*)index, (size_t)N);
+  const NnQueryWs w = nn_carve((char*)workspace, (size_t)M);
+  const unsigned nb = blocks_for(M, KN_THREADS);
+  const unsigned int* bb = ix.bb;
+  hipLaunchKernelGGL(kn_keys_kernel, dim3(nb), dim3(KN_THREADS), 0, s, queries, M, bb, (const int*)(bb + 6), w.keys[0], w.rows[0]);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipcub::DoubleBuffer<u64> dk(w.keys[0], w.keys[1]);
+  hipcub::DoubleBuffer<unsigned int> dv(w.rows[0], w.rows[1]);
+  e = sort_pairs(w.cub, w.cub_bytes, dk, dv, (int)M, 0, 63, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(nn_query_kernel, dim3(nb), dim3(KN_THREADS), 0, s, (const float4*)ix.sp, (const u64*)ix.keys[0], (unsigned int)N, bb, queries,
+                     (const unsigned int*)dv.Current(), (unsigned int)M, dist, idx);
   return hipGetLastError();
 }

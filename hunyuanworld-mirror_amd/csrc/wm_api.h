@@ -32,6 +32,27 @@ hipError_t wm_launch_point_ply(const float* points, const unsigned char* colors,
 size_t wm_knn_ws_bytes(long long N, int K);      // 0 for sizes the launcher refuses
 hipError_t wm_launch_knn(const float* points, long long N, int K, void* workspace, float* dist, int* idx, int* nonfinite_flag, hipStream_t s);
 
+// The nearest point of another cloud (knn.hip): build leaves the index of ref [N,3] in `index` (wm_nearest_index_bytes) and writes
+// *nonfinite_flag (device) as wm_launch_knn does; query writes dist [M] and, when idx is not null, idx [M] for queries [M,3] against an index
+// built for the same N (nothing when the build met a non-finite coordinate; NaN and -1 for a non-finite query row).  No synchronisation.
+// 1 <= N < 2^31, 0 <= M < 2^31.
+size_t wm_nearest_index_bytes(long long N);         // 0 for sizes the launchers refuse
+size_t wm_nearest_query_ws_bytes(long long M);      // 0 for sizes the launchers refuse
+hipError_t wm_launch_nearest_build(const float* ref, long long N, void* index, int* nonfinite_flag, hipStream_t s);
+hipError_t wm_launch_nearest_query(const void* index, long long N, const float* queries, long long M, void* workspace, float* dist, int* idx,
+                                   hipStream_t s);
+
+// ------------------------------------------------------------------ point-cloud evaluation (reconmetrics.hip), entries in wm_api_scene.cpp
+// out (device, 4 + WM_STATS_MAX_THRESHOLDS doubles): the mean and the median of dist [M], the mean and the median of |n_a[i] . n_b[idx[i]]|
+// (written only with normals_a), then the counts of dist < thresholds[k] (host array).  No synchronisation.  1 <= M < 2^31.
+size_t wm_cloud_stats_ws_bytes(long long M);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_cloud_stats(const float* dist, const int* idx, long long M, const float* normals_a, const float* normals_b, long long Nb,
+                                 const float* thresholds, int n_thresholds, void* workspace, double* out, hipStream_t s);
+// out (device, 16 doubles): s, R [9] row-major, t [3], the count of kept pairs, the source variance, 0.  mask [P] bytes or null.  1 <= P < 2^31.
+size_t wm_umeyama_ws_bytes(long long P);      // 0 for sizes the launcher refuses
+hipError_t wm_launch_umeyama(const float* src, const float* dst, const unsigned char* mask, long long P, int with_scale, void* workspace, double* out,
+                             hipStream_t s);
+
 // ------------------------------------------------------------------ PNG compression of splats (compress.hip), entries in wm_api_compress.cpp
 // None of these synchronises.  mm [2 C]: C minima, then C maxima.  *nonfinite_flag (device) is set to 1 for a NaN or infinite value and
 // otherwise left as it is: the caller zeroes it once and reads it once.

@@ -1,6 +1,6 @@
 // Scene-level entries of the C ABI (include/wm_hip.h): the caller's steps on either side of the forward, each with its *_workspace_bytes.
 // In file order: splat pruning, the rasteriser, densification, MCMC, the photometric loss, the bilateral grid, the appearance module, the
-// depth loss and point projection, then image ingest and the point masks (with the novel-view path's select and validity mask), the COLMAP hand-off, the nearest neighbours, the fly-through video, the GLB scene and the trainer evaluation.  Each entry
+// depth loss and point projection, then image ingest and the point masks (with the novel-view path's select and validity mask), the COLMAP hand-off, the nearest neighbours, the point-cloud evaluation, the fly-through video, the GLB scene and the trainer evaluation.  Each entry
 // checks its arguments, fills its launcher's args struct, launches on the caller's stream and maps the hipError_t.
 #include <hip/hip_runtime.h>
 
@@ -620,6 +620,40 @@ extern "C" wm_status wm_knn(const float* points, int64_t N, int K, void* workspa
   const size_t need = wm_knn_ws_bytes(N, K);
   if (need == 0 || !points || !workspace || workspace_bytes < need || !dist || !nonfinite_flag) return WM_ERR_INVALID;
   return wm_status_of(wm_launch_knn(points, N, K, workspace, dist, idx, nonfinite_flag, (hipStream_t)stream));
+}
+
+// the nearest point of another cloud: the index once, the queries many times (the kd-tree of a host-side accuracy / completeness evaluation)
+extern "C" size_t wm_nearest_build_workspace_bytes(int64_t N) { return wm_nearest_index_bytes(N); }
+extern "C" wm_status wm_nearest_build(const float* ref, int64_t N, void* index, size_t index_bytes, int32_t* nonfinite_flag, void* stream) {
+  const size_t need = wm_nearest_index_bytes(N);
+  if (need == 0 || !ref || !index || index_bytes < need || !nonfinite_flag) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_nearest_build(ref, N, index, nonfinite_flag, (hipStream_t)stream));
+}
+extern "C" size_t wm_nearest_query_workspace_bytes(int64_t M) { return wm_nearest_query_ws_bytes(M); }
+extern "C" wm_status wm_nearest_query(const void* index, size_t index_bytes, int64_t N, const float* queries, int64_t M, void* workspace,
+                                      size_t workspace_bytes, float* dist, int32_t* idx, void* stream) {
+  const size_t need_index = wm_nearest_index_bytes(N), need = wm_nearest_query_ws_bytes(M);
+  if (need_index == 0 || need == 0 || !index || index_bytes < need_index || !workspace || workspace_bytes < need) return WM_ERR_INVALID;
+  if (M > 0 && (!queries || !dist)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_nearest_query(index, N, queries, M, workspace, dist, idx, (hipStream_t)stream));
+}
+
+// ---------------------------------------------------------------- point-cloud evaluation (reconmetrics.hip)
+extern "C" size_t wm_cloud_stats_workspace_bytes(int64_t M) { return wm_cloud_stats_ws_bytes(M); }
+extern "C" wm_status wm_cloud_stats(const float* dist, const int32_t* idx, int64_t M, const float* normals_a, const float* normals_b, int64_t Nb,
+                                    const float* thresholds, int n_thresholds, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+  const size_t need = wm_cloud_stats_ws_bytes(M);
+  if (need == 0 || !dist || !out || !workspace || workspace_bytes < need) return WM_ERR_INVALID;
+  if (n_thresholds < 0 || n_thresholds > WM_STATS_MAX_THRESHOLDS || (n_thresholds > 0 && !thresholds)) return WM_ERR_INVALID;
+  if (normals_a && (!normals_b || !idx || Nb < 1)) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_cloud_stats(dist, idx, M, normals_a, normals_b, Nb, thresholds, n_thresholds, workspace, out, (hipStream_t)stream));
+}
+extern "C" size_t wm_umeyama_workspace_bytes(int64_t P) { return wm_umeyama_ws_bytes(P); }
+extern "C" wm_status wm_umeyama(const float* src, const float* dst, const unsigned char* mask, int64_t P, int with_scale, void* workspace,
+                                size_t workspace_bytes, double* out, void* stream) {
+  const size_t need = wm_umeyama_ws_bytes(P);
+  if (need == 0 || !src || !dst || !out || !workspace || workspace_bytes < need) return WM_ERR_INVALID;
+  return wm_status_of(wm_launch_umeyama(src, dst, mask, P, with_scale, workspace, out, (hipStream_t)stream));
 }
 
 // ---------------------------------------------------------------- fly-through video (video.hip)

@@ -881,6 +881,53 @@ size_t wm_knn_workspace_bytes(int64_t N, int K);
 wm_status wm_knn(const float* points, int64_t N, int K, void* workspace, size_t workspace_bytes, float* dist, int32_t* idx,
                  int32_t* nonfinite_flag, void* stream);
 
+/* ---- the nearest point of ANOTHER cloud (csrc/knn.hip), the search under a point-cloud evaluation (accuracy / completeness, ICP): an index
+ * built once over ref [N,3] and queried many times.  The reference ships no evaluation code; the semantics are this library's own.
+ * build: ref [N,3] contiguous fp32 on the device; index: index_bytes >= the wm_nearest_build_workspace_bytes value for N (40 bytes per point + the sort's
+ *   scratch), the caller's memory, opaque, valid for this N until it is overwritten.  *nonfinite_flag (one int on the device, written by
+ *   the call): 0, or 1 when a coordinate of ref is NaN or infinite; such an index answers no query (a query call then writes nothing).
+ * query: queries [M,3] contiguous fp32 on the device, anywhere in space.  dist [M] fp32: dist[i] = the minimum over ALL j of
+ *   sqrt(dx dx + dy dy + dz dz), dx = q_i.x - r_j.x, in fp32, every operation rounded on its own (no fused multiply-add), the distance rule of
+ *   wm_knn.  idx [M] int32 (may be NULL): the lowest row j that attains the minimum of the squared fp32 value.  A query row with a NaN or
+ *   infinite coordinate gets dist = NaN and idx = -1; the other rows are unaffected.  Rows are in input order.  M = 0 launches nothing.
+ * Exact: the Morton-sorted cell structure only prunes, and every pruning comparison is conservative in fp32 for a query at any distance
+ * from the box (csrc/knn.hip).  The same input gives the same bits.  Neither call synchronises or runs a host loop that depends on the data.
+ * Worst case: a query costs the points of the cells its best-distance ball touches.  All of ref inside one finest cell (2^-21 of the
+ * extent) is scanned by every query; a query farther away than 10^4 extents sees the whole cloud at one distance and scans it.  Exact both.
+ * workspace of a query: the _workspace_bytes value for M (24 bytes per query + the sort's scratch).
+ * WM_ERR_INVALID, before anything is launched: N < 1, N or M >= 2^31, M < 0, a null pointer other than idx (with M = 0: other than idx,
+ *   queries and dist), index_bytes or workspace_bytes too small. */
+size_t wm_nearest_build_workspace_bytes(int64_t N);
+wm_status wm_nearest_build(const float* ref, int64_t N, void* index, size_t index_bytes, int32_t* nonfinite_flag, void* stream);
+size_t wm_nearest_query_workspace_bytes(int64_t M);
+wm_status wm_nearest_query(const void* index, size_t index_bytes, int64_t N, const float* queries, int64_t M, void* workspace,
+                           size_t workspace_bytes, float* dist, int32_t* idx, void* stream);
+
+/* ---- the reductions of a point-cloud evaluation (csrc/reconmetrics.hip).  Every sum is fp64 in a fixed order that depends on the element
+ * count alone (a two-level sum: threads, then blocks): the same input gives the same bits.  No call synchronises.
+ * wm_cloud_stats: one direction of accuracy / completeness over a result of wm_nearest_query.  dist [M] fp32, idx [M] int32 (read only with
+ *   normals).  out (device, 4 + WM_STATS_MAX_THRESHOLDS doubles): [0] the mean of dist; [1] its median with numpy's rule (the exact order
+ *   statistics of rank floor((M - 1) / 2) and floor(M / 2) by radix selection, their mean in fp64); [2], [3] with normals_a [M,3] and
+ *   normals_b [Nb,3] the mean and median of |n_a[i] . n_b[idx[i]]|, the product in fp32 with every operation rounded on its own, NaN where idx[i]
+ *   is outside 0 .. Nb-1, and left unwritten without normals; [4 + k] the count of dist < thresholds[k], k < n_thresholds <=
+ *   WM_STATS_MAX_THRESHOLDS (thresholds: a HOST array, read before the call returns).  A NaN makes the mean NaN and ranks above +inf.
+ * wm_umeyama: the similarity (s, R, t) that minimises the sum of |dst_i - (s R src_i + t)|^2 over the pairs with mask[i] != 0 (mask [P]
+ *   bytes on the device, or NULL for all): Umeyama's closed form (IEEE TPAMI 13(4), 1991).  src, dst [P,3] fp32.  The count and the two
+ *   means in one pass, the centred cross-covariance and the source variance in a second, the 3 x 3 singular value decomposition by one-sided
+ *   Jacobi rotations on one thread, the last singular direction mirrored when det U det V < 0 so that R is a rotation.  out (device, 16
+ *   doubles): s (1 with with_scale = 0), R [9] row-major, t [3], the count, the source variance, 0.  Fewer than 3 pairs, or collinear ones,
+ *   leave R undetermined (a count of 0 gives NaNs); the caller reads the count.
+ * workspace: the _workspace_bytes values; 0 for sizes the calls refuse.
+ * WM_ERR_INVALID, before anything is launched: M or P < 1 or >= 2^31, n_thresholds outside 0 .. WM_STATS_MAX_THRESHOLDS, a null pointer
+ *   where none is allowed (idx and normals_b with normals_a, thresholds with n_thresholds > 0), Nb < 1 with normals, a too small workspace. */
+#define WM_STATS_MAX_THRESHOLDS 16
+size_t wm_cloud_stats_workspace_bytes(int64_t M);
+wm_status wm_cloud_stats(const float* dist, const int32_t* idx, int64_t M, const float* normals_a, const float* normals_b, int64_t Nb,
+                         const float* thresholds, int n_thresholds, void* workspace, size_t workspace_bytes, double* out, void* stream);
+size_t wm_umeyama_workspace_bytes(int64_t P);
+wm_status wm_umeyama(const float* src, const float* dst, const unsigned char* mask, int64_t P, int with_scale, void* workspace,
+                     size_t workspace_bytes, double* out, void* stream);
+
 /* ---- fly-through video around the rasteriser (csrc/video.hip): what src/utils/render_utils.py:196-368 render_interpolated_video runs per frame
  * beside rasterize_batches.
  *
